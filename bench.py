@@ -7,19 +7,27 @@
 Workload: what BASELINE.json's metric names -- Image + DNA + Text (configs[2]'s per-GPU shape: LoRA ViT-B/16 + LoRA BarcodeBERT +
 LoRA BERT-small), bf16 MFMA GEMMs with f32 accumulation, local batch 256 per GPU, synthetic 224x224 images + 133-token barcodes
 + 20-token texts resident in HBM, InfoNCE over the (all-gathered, for N > 1) batch, backward, gradient all-reduce, fused AdamW.
---no-text runs configs[1] (Image + DNA, the configuration north_star's 40 % target is stated on); the default single-GPU line
+--no-text runs configs[1] (Image + DNA, the configuration north_star's 40 % target is stated on); the single-GPU --full line
 carries that configuration (and configs[4]'s fp8 shape) as `extra`, measured in the same run on the same number of steps.
 One "step" = zero_grad + forward + loss + backward + (all-reduce) + optimizer step; nothing is skipped or cached.
 
-One JSON line is printed by rank 0 (contract in the task statement).  Besides the required keys:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`) with `config`, `host`, for N > 1 `dist`, and
+  step_roofline -- algorithmic FLOPs of the whole step (SURVEY.md 8d: 118.3 GFLOP per I+D pair) / measured step time
+                   against the dense bf16 MFMA peak (no run of its own: derived from the timed steps and the engine clock over them).
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32): `loss` and
+`param.<parameter name>` for every trainable parameter after the last optimizer step.  Inputs and weights are seeded, so two runs
+with the same arguments compare output for output.  Above 60 MB in all (full fine-tuning), each tensor larger than 4096 elements
+is written as a fixed, seeded sample of its flattened elements.
+--full adds what takes runs of its own (the same keys as before the option existed; --no-extras / --no-cpu-baseline trim it):
   roofline      -- the DOMINANT kernel family of the step by time: the bias-free dX GEMMs (dfc1, dproj, dqkv: 70 launches per step,
                    gemm_nt_pers_kernel<EPI_BF16, no bias>), timed live with HIP events on the launch stream in the step's launch mix;
                    `traffic` from the rocprofv3 --pmc passes of that mix (profiles/*.json, --pmc-traffic), never a constant.
   roofline_lowest -- the LOWEST-fraction GEMM family (fc1 + bias + GELU, 24 launches per step), same method.
   roofline_families -- every kernel family that takes more than 2 % of the step (the GEMM families by epilogue, attention forward /
                    backward), each timed live in its own launch mix: TFLOP/s and fraction of the dense bf16 MFMA peak.
-  step_roofline -- algorithmic FLOPs of the whole step (SURVEY.md 8d: 118.3 GFLOP per I+D pair) / measured step time
-                   against the dense bf16 MFMA peak.
+  extra, parity_mode_ms_per_step, exact_mode_ms_per_step, numerics_modes -- the other single-GPU BASELINE shapes and numerics
+                   modes, each a model of its own timed on the same number of steps (default I+D+T line at local batch 256).
   cpu_baseline  -- the CPU oracle (a port; the reference's Python cannot travel to the GPU box) timed on the host
                    cores on a bounded sample of BASELINE configs[0] (I+D, B=8).
 """
@@ -395,6 +403,37 @@ def side_measurement(device, with_text, fp8, B, steps=20, parity=0):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # array data of --dump-outputs; with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- the loss and every trainable
+    parameter after the optimizer step -- as <path>/<name>.npy in float32.  When the set exceeds DUMP_BUDGET_BYTES (full
+    fine-tuning trains every parameter), each tensor larger than 4096 elements is written as a sample of its flattened elements:
+    indices drawn from a generator seeded by the tensor's name, as many as keep the set within the budget, so that two runs with
+    the same arguments write the same elements."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = [("loss", loss.detach().reshape(1))]
+    arrays += [("param." + n, p.detach()) for n, p in model.named_parameters() if p.requires_grad]
+    small = sum(t.numel() for _, t in arrays if t.numel() <= 4096)
+    large = sum(t.numel() for _, t in arrays if t.numel() > 4096)
+    keep = 1.0 if 4 * (small + large) <= DUMP_BUDGET_BYTES else (DUMP_BUDGET_BYTES - 4 * small) / (4 * large)
+    for name, t in arrays:
+        flat = t.float().reshape(-1)
+        if keep < 1.0 and flat.numel() > 4096:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (max(1, int(flat.numel() * keep)),), generator=g).sort().values
+            arr = flat[idx.to(flat.device)].cpu().numpy()
+        else:
+            arr = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+    print(f"[bench] wrote {len(arrays)} arrays to {path}" + ("" if keep == 1.0 else f" (tensors over 4096 elements sampled at {keep:.3f})"),
+          file=sys.stderr, flush=True)
+
+
 def main():
     # stdout carries exactly one line, the JSON result.  Native libraries print there too (RCCL writes a version banner to
     # fd 1 when the first communicator is created), so fd 1 is pointed at stderr for the duration of the run and the result
@@ -413,9 +452,14 @@ def main():
     ap.add_argument("--full-ft", action="store_true", help="disable_lora: true -- train every parameter (SURVEY 8f-4; not a BASELINE config)")
     ap.add_argument("--lr", type=float, default=None, help="AdamW lr (default 1e-3; 1e-6 with --full-ft, the reference's full fine-tuning base lr: random-init towers on noise images collapse under larger steps, tools/ft_dynamics_probe.py)")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every launch from Python instead of replaying the captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (configs[1] I+D at B=256, fp8 trunks at B=512) the "
-                    "default single-GPU line carries as extra keys")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run what takes runs of its own: the roofline / "
+                    "roofline_lowest / roofline_families kernel timings, the side measurements (extra, parity and exact mode) and the "
+                    "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss and trainable parameters "
+                    "as DIR/<name>.npy (float32, at most 64 MB in all; larger sets as fixed seeded samples)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements (configs[1] I+D at B=256, fp8 trunks "
+                    "at B=512, parity and exact mode) and roofline_families")
     ap.add_argument("--pmc-traffic", default=None, help="JSON of the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over the dominant kernel's "
                     "launch mix (tools/scripts/r05_dx_pmc.sh); default profiles/r05_dx_pmc.json")
     a = ap.parse_args()
@@ -646,14 +690,17 @@ def main():
                                "the HIP / ROCr runtime's own helper threads"}
         if dist_info is not None:
             out["dist"] = dist_info
-        out["roofline"] = time_gemm_family("dx", B, device, a.pmc_traffic or DEFAULT_PMC_TRAFFIC["dx"])
-        out["roofline_lowest"] = time_gemm_family("fc1", B, device, DEFAULT_PMC_TRAFFIC["fc1"])
-        if world == 1 and not (a.fp8 or a.full_ft or a.no_extras):
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, loss, model)
+        if a.full:
+            out["roofline"] = time_gemm_family("dx", B, device, a.pmc_traffic or DEFAULT_PMC_TRAFFIC["dx"])
+            out["roofline_lowest"] = time_gemm_family("fc1", B, device, DEFAULT_PMC_TRAFFIC["fc1"])
+        if a.full and world == 1 and not (a.fp8 or a.full_ft or a.no_extras):
             try:
                 out["roofline_families"] = time_families(B, device)
             except Exception as exc:   # noqa: BLE001
                 out["roofline_families"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not force_dist and not (a.no_extras or a.no_text or a.fp8 or a.full_ft or nodrop or B != 256):
+        if a.full and world == 1 and not force_dist and not (a.no_extras or a.no_text or a.fp8 or a.full_ft or nodrop or B != 256):
             # the other single-GPU-measurable BASELINE shapes, so that they are driver-run numbers
             graphed = None
             del opt, model
@@ -687,7 +734,7 @@ def main():
                 out["extra"] = {"error": f"{type(exc).__name__}: {exc}"}
         print(f"[bench] gpu: {ms:.2f} ms/step, {out['value']} pairs/s; host enqueue wall {t_enq / a.steps * 1e3:.2f} ms/step, "
               f"host cpu {host_cpu_s / a.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
