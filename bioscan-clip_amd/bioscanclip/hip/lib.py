@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("BSCLIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libbs
 
 (EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32, EPI_DGELU_BF16, EPI_PATCH_F32, EPI_GELU_FP8, EPI_RESID_BF16,
  EPI_PATCH_BF16) = range(9)
+OPERANDS_FP16 = 0x100   # BSCLIP_OPERANDS_FP16, or-ed into a bsclip_gemm_bf16 epilogue: fp16 operands and 16-bit epilogue values
 KPAD = 64
 LORA_COLS = 8
 

@@ -10,10 +10,11 @@ import torch
 
 from . import lib as _l
 from .lib import (EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_GELU_FP8, EPI_PATCH_BF16, EPI_PATCH_F32,  # noqa: F401
-                  EPI_RESID_BF16, EPI_RESID_F32, KPAD,
+                  EPI_RESID_BF16, EPI_RESID_F32, KPAD, OPERANDS_FP16,
                   EpiArgs, Fp8Args, check)
 
 BF16 = torch.bfloat16
+F16 = torch.float16
 F32 = torch.float32
 
 
@@ -40,14 +41,16 @@ def _rowmajor(t, name):
 
 
 def gemm(a, b, out, epilogue=EPI_BF16, bias=None, resid=None, aux=None, M=None, K=None, dropout=None):
-    """out = epilogue(a[:M, :K] @ b[:, :K].T).  a [M, >=K] bf16, b [N, >=K] bf16 (row strides may exceed K)."""
+    """out = epilogue(a[:M, :K] @ b[:, :K].T).  a [M, >=K], b [N, >=K] (row strides may exceed K), both bf16 or both fp16; with
+    fp16 operands every 16-bit output / residual of the epilogue is fp16 too (BSCLIP_OPERANDS_FP16)."""
     lda, ldb, ldc = _rowmajor(a, "a"), _rowmajor(b, "b"), _rowmajor(out, "out")
-    _req(a.dtype == BF16 and b.dtype == BF16, "gemm operands must be bf16")
+    _req(a.dtype == b.dtype and a.dtype in (BF16, F16), "gemm operands must be both bf16 or both fp16")
+    h16 = a.dtype
     M = a.shape[0] if M is None else M
     K = min(a.shape[1], b.shape[1]) if K is None else K
     N = b.shape[0]
     _req(M <= a.shape[0] and K <= a.shape[1] and K <= b.shape[1], "gemm: M/K exceed operand shapes")
-    want = F32 if epilogue in (EPI_F32, EPI_RESID_F32, EPI_PATCH_F32) else BF16
+    want = F32 if epilogue in (EPI_F32, EPI_RESID_F32, EPI_PATCH_F32) else h16
     if out.dtype != want:
         raise ValueError(f"gemm: out dtype {out.dtype} != {want}")
     if epilogue in (EPI_PATCH_F32, EPI_PATCH_BF16):
@@ -59,7 +62,8 @@ def gemm(a, b, out, epilogue=EPI_BF16, bias=None, resid=None, aux=None, M=None, 
         _req(bias.dtype == F32 and bias.numel() >= N and bias.is_contiguous(), "gemm: bias must be f32 [N]")
         args.bias = bias.data_ptr()
     if resid is not None:
-        _req(resid.dtype == (BF16 if epilogue == EPI_RESID_BF16 else F32), "gemm: resid must be f32 (bf16 for EPI_RESID_BF16)")
+        _req(resid.dtype == (h16 if epilogue == EPI_RESID_BF16 else F32),
+             "gemm: resid must be f32 (for EPI_RESID_BF16 the operands' 16-bit type)")
         need = 197 if epilogue in (EPI_PATCH_F32, EPI_PATCH_BF16) else M
         _req(resid.shape[0] >= need and resid.shape[1] >= N, "gemm: resid too small")
         args.resid = resid.data_ptr()
@@ -71,7 +75,8 @@ def gemm(a, b, out, epilogue=EPI_BF16, bias=None, resid=None, aux=None, M=None, 
     if dropout is not None:  # (p, seed): C = dropout(acc + bias) + resid
         _req(epilogue in (EPI_RESID_F32, EPI_RESID_BF16), "gemm: dropout is only defined for EPI_RESID_F32 / _BF16")
         args.dropout_p, args.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF
-    check(_l.load().bsclip_gemm_bf16(_p(a), lda, _p(b), ldb, _p(out), ldc, M, N, K, epilogue, ctypes.byref(args),
+    fmt = OPERANDS_FP16 if h16 == F16 else 0
+    check(_l.load().bsclip_gemm_bf16(_p(a), lda, _p(b), ldb, _p(out), ldc, M, N, K, epilogue | fmt, ctypes.byref(args),
                                      _stream()))
     return out
 

@@ -46,6 +46,32 @@ __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
 
+// ---- 16-bit operand format as a template parameter: F16 = false is bf16 (the default), true is IEEE fp16 (bsclip_gemm_bf16 with
+// BSCLIP_OPERANDS_FP16).  Buffers, LDS images and DMA paths are the same bytes in both; only the conversions and the MFMA differ.
+// f32 -> fp16 is v_cvt_f16_f32 in the default round-to-nearest-even mode: subnormals kept, overflow to inf (never the packed
+// v_cvt_pkrtz_f16_f32, which rounds toward zero).
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+template <bool F16>
+__device__ __forceinline__ float h2f(bf16_t v) {
+    if constexpr (F16) return (float)__builtin_bit_cast(_Float16, v);
+    else return bf2f(v);
+}
+template <bool F16>
+__device__ __forceinline__ unsigned pack_h2(float lo, float hi) {
+    if constexpr (F16) {
+        const _Float16 l = (_Float16)lo, h = (_Float16)hi;
+        return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
+    } else {
+        return pack_bf2(lo, hi);
+    }
+}
+// v_mfma_f32_16x16x32_{bf16,f16}: same cycles on gfx950; the fragments are 16 bytes of either format
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
 // ---- dropout: counter-based, layout-independent ----------------------------------------------------
 // The decision for logical element `idx` of a site depends only on (seed, idx): every kernel that touches the
 // element (forward epilogue, the backward pass that regenerates the mask, either attention orientation) gets the

@@ -159,10 +159,13 @@ __device__ __forceinline__ void gelu_lut_batch(const char* lut, const f32x4 (&x)
     }
 }
 
+// four 16-bit values (bf16, or fp16 when F16) <-> f32
+template <bool F16 = false>
 __device__ __forceinline__ f32x4 bf4_to_f32(uint2 u) {
-    return f32x4{bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16)};
+    return f32x4{h2f<F16>(u.x & 0xffff), h2f<F16>(u.x >> 16), h2f<F16>(u.y & 0xffff), h2f<F16>(u.y >> 16)};
 }
-__device__ __forceinline__ uint2 f32_to_bf4(f32x4 v) { return uint2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])}; }
+template <bool F16 = false>
+__device__ __forceinline__ uint2 f32_to_bf4(f32x4 v) { return uint2{pack_h2<F16>(v[0], v[1]), pack_h2<F16>(v[2], v[3])}; }
 constexpr bool epi_is_resid(int epi) { return epi == BSCLIP_EPI_RESID_F32 || epi == BSCLIP_EPI_RESID_BF16; }
 constexpr bool epi_is_patch(int epi) { return epi == BSCLIP_EPI_PATCH_F32 || epi == BSCLIP_EPI_PATCH_BF16; }
 constexpr bool epi_out_bf16_from_f32_slab(int epi) {
@@ -170,12 +173,12 @@ constexpr bool epi_out_bf16_from_f32_slab(int epi) {
 }
 
 // v already holds acc (+ bias).  No data-dependent branch guards a load.
-template <int EPI>
+template <int EPI, bool F16 = false>
 __device__ __forceinline__ void epilogue_store(f32x4 v, int m, int n, void* C, int ldc, const EpiArgs& e) {
     if constexpr (EPI == BSCLIP_EPI_BF16) {
         uint2 o;
-        o.x = pack_bf2(v[0], v[1]);
-        o.y = pack_bf2(v[2], v[3]);
+        o.x = pack_h2<F16>(v[0], v[1]);
+        o.y = pack_h2<F16>(v[2], v[3]);
         *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n) = o;
     } else if constexpr (EPI == BSCLIP_EPI_F32) {
         *reinterpret_cast<f32x4*>(static_cast<float*>(C) + (size_t)m * ldc + n) = v;
@@ -189,8 +192,8 @@ __device__ __forceinline__ void epilogue_store(f32x4 v, int m, int n, void* C, i
         if (e.aux)  // store only: gelu'(pre-activation) as 8-bit codes, all the backward pass needs
             *reinterpret_cast<unsigned*>(e.aux + (size_t)m * e.ld_aux + n) = dg8_pack4(dg[0], dg[1], dg[2], dg[3]);
         uint2 o;
-        o.x = pack_bf2(gl[0], gl[1]);
-        o.y = pack_bf2(gl[2], gl[3]);
+        o.x = pack_h2<F16>(gl[0], gl[1]);
+        o.y = pack_h2<F16>(gl[2], gl[3]);
         *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n) = o;
     } else if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
         const f32x4 r = *reinterpret_cast<const f32x4*>(e.resid + (size_t)m * e.ld_resid + n);
@@ -200,8 +203,8 @@ __device__ __forceinline__ void epilogue_store(f32x4 v, int m, int n, void* C, i
     } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
         const f32x4 z = dg8_unpack4(*reinterpret_cast<const unsigned*>(e.aux + (size_t)m * e.ld_aux + n));
         uint2 o;
-        o.x = pack_bf2(v[0] * z[0], v[1] * z[1]);
-        o.y = pack_bf2(v[2] * z[2], v[3] * z[3]);
+        o.x = pack_h2<F16>(v[0] * z[0], v[1] * z[1]);
+        o.y = pack_h2<F16>(v[2] * z[2], v[3] * z[3]);
         *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n) = o;
     } else if constexpr (EPI == BSCLIP_EPI_PATCH_F32) {
         const int b = m / 196, p = m - b * 196;
@@ -211,20 +214,20 @@ __device__ __forceinline__ void epilogue_store(f32x4 v, int m, int n, void* C, i
     } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
         const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(e.resid) + (size_t)m * e.ld_resid + n);
         if (e.drop.thr16) v = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, v);
-        v += bf4_to_f32(r);
-        *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n) = f32_to_bf4(v);
+        v += bf4_to_f32<F16>(r);
+        *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n) = f32_to_bf4<F16>(v);
     } else if constexpr (EPI == BSCLIP_EPI_PATCH_BF16) {
         const int b = m / 196, p = m - b * 196;
         const f32x4 pos = *reinterpret_cast<const f32x4*>(e.resid + (size_t)(1 + p) * e.ld_resid + n);
         v += pos;
-        *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n) = f32_to_bf4(v);
+        *reinterpret_cast<uint2*>(static_cast<bf16_t*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n) = f32_to_bf4<F16>(v);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // generic tile, one barrier per K-tile
 // ---------------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool HAS_BIAS>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool HAS_BIAS, bool F16 = false>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const bf16_t* __restrict__ A, int lda,
                                                                          const bf16_t* __restrict__ B, int ldb,
                                                                          void* __restrict__ C, int ldc, int M, int N,
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const bf
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = mfma16x16x32<F16>(bfr[j], af[i], acc[i][j]);
         }
         __syncthreads();
     }
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const bf
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int n = n0 + wn * WTN + j * 16 + fq * 4;
-                    epilogue_store<EPI>(acc[i][j], m, n, C, ldc, e);
+                    epilogue_store<EPI, F16>(acc[i][j], m, n, C, ldc, e);
                 }
             }
         }
@@ -373,20 +376,23 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const bf
 //   OP 1: the two 8-byte halves feed two v_mfma_f32_16x16x32_fp8_fp8 (bf16 rate: gains the bytes only);
 //   OP 2: the fragments of both half-tiles (32 bytes) feed ONE v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales
 //         (E8M0 127): 2x the bf16 MFMA rate.
+// OP 3 = IEEE fp16 (bsclip_gemm_bf16 | BSCLIP_OPERANDS_FP16): OP 0's loop with v_mfma_f32_16x16x32_f16, and every 16-bit value the
+// epilogue reads or writes (C, RESID_BF16's stream) is fp16.
 // An optional LAST K-tile is bf16 (e.a_aug / e.b_aug, 64 columns): the LoRA branch t . B^T stays in bf16 and is added in the
 // accumulator's units (B_aug rows pre-divided by alpha[n]), then alpha[n] dequantises the sum in the epilogue.
 template <int EPI, bool HAS_BIAS, bool DIAG = false, int ABL = 0, int SCHED = 0, int OP = 0>
 __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restrict__ A, int lda,
                                                           const bf16_t* __restrict__ B, int ldb, void* __restrict__ C,
                                                           int ldc, int M, int N, int K, int tiles_n, EpiArgs e) {
-    static_assert(OP == 0 || (SCHED == 0 && ABL == 0), "fp8 operands: production schedule only");
+    static_assert(OP == 0 || (SCHED == 0 && ABL == 0), "fp8 / fp16 operands: production schedule only");
+    constexpr bool FP8 = OP == 1 || OP == 2, F16 = OP == 3;
     if constexpr (EPI == BSCLIP_EPI_F32 && !HAS_BIAS && OP == 0) {   // split-K slabs (gridDim.y == 1: no-op)
         A += (size_t)blockIdx.y * K;
         B += (size_t)blockIdx.y * K;
         C = static_cast<float*>(C) + (size_t)blockIdx.y * e.split_stride;
     }
     if constexpr (epi_is_resid(EPI)) BSCLIP_DROP_RESOLVE(e.drop);
-    constexpr int ESZ = OP == 0 ? 2 : 1;   // bytes per element of the main operands
+    constexpr int ESZ = FP8 ? 1 : 2;   // bytes per element of the main operands
     constexpr int SET = 65536, HALF = 16384, B_OFF = 32768;
     // main loop 128 KiB; epilogue slabs 2x64x1040 (f32) or 4x64x528 (bf16 x2) = 132 KiB, + 16 KiB GELU table
     __shared__ __attribute__((aligned(16))) char smem[4 * 64 * 528 + (EPI == BSCLIP_EPI_GELU_BF16 || EPI == BSCLIP_EPI_GELU_FP8 ? GELU_LUT_BYTES : 0)];
@@ -412,7 +418,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
             srcB[h][i] = reinterpret_cast<const char*>(B) + (size_t)min(n0 + row, N - 1) * ldb * ESZ + c * 16;
         }
     const int nk_main = K / (BK * 2 / ESZ);
-    const bool aug = OP != 0 && e.a_aug != nullptr;   // wave-uniform
+    const bool aug = FP8 && e.a_aug != nullptr;   // wave-uniform
     const int dma_off = wave * 1024;  // + i*8192 + half*HALF (+ B_OFF) + set*SET
     // the bf16 K-augmentation tile: its per-lane sources are recomputed when it is staged (once per workgroup) instead of
     // living in 16 more VGPRs through the whole loop
@@ -424,7 +430,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
     auto dmaA = [&](int set, int h, int k0) {   // k0 = K-tile index * 128 (byte offset into the row)
         if constexpr (ABL & 4) return;
         char* d = smem + set * SET + h * HALF + dma_off;
-        if (OP != 0 && aug && k0 == nk_main * 128) {
+        if (FP8 && aug && k0 == nk_main * 128) {
             glds16(aug_src(e.a_aug, e.ld_a_aug, m0, M - 1, h, 0), d);
             glds16(aug_src(e.a_aug, e.ld_a_aug, m0, M - 1, h, 1), d + 8192);
         } else {
@@ -435,7 +441,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
     auto dmaB = [&](int set, int h, int k0) {
         if constexpr (ABL & 4) return;
         char* d = smem + set * SET + B_OFF + h * HALF + dma_off;
-        if (OP != 0 && aug && k0 == nk_main * 128) {
+        if (FP8 && aug && k0 == nk_main * 128) {
             glds16(aug_src(e.b_aug, e.ld_b_aug, n0, N - 1, h, 0), d);
             glds16(aug_src(e.b_aug, e.ld_b_aug, n0, N - 1, h, 1), d + 8192);
         } else {
@@ -513,10 +519,10 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                     fb[ni][ks][j] = *reinterpret_cast<const bf16x8*>(base + ((b_off ^ (ks << 6)) + (32 * ni + 16 * j) * ROW_BYTES));
         }
     };
-    // BF16TILE (compile-time tag): bf16 MFMAs -- always for OP 0, for the peeled K-augmentation tile of the fp8 builds
+    // BF16TILE (compile-time tag): 16-bit MFMAs -- always for OP 0 / 3, for the peeled bf16 K-augmentation tile of the fp8 builds
     auto mma = [&](int mi, int ni, auto bf16_tag = std::true_type{}) {
         if constexpr (ABL & 1) return;
-        constexpr bool BF16TILE = OP == 0 || decltype(bf16_tag)::value;
+        constexpr bool BF16TILE = !FP8 || decltype(bf16_tag)::value;
         __builtin_amdgcn_s_setprio(1);
         if constexpr (BF16TILE && OP == 2) {
 #pragma unroll
@@ -538,7 +544,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j], 0, 0, 0);
+                        acc[mi][ni][i][j] = mfma16x16x32<F16>(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j]);
         } else if constexpr (OP == 1) {
             typedef long i64x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -782,7 +788,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
             mma(0, 1, tag);
             PP_BARRIER();
         };
-        if constexpr (OP == 0) {
+        if constexpr (!FP8) {
             for (int t = 0; t < nk; ++t) k_tile(t, std::true_type{});
         } else {  // fp8 tiles, then the peeled bf16 K-augmentation tile (same schedule, bf16 MFMAs)
             for (int t = 0; t < nk_main; ++t) k_tile(t, std::false_type{});
@@ -805,7 +811,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
             if constexpr (HAS_BIAS)
                 bias[ni][j] = *reinterpret_cast<const f32x4*>(e.bias + n0 + 64 * wc + 32 * ni + 16 * j + fq * 4);
         }
-    if constexpr (OP != 0) {  // dequantise: alpha[n] = activation scale x weight-row scale
+    if constexpr (FP8) {  // dequantise: alpha[n] = activation scale x weight-row scale
         f32x4 al[2][2];
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
@@ -1015,11 +1021,11 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                                 pack_fp8x4(gl0[0], gl0[1], gl1[0], gl1[1]);
                             continue;
                         }
-                        o.x = pack_bf2(gl0[0], gl0[1]);
-                        o.y = pack_bf2(gl1[0], gl1[1]);
+                        o.x = pack_h2<F16>(gl0[0], gl0[1]);
+                        o.y = pack_h2<F16>(gl1[0], gl1[1]);
                     } else {
-                        o.x = pack_bf2(v[0], v[1]);
-                        o.y = pack_bf2(v[2], v[3]);
+                        o.x = pack_h2<F16>(v[0], v[1]);
+                        o.y = pack_h2<F16>(v[2], v[3]);
                     }
                     *reinterpret_cast<uint2*>((g ? smem + 64 * SB : smem) + off) = o;
                 }
@@ -1082,7 +1088,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                 if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
                     R[it] = *reinterpret_cast<const f32x4*>(e.resid + (size_t)m * e.ld_resid + n);
                 } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
-                    R[it] = bf4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(e.resid) + (size_t)m * e.ld_resid + n));
+                    R[it] = bf4_to_f32<F16>(*reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(e.resid) + (size_t)m * e.ld_resid + n));
                 } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
                     R[it] = dg8_unpack4(*reinterpret_cast<const unsigned*>(e.aux + (size_t)m * e.ld_aux + n));
                 } else if constexpr (epi_is_patch(EPI)) {
@@ -1109,8 +1115,8 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                     } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
                         v *= R[it];
                         uint2 o;
-                        o.x = pack_bf2(v[0], v[1]);
-                        o.y = pack_bf2(v[2], v[3]);
+                        o.x = pack_h2<F16>(v[0], v[1]);
+                        o.y = pack_h2<F16>(v[2], v[3]);
                         nt_store(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, o);
                     } else if constexpr (EPI == BSCLIP_EPI_PATCH_F32) {
                         const int b = m / 196, p = m - b * 196;
@@ -1119,11 +1125,11 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                     } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
                         if (e.drop.thr16) v = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, v);
                         v += R[it];
-                        nt_store(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, f32_to_bf4(v));
+                        nt_store(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, f32_to_bf4<F16>(v));
                     } else if constexpr (EPI == BSCLIP_EPI_PATCH_BF16) {
                         const int b = m / 196, p = m - b * 196;
                         v += R[it];
-                        nt_store(static_cast<bf16_t*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n, f32_to_bf4(v));
+                        nt_store(static_cast<bf16_t*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n, f32_to_bf4<F16>(v));
                     }
                 }
             }
@@ -1158,25 +1164,28 @@ const bool g_duo_off = !(getenv("BSCLIP_GEMM_DUO") && atoi(getenv("BSCLIP_GEMM_D
 const bool g_pers_off = getenv("BSCLIP_GEMM_PERSISTENT") && atoi(getenv("BSCLIP_GEMM_PERSISTENT")) == 0;   // A/B switch
 [[maybe_unused]] int g_diag_ablate = 0;  // tools/gemm_ablate.py: which parts of the K loop the diagnostic EPI_BF16 build leaves out
 
-template <int BM, int BN, int WM, int WN, int EPI, bool HB>
+template <int BM, int BN, int WM, int WN, int EPI, bool HB, bool F16>
 void launch_cfg(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
                 const EpiArgs& e, hipStream_t s) {
     const int tiles_m = ceil_div(M, BM), tiles_n = N / BN;
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, EPI, HB>), dim3(tiles_m * tiles_n), dim3(WM * WN * 64), 0, s, A,
+    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, EPI, HB, F16>), dim3(tiles_m * tiles_n), dim3(WM * WN * 64), 0, s, A,
                        lda, B, ldb, C, ldc, M, N, K, tiles_n, e);
 }
 
 bool g_lut_ready = false;
 
-template <int EPI, bool HB, int SCHED = 0>
+template <int EPI, bool HB, bool F16, int SCHED = 0>
 void launch_pp(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
                const EpiArgs& e, hipStream_t s) {
     const int tiles_m = ceil_div(M, 256), tiles_n = N / 256;
-    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, HB, false, 0, SCHED>), dim3(tiles_m * tiles_n), dim3(512), 0, s, A, lda, B,
+    // fp16 (OP 3) has the production schedule only
+    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, HB, false, 0, F16 ? 0 : SCHED, F16 ? 3 : 0>), dim3(tiles_m * tiles_n), dim3(512), 0, s, A, lda, B,
                        ldb, C, ldc, M, N, K, tiles_n, e);
 }
 
-template <int EPI, bool HB>
+// F16: fp16 operands (BSCLIP_OPERANDS_FP16).  The same tile selection as bf16, except that the duo kernel (bsclip_gemm_set_tile(5),
+// BSCLIP_GEMM_DUO=1) has no fp16 form: the ping-pong kernel takes its shapes.
+template <int EPI, bool HB, bool F16>
 void launch_epi(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
                 const EpiArgs& e, hipStream_t s) {
     if (EPI == BSCLIP_EPI_GELU_BF16 && !g_lut_ready) {  // once per process, stream-ordered ahead of the first consumer
@@ -1202,26 +1211,29 @@ void launch_epi(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int
         // workgroup has more than one tile to walk (g_pers_max_k / g_pers_min_tiles above)
         if (tile == 4 && pers_supported(EPI) && K <= g_pers_max_k && K >= 2 * BK && t256 >= g_pers_min_tiles && !g_pers_off) tile = 8;
     }
+    if (F16 && tile == 5) tile = 4;
     if ((tile == 3 || tile == 4 || tile == 6 || tile == 7 || tile == 8) && N % 256 != 0) tile = 2;
     switch (tile) {
-        case 4: launch_pp<EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
-        case 5: launch_duo<EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
+        case 4: launch_pp<EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
+        case 5:
+            if constexpr (!F16) launch_duo<EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+            break;
         case 8:
             if constexpr (pers_supported(EPI)) {
                 if (K >= 2 * BK && (size_t)M * lda * 2 < (1ull << 32) && (size_t)N * ldb * 2 < (1ull << 32)) {
-                    launch_pers<EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+                    launch_pers<EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
                     break;
                 }
             }
-            launch_pp<EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+            launch_pp<EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
             break;
 #ifdef BSCLIP_DIAG
-        case 6: launch_pp<EPI, HB, 1>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;  // two-tiles-ahead DMA (comparison)
-        case 7: launch_pp<EPI, HB, 2>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;  // four barriers per K-tile (experimental)
+        case 6: launch_pp<EPI, HB, F16, 1>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;  // two-tiles-ahead DMA (comparison)
+        case 7: launch_pp<EPI, HB, F16, 2>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;  // four barriers per K-tile (experimental)
 #endif
-        case 3: launch_cfg<256, 256, 2, 4, EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
-        case 2: launch_cfg<256, 128, 4, 2, EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
-        default: launch_cfg<128, 128, 2, 2, EPI, HB>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
+        case 3: launch_cfg<256, 256, 2, 4, EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
+        case 2: launch_cfg<256, 128, 4, 2, EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
+        default: launch_cfg<128, 128, 2, 2, EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
     }
 }
 
@@ -1239,9 +1251,14 @@ void launch_f8(const void* A, int lda, const void* B, int ldb, void* C, int ldc,
 
 template <int EPI>
 void launch_bias(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
-                 const EpiArgs& e, hipStream_t s) {
-    if (e.bias) launch_epi<EPI, true>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
-    else launch_epi<EPI, false>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+                 const EpiArgs& e, hipStream_t s, bool f16) {
+    if (f16) {
+        if (e.bias) launch_epi<EPI, true, true>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+        else launch_epi<EPI, false, true>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+    } else {
+        if (e.bias) launch_epi<EPI, true, false>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+        else launch_epi<EPI, false, false>(A, lda, B, ldb, C, ldc, M, N, K, e, s);
+    }
 }
 
 }  // namespace
@@ -1412,6 +1429,8 @@ extern "C" int bsclip_epi_args_size(void) { return (int)sizeof(bsclip_epi_args);
 extern "C" int bsclip_gemm_bf16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                                 int epilogue, const bsclip_epi_args* args, void* stream) {
     BSCLIP_REQUIRE(A && B && C, "bsclip_gemm_bf16: null operand");
+    const bool f16 = (epilogue & BSCLIP_OPERANDS_FP16) != 0;   // fp16 operands and 16-bit epilogue values (include/bsclip.h)
+    epilogue &= ~BSCLIP_OPERANDS_FP16;
     BSCLIP_REQUIRE(M > 0 && N > 0 && K > 0, "bsclip_gemm_bf16: bad shape M=%d N=%d K=%d", M, N, K);
     BSCLIP_REQUIRE(K % 64 == 0, "bsclip_gemm_bf16: K=%d must be a multiple of 64", K);
     BSCLIP_REQUIRE(N % 128 == 0, "bsclip_gemm_bf16: N=%d must be a multiple of 128", N);
@@ -1443,29 +1462,29 @@ extern "C" int bsclip_gemm_bf16(const void* A, int lda, const void* B, int ldb, 
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
     switch (epilogue) {
-        case BSCLIP_EPI_BF16: launch_bias<BSCLIP_EPI_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s); break;
-        case BSCLIP_EPI_F32: launch_bias<BSCLIP_EPI_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s); break;
-        case BSCLIP_EPI_GELU_BF16: launch_bias<BSCLIP_EPI_GELU_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s); break;
+        case BSCLIP_EPI_BF16: launch_bias<BSCLIP_EPI_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16); break;
+        case BSCLIP_EPI_F32: launch_bias<BSCLIP_EPI_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16); break;
+        case BSCLIP_EPI_GELU_BF16: launch_bias<BSCLIP_EPI_GELU_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16); break;
         case BSCLIP_EPI_RESID_F32:
             BSCLIP_REQUIRE(e.resid && e.ld_resid >= N, "bsclip_gemm_bf16: RESID needs resid/ld_resid");
-            launch_bias<BSCLIP_EPI_RESID_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s);
+            launch_bias<BSCLIP_EPI_RESID_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         case BSCLIP_EPI_DGELU_BF16:
             BSCLIP_REQUIRE(e.aux && e.ld_aux >= N, "bsclip_gemm_bf16: DGELU needs aux/ld_aux");
-            launch_bias<BSCLIP_EPI_DGELU_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s);
+            launch_bias<BSCLIP_EPI_DGELU_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         case BSCLIP_EPI_PATCH_F32:
             BSCLIP_REQUIRE(e.resid && e.ld_resid >= N && M % 196 == 0, "bsclip_gemm_bf16: PATCH needs pos, M%%196==0");
-            launch_bias<BSCLIP_EPI_PATCH_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s);
+            launch_bias<BSCLIP_EPI_PATCH_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         case BSCLIP_EPI_RESID_BF16:
             BSCLIP_REQUIRE(e.resid && e.ld_resid >= N && e.ld_resid % 4 == 0 && (((uintptr_t)e.resid) & 7) == 0,
                            "bsclip_gemm_bf16: RESID_BF16 needs resid (bf16, 8-byte aligned rows) / ld_resid");
-            launch_bias<BSCLIP_EPI_RESID_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s);
+            launch_bias<BSCLIP_EPI_RESID_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         case BSCLIP_EPI_PATCH_BF16:
             BSCLIP_REQUIRE(e.resid && e.ld_resid >= N && M % 196 == 0, "bsclip_gemm_bf16: PATCH needs pos, M%%196==0");
-            launch_bias<BSCLIP_EPI_PATCH_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s);
+            launch_bias<BSCLIP_EPI_PATCH_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         default: BSCLIP_REQUIRE(false, "bsclip_gemm_bf16: unknown epilogue %d", epilogue);
     }

@@ -36,7 +36,8 @@ __device__ __forceinline__ void pers_store(void* p, T v, bool skip = false) {
     else *static_cast<T*>(p) = v;
 }
 
-template <int EPI, bool HAS_BIAS, bool DIAG = false, bool NT = false>
+// F16: IEEE fp16 operands and 16-bit epilogue values (gemm.hip, OP 3 of the ping-pong kernel)
+template <int EPI, bool HAS_BIAS, bool DIAG = false, bool NT = false, bool F16 = false>
 __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restrict__ A, int lda,
                                                             const bf16_t* __restrict__ B, int ldb, void* __restrict__ C,
                                                             int ldc, int M, int N, int K, int tiles_n, int ntiles, EpiArgs e) {
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j], 0, 0, 0);
+                    acc[mi][ni][i][j] = mfma16x16x32<F16>(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j]);
         __builtin_amdgcn_s_setprio(0);
     };
 #define PERS_BARRIER()                         \
@@ -315,11 +316,11 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                             if constexpr (GELU) {
                                 *reinterpret_cast<unsigned*>(slab2 + (16 * i2 + fre) * S8 + col) =
                                     dg8_pack4(dg8_f32x2{dg[k][0], dg[k][1]}, dg8_f32x2{dg[k][2], dg[k][3]});
-                                o.x = pack_bf2(gl[k][0], gl[k][1]);
-                                o.y = pack_bf2(gl[k][2], gl[k][3]);
+                                o.x = pack_h2<F16>(gl[k][0], gl[k][1]);
+                                o.y = pack_h2<F16>(gl[k][2], gl[k][3]);
                             } else {
-                                o.x = pack_bf2(x[k][0], x[k][1]);
-                                o.y = pack_bf2(x[k][2], x[k][3]);
+                                o.x = pack_h2<F16>(x[k][0], x[k][1]);
+                                o.y = pack_h2<F16>(x[k][2], x[k][3]);
                             }
                             *reinterpret_cast<uint2*>(slab + (16 * i2 + fre) * SB + col * 2) = o;
                         }
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                 }
             };
             auto cooked = [&](const raw_t& r) -> f32x4 {
-                if constexpr (RAW2) return bf4_to_f32(r);
+                if constexpr (RAW2) return bf4_to_f32<F16>(r);
                 else if constexpr (RAW1) return dg8_unpack4(r);
                 else return r;
             };
@@ -407,14 +408,14 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                         } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
                             x *= cooked(R[it]);
                             {
-                                const uint2 o = f32_to_bf4(x);
+                                const uint2 o = f32_to_bf4<F16>(x);
                                 pers_store<NT>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, pers_u32x2{o.x, o.y}, abl_st);
                             }
                         } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
                             if (e.drop.thr16) x = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, x);
                             x += cooked(R[it]);
                             {
-                                const uint2 o = f32_to_bf4(x);
+                                const uint2 o = f32_to_bf4<F16>(x);
                                 pers_store<NT>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, pers_u32x2{o.x, o.y}, abl_st);
                             }
                         }
@@ -468,7 +469,7 @@ const bool g_pers_nt = !(getenv("BSCLIP_GEMM_NT") && atoi(getenv("BSCLIP_GEMM_NT
 const int g_pers_gw = getenv("BSCLIP_GEMM_GW") ? atoi(getenv("BSCLIP_GEMM_GW")) : 0;   // experiment: super-column width
 int g_pers_grid = getenv("BSCLIP_GEMM_WGS") ? atoi(getenv("BSCLIP_GEMM_WGS")) : 0;   // bsclip_gemm_set_persistent_grid: workgroups of the persistent launch, 0 = one per CU
 
-template <int EPI, bool HB>
+template <int EPI, bool HB, bool F16 = false>
 void launch_pers(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K, const EpiArgs& e_in,
                  hipStream_t s) {
     static int cus = 0;
@@ -492,9 +493,9 @@ void launch_pers(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, in
                 }
     }
     if (g_pers_nt)
-        hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, HB, false, true>), dim3(nt < wgs ? nt : wgs), dim3(512), 0, s, A, lda, B, ldb, C,
+        hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, HB, false, true, F16>), dim3(nt < wgs ? nt : wgs), dim3(512), 0, s, A, lda, B, ldb, C,
                            ldc, M, N, K, tiles_n, nt, e);
     else
-        hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, HB>), dim3(nt < wgs ? nt : wgs), dim3(512), 0, s, A, lda, B, ldb, C, ldc, M, N,
+        hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, HB, false, false, F16>), dim3(nt < wgs ? nt : wgs), dim3(512), 0, s, A, lda, B, ldb, C, ldc, M, N,
                            K, tiles_n, nt, e);
 }

@@ -70,6 +70,12 @@ enum bsclip_epilogue {
     BSCLIP_EPI_RESID_BF16 = 7, /* C bf16 = acc + bias + resid, resid bf16 [M, ld_resid] (+ dropout as RESID_F32)  */
     BSCLIP_EPI_PATCH_BF16 = 8  /* as PATCH_F32 with a bf16 C (pos_embed stays f32)                         */
 };
+/* fp16 operands: bsclip_gemm_bf16 with (epilogue | BSCLIP_OPERANDS_FP16) takes A and B as IEEE fp16 (v_mfma_f32_16x16x32_f16,
+ * the bf16 form's rate) and every 16-bit value of the epilogue -- the C of the *_BF16 epilogues, RESID_BF16's resid -- is fp16 as
+ * well; f32 values and the 8-bit gelu' codes are unchanged.  Conversions round to nearest even, keep subnormals and overflow to
+ * +-inf.  Same requirements as the bf16 form; the LoRA branch rides in K as there.  Library releases before this flag reject it
+ * (unknown epilogue). */
+#define BSCLIP_OPERANDS_FP16 0x100
 typedef struct bsclip_epi_args {
     uint32_t struct_size; /* = sizeof(bsclip_epi_args) = bsclip_epi_args_size(); a mismatch is rejected (ABI drift guard) */
     const float* bias;    /* [N] or NULL */
