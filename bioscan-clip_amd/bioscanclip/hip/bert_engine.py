@@ -2,7 +2,7 @@
 (language_encoder.py:87-89)."""
 import torch
 
-from .engine import BertEngine, run_encoder, wants_fp8, wants_full_ft
+from .engine import BertEngine, run_encoder, wants_fp8, wants_fp16, wants_full_ft
 
 
 def _need_gpu(t, who):
@@ -18,7 +18,7 @@ def barcode_bert_forward(module, ids):
         if wants_full_ft(module):
             from .engine_ft import BertEngineFT
             return BertEngineFT(m.bert, "mlm_softmax_mean", heads, ids.device)
-        return BertEngine(m.bert, "mlm_softmax_mean", heads, ids.device, fp8=wants_fp8(module))
+        return BertEngine(m.bert, "mlm_softmax_mean", heads, ids.device, fp8=wants_fp8(module), fp16=wants_fp16(module))
     # the reference passes input_ids only: token_type 0, no attention mask
     return run_encoder(module, build, (ids.to(torch.int64), None, None))
 
@@ -30,7 +30,7 @@ def bert_text_forward(module, x):
         if wants_full_ft(module):
             from .engine_ft import BertEngineFT
             return BertEngineFT(module.lora_bert, "mean_proj", (module.proj,), ids.device)
-        return BertEngine(module.lora_bert, "mean_proj", (module.proj,), ids.device)
+        return BertEngine(module.lora_bert, "mean_proj", (module.proj,), ids.device, fp16=wants_fp16(module))
     tt = x.get("token_type_ids")
     am = x.get("attention_mask")
     return run_encoder(module, build, (ids.to(torch.int64), None if tt is None else tt.to(torch.int64),

@@ -22,6 +22,7 @@ from .lib import (EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_GELU_FP8
                   EPI_RESID_F32, KPAD)
 
 BF16 = torch.bfloat16
+F16 = torch.float16
 F32 = torch.float32
 # Residual-GRADIENT stream dtype of the LoRA-regime backward (the gradient that flows down the skip connections, read and
 # written by every LayerNorm backward): "bf16" halves its bytes (LN backward is HBM-bound: 16 -> 10-12 bytes per element);
@@ -200,17 +201,18 @@ class FlatParams:
                 p.grad = self.grad[o:o + p.numel()].view(p.shape)
 
 
-def _pack_qkv(w_qkv, b_qkv, H, dev):
-    """W_aug bf16 [3H, H+KPAD] (LoRA-B columns refreshed every step) and W^T bf16 [H, 3H] for dX."""
+def _pack_qkv(w_qkv, b_qkv, H, dev, h16=BF16):
+    """W_aug [3H, H+KPAD] (LoRA-B columns refreshed every step) and W^T [H, 3H] for dX, both in the 16-bit format h16.  An fp16
+    engine runs no backward: it gets no transposed copy (None)."""
     w = w_qkv.detach().to(dev, F32)
-    waug = torch.zeros(3 * H, H + KPAD, dtype=BF16, device=dev)
-    waug[:, :H] = w.to(BF16)
-    return waug, w.t().contiguous().to(BF16), _f32(b_qkv, dev)
+    waug = torch.zeros(3 * H, H + KPAD, dtype=h16, device=dev)
+    waug[:, :H] = w.to(h16)
+    return waug, None if h16 == F16 else w.t().contiguous().to(BF16), _f32(b_qkv, dev)
 
 
-def _pack_linear(lin, dev):
+def _pack_linear(lin, dev, h16=BF16):
     w = lin.weight.detach().to(dev, F32)
-    return w.to(BF16).contiguous(), w.t().contiguous().to(BF16), _f32(lin.bias, dev)
+    return w.to(h16).contiguous(), None if h16 == F16 else w.t().contiguous().to(BF16), _f32(lin.bias, dev)
 
 
 class _Layer:
@@ -269,7 +271,7 @@ class EncoderEngineBase:
             self._waug_table = (torch.tensor(rows, dtype=torch.int64, device=self.device).reshape(-1, 3).contiguous(), len(rows), lds.pop())
         table, n, ld_w = self._waug_table
         if n:
-            ops.waug_set_lora_layers(table, n, ld_w, self.H)
+            ops.waug_set_lora_layers(table, n, ld_w, self.H, dtype=self.h16)
         if self.fp8:  # LoRA-B columns of the bf16 K-augmentation tile, in the fp8 accumulator's units
             for l, lay in enumerate(self.layers):
                 b = self.lora_b(l)
@@ -277,6 +279,19 @@ class EncoderEngineBase:
                     ops.lora_baug_set(lay.baug, self.H, b[0], b[1], lay.s_qkv)
 
     fp8 = False
+    fp16 = False
+    h16 = BF16
+
+    def _set_format(self, fp16):
+        """fp16 operands (set_operand_format): every frozen weight the forward reads, the head weight's per-forward cast and the
+        workspace's 16-bit buffers are IEEE fp16; the kernels get BSCLIP_OPERANDS_FP16.  Inference only in this release."""
+        self.fp16 = bool(fp16)
+        self.h16 = F16 if self.fp16 else BF16
+
+    def _no_fp16_backward(self):
+        if self.fp16:
+            raise RuntimeError(f"{type(self).__name__}: the fp16-operand engines are inference-only (the fp16 backward is not built "
+                               "yet): run the encoder under eval() and torch.no_grad(), or set_operand_format(model, 'bf16')")
 
     # ------------------------------------------------------------------------------ exact mode (BSCLIP_PARITY=2)
     def exact(self):
@@ -339,20 +354,22 @@ class EncoderEngineBase:
 class ViTEngine(EncoderEngineBase):
     """LoRA ViT-B/16 forward/backward (reference image_encoder.py:15-109 over timm vit_base_patch16_224)."""
 
-    def __init__(self, module, device, fp8=False):
+    def __init__(self, module, device, fp8=False, fp16=False):
         vit = module.lora_vit
         self.fp8 = bool(fp8)
+        self._set_format(fp16)
+        h16 = self.h16
         self.device = dev = device
         self.H = H = vit.blocks[0].norm1.weight.numel()
         self.heads = vit.blocks[0].attn.num_heads
         self.S = vit.pos_embed.shape[1]
         assert H == 768 and self.S == 197 and vit.patch_embed.proj.weight.shape[-1] == 16, \
             "HIP ViT engine is built for vit_base_patch16_224"
-        self.w_patch = _bf16(vit.patch_embed.proj.weight.reshape(H, -1), dev)
-        # split-bf16 patch embedding (PATCH_SPLIT): the weight as [hi | hi | lo] against im2col rows [hi | lo | hi]
+        self.w_patch = vit.patch_embed.proj.weight.detach().reshape(H, -1).to(dev, F32).to(h16).contiguous()
+        # split-bf16 patch embedding (PATCH_SPLIT): the weight as [hi | hi | lo] against im2col rows [hi | lo | hi] (fp16 parts in fp16 mode)
         w32 = vit.patch_embed.proj.weight.detach().reshape(H, -1).to(dev, F32)
-        w_hi = w32.to(BF16)
-        self.w_patch3 = torch.cat([w_hi, w_hi, (w32 - w_hi.to(F32)).to(BF16)], dim=1).contiguous()
+        w_hi = w32.to(h16)
+        self.w_patch3 = torch.cat([w_hi, w_hi, (w32 - w_hi.to(F32)).to(h16)], dim=1).contiguous()
         self.b_patch = _f32(vit.patch_embed.proj.bias, dev)
         self.cls = _f32(vit.cls_token.reshape(-1), dev)
         self.pos = _f32(vit.pos_embed.reshape(self.S, H), dev)
@@ -366,13 +383,13 @@ class ViTEngine(EncoderEngineBase):
             else:
                 base = q
                 qv.append(None)
-            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(base.weight, base.bias, H, dev)
+            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(base.weight, base.bias, H, dev, h16)
             lay.src = (base.weight, blk.attn.proj.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight)   # f32 masters (exact forward)
             lay.ln1 = (_f32(blk.norm1.weight, dev), _f32(blk.norm1.bias, dev))
             lay.ln2 = (_f32(blk.norm2.weight, dev), _f32(blk.norm2.bias, dev))
-            lay.w_proj, lay.w_proj_t, lay.b_proj = _pack_linear(blk.attn.proj, dev)
-            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(blk.mlp.fc1, dev)
-            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(blk.mlp.fc2, dev)
+            lay.w_proj, lay.w_proj_t, lay.b_proj = _pack_linear(blk.attn.proj, dev, h16)
+            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(blk.mlp.fc1, dev, h16)
+            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(blk.mlp.fc2, dev, h16)
             if self.fp8:
                 self._pack_fp8(lay, base.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight, dev)
             self.layers.append(lay)
@@ -381,8 +398,8 @@ class ViTEngine(EncoderEngineBase):
         self.out_dim = vit.head.weight.shape[0]
         assert self.out_dim % 128 == 0, "head width must be a multiple of 128 for the HIP GEMM"
         self._setup_lora(qv, H, dev, [vit.head.weight, vit.head.bias])
-        self.w_head_bf = torch.empty(self.out_dim, H, dtype=BF16, device=dev)
-        self.w_head_t = torch.empty(H, self.out_dim, dtype=BF16, device=dev)
+        self.w_head_bf = torch.empty(self.out_dim, H, dtype=h16, device=dev)     # the head weight in the operand format, cast every forward
+        self.w_head_t = None if self.fp16 else torch.empty(H, self.out_dim, dtype=BF16, device=dev)
         self.ws = None
 
     # ------------------------------------------------------------------------------------------ workspace
@@ -391,7 +408,8 @@ class ViTEngine(EncoderEngineBase):
             return self.ws
         dev, H, S, L, FF = self.device, self.H, self.S, len(self.layers), self.FF
         M = B * S
-        z = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
+        h16 = self.h16     # the 16-bit operand buffers (and the 16-bit residual stream) are fp16 in an fp16 engine
+        z = lambda *s, dt=h16: torch.empty(*s, dtype=dt, device=dev)
         ws = {"B": B, "M": M, "gen": next(_WS_GEN)}
         ws["cols"] = z(B * 196, 3 * H if (PATCH_SPLIT and not self.full_ft) else H)
         rb = ws["resid_bf16"] = RESID_STREAM_BF16 and not self.full_ft and not self.fp8
@@ -409,7 +427,7 @@ class ViTEngine(EncoderEngineBase):
             ws["dcls32"] = z(B, H, dt=F32)
             ws["t3a"], ws["t3b"] = z(self.out_dim * 3 * Bq), z(H * 3 * Bq)         # dW operands of the head
             ws["wheadT3"] = z(H * 3 * self.out_dim)
-        ws["x"] = [z(M, H, dt=BF16 if rb else F32) for _ in range(2 * L + 1)]   # residual stream after every sub-layer
+        ws["x"] = [z(M, H, dt=h16 if rb else F32) for _ in range(2 * L + 1)]   # residual stream after every sub-layer
         ws["h1"] = [z(M, H + KPAD) for _ in range(L)]                 # LN1 output + LoRA t (QKV operand)
         ws["st1"] = [z(M, 2, dt=F32) for _ in range(L)]
         ws["st2"] = [z(M, 2, dt=F32) for _ in range(L)]
@@ -428,6 +446,10 @@ class ViTEngine(EncoderEngineBase):
             ws["h2_8"], ws["act8"] = z(M, H, dt=ops.FP8), z(M, FF, dt=ops.FP8)
         ws["clsn"] = z(B, H)
         ws["st_f"] = z(B, 2, dt=F32)
+        ws["h2_c"], ws["act_c"], ws["z_c"], ws["st_c"] = z(B, H), z(B, FF), z(B, FF, dt=torch.uint8), z(B, 2, dt=F32)   # last-block token-0 path
+        if self.fp16:    # inference only: no backward temporaries
+            self.ws = ws
+            return ws
         # backward temporaries
         ws["grad_bf16"] = GRAD_STREAM_BF16 and not self.full_ft
         ws["dx"] = None if ws["grad_bf16"] else torch.zeros(M, H, dtype=F32, device=dev)
@@ -443,8 +465,7 @@ class ViTEngine(EncoderEngineBase):
         ws["dout_t"] = torch.zeros(self.out_dim, Bp, dtype=BF16, device=dev)
         ws["clsn_t"] = torch.zeros(H, Bp, dtype=BF16, device=dev)
         ws["dclsn"] = z(B, H)
-        ws["dz_c"], ws["dh_c"], ws["st_c"] = z(B, FF), z(B, H), z(B, 2, dt=F32)   # last-block token-0 path
-        ws["h2_c"], ws["act_c"], ws["z_c"] = z(B, H), z(B, FF), z(B, FF, dt=torch.uint8)
+        ws["dz_c"], ws["dh_c"] = z(B, FF), z(B, H)
         self.ws = ws
         return ws
 
@@ -565,6 +586,7 @@ class ViTEngine(EncoderEngineBase):
 
     # ------------------------------------------------------------------------------------------- backward
     def backward(self, dout):
+        self._no_fp16_backward()
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
@@ -693,8 +715,10 @@ class BertEngine(EncoderEngineBase):
       'mean_proj'        : mean over tokens -> proj Linear (text)
     """
 
-    def __init__(self, bert, head, head_modules, device, fp8=False):
+    def __init__(self, bert, head, head_modules, device, fp8=False, fp16=False):
         self.fp8 = bool(fp8)
+        self._set_format(fp16)
+        h16 = self.h16
         self.device = dev = device
         cfg = getattr(bert, "config", None)
         emb = bert.embeddings
@@ -723,12 +747,12 @@ class BertEngine(EncoderEngineBase):
                 qb, vb = q, v
             w = torch.cat([qb.weight.detach(), k.weight.detach(), vb.weight.detach()], 0)
             b = torch.cat([qb.bias.detach(), k.bias.detach(), vb.bias.detach()], 0)
-            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(w, b, H, dev)
+            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(w, b, H, dev, h16)
             lay.src = (w, layer.attention.output.dense.weight, layer.intermediate.dense.weight, layer.output.dense.weight)   # f32 masters
-            lay.w_o, lay.w_o_t, lay.b_o = _pack_linear(layer.attention.output.dense, dev)
+            lay.w_o, lay.w_o_t, lay.b_o = _pack_linear(layer.attention.output.dense, dev, h16)
             lay.ln_a = (_f32(layer.attention.output.LayerNorm.weight, dev), _f32(layer.attention.output.LayerNorm.bias, dev))
-            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(layer.intermediate.dense, dev)
-            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(layer.output.dense, dev)
+            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(layer.intermediate.dense, dev, h16)
+            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(layer.output.dense, dev, h16)
             lay.ln_b = (_f32(layer.output.LayerNorm.weight, dev), _f32(layer.output.LayerNorm.bias, dev))
             if self.fp8:
                 self._pack_fp8(lay, w, layer.intermediate.dense.weight, layer.output.dense.weight, dev)
@@ -737,7 +761,7 @@ class BertEngine(EncoderEngineBase):
         self.head = head
         if head == "mlm_softmax_mean":
             tr, dec = head_modules
-            self.w_tr, self.w_tr_t, self.b_tr = _pack_linear(tr.dense, dev)
+            self.w_tr, self.w_tr_t, self.b_tr = _pack_linear(tr.dense, dev, h16)
             self.src_tr = tr.dense.weight
             self.ln_t = (_f32(tr.LayerNorm.weight, dev), _f32(tr.LayerNorm.bias, dev))
             self.eps_t = float(tr.LayerNorm.eps)
@@ -750,8 +774,8 @@ class BertEngine(EncoderEngineBase):
             self.out_dim, self.head_in = proj.weight.shape
         assert self.out_dim % 128 == 0 and self.head_in % 128 == 0
         self._setup_lora(qv, H, dev, trainable)
-        self.w_head_bf = torch.empty(self.out_dim, self.head_in, dtype=BF16, device=dev)
-        self.w_head_t = torch.empty(self.head_in, self.out_dim, dtype=BF16, device=dev)
+        self.w_head_bf = torch.empty(self.out_dim, self.head_in, dtype=h16, device=dev)   # the head weight in the operand format
+        self.w_head_t = None if self.fp16 else torch.empty(self.head_in, self.out_dim, dtype=BF16, device=dev)
         self.ws = None
 
     def _workspace(self, B, S):
@@ -759,12 +783,13 @@ class BertEngine(EncoderEngineBase):
             return self.ws
         dev, H, L, FF = self.device, self.H, len(self.layers), self.FF
         M = B * S
-        z = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
+        h16 = self.h16     # the 16-bit operand buffers (and the 16-bit residual stream) are fp16 in an fp16 engine
+        z = lambda *s, dt=h16: torch.empty(*s, dtype=dt, device=dev)
         ws = {"B": B, "S": S, "M": M, "gen": next(_WS_GEN)}
         ws["emb"] = z(M, H, dt=F32)
         ws["yb"] = [z(M, H + KPAD) for _ in range(L + 1)]   # LN outputs feeding each layer's QKV GEMM (+ LoRA t)
         rb = ws["resid_bf16"] = RESID_STREAM_BF16 and not self.full_ft and not self.fp8
-        sdt = BF16 if rb else F32
+        sdt = h16 if rb else F32
         ws["y"] = z(M, H, dt=F32)                           # f32 copy of the current layer input (residual; bf16 stream: head input only)
         ws["ym"] = None if rb else z(M, H, dt=F32)
         ws["ymb"] = z(M, H)
@@ -774,7 +799,7 @@ class BertEngine(EncoderEngineBase):
         # attention-probs dropout: the forward leaves its keep decisions (1 bit per probability, 32 B per query row) for the backward,
         # which otherwise re-hashes every element (BSCLIP_ATTN_KEEP_BITS=0: the re-hashing form, same masks); 64 B per query row
         ws["kbits"] = ([torch.zeros(B * self.heads * S * ops.KEEP_WORDS, dtype=torch.int32, device=dev) for _ in range(L)]
-                       if self.p_attn > 0.0 and ATTN_KEEP_BITS and not self.exact() else None)
+                       if self.p_attn > 0.0 and ATTN_KEEP_BITS and not self.exact() and not self.fp16 else None)
         ws["s1"] = [z(M, H, dt=sdt) for _ in range(L)]      # pre-LN sums (LN backward inputs)
         ws["s2"] = [z(M, H, dt=sdt) for _ in range(L)]
         ws["sta"] = [z(M, 2, dt=F32) for _ in range(L)]
@@ -808,6 +833,14 @@ class BertEngine(EncoderEngineBase):
                 ws["tz32"], ws["tn32"], ws["dlog32"] = z(M, H, dt=F32), z(M, H, dt=F32), z(M, self.out_dim, dt=F32)
         ws["key_bias"] = None
         ws["kb_buf"] = z(B, S, dt=F32)
+        if self.fp16:    # inference only: the forward's head buffers, no backward temporaries
+            if self.head == "mlm_softmax_mean":
+                ws["tz"], ws["tg"], ws["tn"] = z(M, H, dt=torch.uint8), z(M, H), z(M, H)
+                ws["st_t"], ws["logits"], ws["sm"] = z(M, 2, dt=F32), z(M, self.out_dim, dt=F32), z(M, 2, dt=F32)
+            else:
+                ws["mp"], ws["mp32"] = z(B, H), z(B, H, dt=F32)
+            self.ws = ws
+            return ws
         # backward temporaries
         ws["grad_bf16"] = GRAD_STREAM_BF16 and not self.full_ft
         gdt = BF16 if ws["grad_bf16"] else F32       # residual-gradient stream (see GRAD_STREAM_BF16)
@@ -1060,12 +1093,17 @@ class BertEngine(EncoderEngineBase):
             ops.gemm(ws["tn"], self.w_head_bf, ws["logits"], EPI_F32, bias=self.extra(1))
             ops.softmax_meanpool_fwd(ws["logits"], B, S, out, ws["sm"])
         else:
-            ops.meanpool_tokens_fwd(ws["y"], B, S, ws["mp"])
+            if self.fp16:   # the mean-pool kernel writes bf16: pool in f32, round once to fp16
+                ops.meanpool_tokens_f32(ws["y"], B, S, ws["mp32"])
+                ops.cast_f32_bf16(ws["mp32"], ws["mp"])
+            else:
+                ops.meanpool_tokens_fwd(ws["y"], B, S, ws["mp"])
             ops.gemm(ws["mp"], self.w_head_bf, out, EPI_F32, bias=self.extra(1))
         ops.set_dropout_step(None)   # the pointer is per thread: do not leak it into the caller's own launches
         return out
 
     def backward(self, dout):
+        self._no_fp16_backward()
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
@@ -1213,6 +1251,43 @@ def set_precision(model, precision):
             m._engine = None
 
 
+OPERAND_FORMATS = ("bf16", "fp16")
+
+
+def wants_fp16(module):
+    """``module.hip_operands = "fp16"`` (set_operand_format): the encoder's forward runs on fp16 operands (inference only)."""
+    return getattr(module, "hip_operands", "bf16") == "fp16"
+
+
+def set_operand_format(model, fmt):
+    """Select the 16-bit operand format of the ViT, BarcodeBERT and text encoders under ``model``: "bf16" (default) or "fp16".
+    fp16 runs every GEMM, attention product and LayerNorm output of the forward on IEEE fp16 (same MFMA rate, 3 more mantissa bits:
+    DESIGN.md 4); its engines are inference-only in this release -- eval() and torch.no_grad().  Engines are rebuilt on the next
+    forward."""
+    if fmt not in OPERAND_FORMATS:
+        raise ValueError(f"operand format must be 'bf16' or 'fp16', not {fmt!r}")
+    for m in model.modules():
+        if hasattr(m, "lora_vit") or hasattr(m, "lora_barcode_bert") or hasattr(m, "lora_bert"):
+            m.hip_operands = fmt
+            m._engine = None
+
+
+def _check_fp16(module):
+    """fp16 operands: an inference-only forward of the LoRA-regime engines on the 16-bit streams -- everything else is refused
+    before an engine is built."""
+    who = type(module).__name__
+    if wants_fp8(module):
+        raise ValueError(f"{who}: fp16 operands cannot be combined with set_precision(..., 'fp8')")
+    if wants_full_ft(module):
+        raise ValueError(f"{who}: fp16 operands are not available for full fine-tuning (disable_lora: true)")
+    if EXACT_FORWARD or not RESID_STREAM_BF16:
+        raise ValueError(f"{who}: fp16 operands run on the 16-bit residual stream: not with BSCLIP_PARITY=1 / 2 "
+                         "(set_parity_mode) or BSCLIP_RESID_STREAM=f32")
+    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
+        raise RuntimeError(f"{who}: the fp16-operand forward is inference-only (the fp16 backward is not built yet): call "
+                           "model.eval() and run it under torch.no_grad(), or set_operand_format(model, 'bf16')")
+
+
 def wants_full_ft(module):
     """``module.hip_full_ft`` (set by load_clip_model for ``disable_lora: true``): every parameter is trained."""
     return bool(getattr(module, "hip_full_ft", False))
@@ -1220,7 +1295,8 @@ def wants_full_ft(module):
 
 def _engine_for(module, build):
     eng = getattr(module, "_engine", None)
-    if eng is not None and (eng.fp8 != wants_fp8(module) or eng.full_ft != wants_full_ft(module)):
+    if eng is not None and (eng.fp8 != wants_fp8(module) or eng.full_ft != wants_full_ft(module)
+                            or getattr(eng, "fp16", False) != wants_fp16(module)):
         eng = None
     if eng is not None and eng.flat.valid() and _frozen_signature(module, eng) != eng._frozen_sig:
         eng = None  # frozen weights were overwritten (checkpoint loaded after the first forward): repack
@@ -1235,6 +1311,8 @@ def _engine_for(module, build):
 
 
 def run_encoder(module, build, fwd_args):
+    if wants_fp16(module):
+        _check_fp16(module)
     eng = _engine_for(module, build)
     eng.training = module.training
     eng._owner = module

@@ -162,17 +162,26 @@ def set_gemm_persistent_grid(workgroups):
     check(_l.load().bsclip_gemm_set_persistent_grid(workgroups))
 
 
+def _h16(*ts, who):
+    """The 16-bit operand format shared by the 16-bit tensors among ``ts`` (None entries skipped): bf16 or fp16, never mixed."""
+    kinds = {t.dtype for t in ts if t is not None and t.dtype in (BF16, F16)}
+    _req(len(kinds) <= 1, f"{who}: 16-bit tensors must all be bf16 or all fp16, got {sorted(str(k) for k in kinds)}")
+    return kinds.pop() if kinds else BF16
+
+
 def layernorm_fwd(x, gamma, beta, eps, y_bf16=None, y_f32=None, lora_a=None, stats=None, M=None, dropout=None, y_split3=None):
-    """``y_split3`` (exact mode): bf16 [M, >= 3H] that receives the output as a split-bf16 GEMM operand [hi | lo | hi]."""
+    """``y_split3`` (exact mode): bf16 [M, >= 3H] that receives the output as a split-bf16 GEMM operand [hi | lo | hi].
+    fp16 operands (BSCLIP_OPERANDS_FP16): a 16-bit x and y_bf16 are fp16; no y_split3, no dropout."""
     ld_x = _rowmajor(x, "x")
     H = gamma.numel()
     M = x.shape[0] if M is None else M
-    _req(x.dtype in (F32, BF16) and x.shape[1] >= H and M <= x.shape[0], "layernorm_fwd: bad x")
+    _req(x.dtype in (F32, BF16, F16) and x.shape[1] >= H and M <= x.shape[0], "layernorm_fwd: bad x")
+    h16 = _h16(x, y_bf16, who="layernorm_fwd")
     _req(gamma.dtype == F32 and beta.dtype == F32 and beta.numel() == H, "layernorm_fwd: gamma/beta f32 [H]")
     ld_y = 0
     if y_bf16 is not None:
         ld_y = _rowmajor(y_bf16, "y_bf16")
-        _req(y_bf16.dtype == BF16 and y_bf16.shape[0] >= M and y_bf16.shape[1] >= H + (KPAD if lora_a is not None else 0),
+        _req(y_bf16.dtype == h16 and y_bf16.shape[0] >= M and y_bf16.shape[1] >= H + (KPAD if lora_a is not None else 0),
              "layernorm_fwd: y_bf16 too small")
     if y_f32 is not None:
         _req(y_f32.dtype == F32 and y_f32.is_contiguous() and y_f32.shape[0] >= M and y_f32.shape[1] == H,
@@ -186,7 +195,8 @@ def layernorm_fwd(x, gamma, beta, eps, y_bf16=None, y_f32=None, lora_a=None, sta
         ld_y3 = _rowmajor(y_split3, "y_split3")
         _req(y_split3.dtype == BF16 and y_split3.shape[0] >= M and y_split3.shape[1] >= 3 * H, "layernorm_fwd: y_split3 bf16 [M, >= 3H]")
     dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
-    check(_l.load().bsclip_layernorm_fwd(_p(x), ld_x, int(x.dtype == BF16), M, H, _p(gamma), _p(beta), float(eps),
+    fmt = OPERANDS_FP16 if h16 == F16 else 0
+    check(_l.load().bsclip_layernorm_fwd(_p(x), ld_x, int(x.dtype != F32) | fmt, M, H, _p(gamma), _p(beta), float(eps),
                                          _p(y_bf16), ld_y, _p(y_f32), _p(y_split3), ld_y3, _p(lora_a), _p(stats), dp, ds, _stream()))
 
 
@@ -270,17 +280,20 @@ def _keep_bits_ok(keep_bits, B, S, heads, who):
 
 
 def attn_fwd(qkv, B, S, heads, scale, ctx, lse, key_bias=None, dropout=None, q_rows=0, keep_bits=None):
-    """``keep_bits`` (int32 [B * heads, S, 2, 8], with dropout only): the forward leaves its keep decisions there for ``attn_bwd``."""
+    """``keep_bits`` (int32 [B * heads, S, 2, 8], with dropout only): the forward leaves its keep decisions there for ``attn_bwd``.
+    qkv and ctx both bf16, or both fp16 (BSCLIP_OPERANDS_FP16: inference only, no dropout / keep_bits)."""
     ld_qkv, ld_ctx = _rowmajor(qkv, "qkv"), _rowmajor(ctx, "ctx")
     _keep_bits_ok(keep_bits, B, S, heads, "attn_fwd")
-    _req(qkv.dtype == BF16 and ctx.dtype == BF16 and lse.dtype == F32, "attn_fwd dtypes")
+    h16 = _h16(qkv, ctx, who="attn_fwd")
+    _req(qkv.dtype == h16 and ctx.dtype == h16 and lse.dtype == F32, "attn_fwd dtypes")
     _req(qkv.shape[0] >= B * S and qkv.shape[1] >= 3 * heads * 64, "attn_fwd: qkv too small")
     _req(ctx.shape[0] >= B * S and ctx.shape[1] >= heads * 64 and lse.numel() >= B * heads * S, "attn_fwd: outputs too small")
     if key_bias is not None:
         _req(key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S, "key_bias f32 [B,S]")
     dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    fmt = OPERANDS_FP16 if h16 == F16 else 0
     check(_l.load().bsclip_attn_fwd(_p(qkv), ld_qkv, B, S, heads, _p(key_bias), float(scale), _p(ctx), ld_ctx, _p(lse),
-                                    int(q_rows), _p(keep_bits), dp, ds, _stream()))
+                                    int(q_rows) | fmt, _p(keep_bits), dp, ds, _stream()))
 
 
 def attn_bwd(qkv, dctx, lse, B, S, heads, scale, dqkv, key_bias=None, dropout=None, q_rows=0, keep_bits=None, lora=None):
@@ -469,9 +482,10 @@ def attn_bwd_f32(qkv, dctx, ctx, lse, B, S, heads, scale, dqkv, key_bias=None, d
 def im2col_patch16(image, cols):
     B = image.shape[0]
     _req(image.dtype == F32 and image.is_contiguous() and tuple(image.shape[1:]) == (3, 224, 224), "image f32 [B,3,224,224]")
-    _req(cols.dtype == BF16 and cols.is_contiguous() and cols.shape[0] >= B * 196 and cols.shape[1] in (768, 2304),
-         "cols bf16 [B*196, 768] (or [B*196, 2304]: split-bf16 rows [hi | lo | hi])")
-    check(_l.load().bsclip_im2col_patch16(_p(image), B, _p(cols), cols.shape[1], int(cols.shape[1] == 2304), _stream()))
+    _req(cols.dtype in (BF16, F16) and cols.is_contiguous() and cols.shape[0] >= B * 196 and cols.shape[1] in (768, 2304),
+         "cols bf16 / fp16 [B*196, 768] (or [B*196, 2304]: split rows [hi | lo | hi])")
+    fmt = OPERANDS_FP16 if cols.dtype == F16 else 0
+    check(_l.load().bsclip_im2col_patch16(_p(image), B, _p(cols), cols.shape[1], int(cols.shape[1] == 2304) | fmt, _stream()))
 
 
 def mask_to_bias(mask, bias):
@@ -481,9 +495,10 @@ def mask_to_bias(mask, bias):
 
 
 def vit_cls_rows(x, cls_token, pos_embed, B, S, H):
-    _req(x.dtype in (F32, BF16) and x.is_contiguous() and x.numel() >= B * S * H, "x f32 / bf16 [B*S,H]")
+    _req(x.dtype in (F32, BF16, F16) and x.is_contiguous() and x.numel() >= B * S * H, "x f32 / bf16 / fp16 [B*S,H]")
     _req(cls_token.numel() == H and pos_embed.numel() >= H and cls_token.dtype == F32 and pos_embed.dtype == F32, "cls/pos")
-    check(_l.load().bsclip_vit_cls_rows(_p(x), int(x.dtype == BF16), _p(cls_token), _p(pos_embed), B, S, H, _stream()))
+    flag = {F32: 0, BF16: 1, F16: 1 | OPERANDS_FP16}[x.dtype]
+    check(_l.load().bsclip_vit_cls_rows(_p(x), flag, _p(cls_token), _p(pos_embed), B, S, H, _stream()))
 
 
 def bert_embed(ids, type_ids, word, pos, typ, out):
@@ -682,15 +697,20 @@ def transpose_colsum_bf16(src, R, C, dst, colsum_out):
 
 
 def cast_f32_bf16(src, dst):
-    _req(src.dtype == F32 and dst.dtype == BF16 and src.is_contiguous() and dst.is_contiguous()
+    """dst = src rounded to dst's 16-bit format: bf16, or fp16 (bsclip_cast_f32_f16)."""
+    _req(src.dtype == F32 and dst.dtype in (BF16, F16) and src.is_contiguous() and dst.is_contiguous()
          and dst.numel() >= src.numel(), "cast_f32_bf16")
-    check(_l.load().bsclip_cast_f32_bf16(_p(src), src.numel(), _p(dst), _stream()))
+    fn = _l.load().bsclip_cast_f32_f16 if dst.dtype == F16 else _l.load().bsclip_cast_f32_bf16
+    check(fn(_p(src), src.numel(), _p(dst), _stream()))
 
 
-def waug_set_lora_layers(table, layers, ld_w, H):
-    """One launch for all LoRA layers of an encoder: ``table`` int64 [layers, 3] of device addresses (W_aug, B_q, B_v)."""
+def waug_set_lora_layers(table, layers, ld_w, H, dtype=BF16):
+    """One launch for all LoRA layers of an encoder: ``table`` int64 [layers, 3] of device addresses (W_aug, B_q, B_v); ``dtype`` is
+    the W_aug buffers' 16-bit format (fp16: BSCLIP_OPERANDS_FP16, fewer than 256 layers)."""
     _req(table.dtype == torch.int64 and table.is_contiguous() and table.is_cuda and table.numel() >= 3 * layers, "waug_set_lora_layers: table")
-    check(_l.load().bsclip_waug_set_lora_layers(_p(table), int(layers), int(ld_w), int(H), _stream()))
+    _req(dtype in (BF16, F16), "waug_set_lora_layers: dtype bf16 or fp16")
+    fmt = OPERANDS_FP16 if dtype == F16 else 0
+    check(_l.load().bsclip_waug_set_lora_layers(_p(table), int(layers) | fmt, int(ld_w), int(H), _stream()))
 
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
@@ -718,10 +738,11 @@ def set_dropout_step(counter):
 
 
 def count_nonfinite(t, counter):
-    """counter (int32 / uint32 device word) += the number of Inf / NaN elements of the contiguous f32 / bf16 tensor ``t``."""
-    _req(t.dtype in (F32, BF16) and t.is_contiguous() and t.numel() > 0, "count_nonfinite: contiguous f32 / bf16 tensor")
+    """counter (int32 / uint32 device word) += the number of Inf / NaN elements of the contiguous f32 / bf16 / fp16 tensor ``t``."""
+    _req(t.dtype in (F32, BF16, F16) and t.is_contiguous() and t.numel() > 0, "count_nonfinite: contiguous f32 / bf16 / fp16 tensor")
     _req(counter.dtype == torch.int32 and counter.numel() >= 1 and counter.device == t.device, "count_nonfinite: int32 device counter")
-    check(_l.load().bsclip_count_nonfinite(_p(t), t.numel(), int(t.dtype == BF16), _p(counter), _stream()))
+    kind = {F32: 0, BF16: 1, F16: 1 | OPERANDS_FP16}[t.dtype]
+    check(_l.load().bsclip_count_nonfinite(_p(t), t.numel(), kind, _p(counter), _stream()))
 
 
 def counter_add(counter, inc=1):

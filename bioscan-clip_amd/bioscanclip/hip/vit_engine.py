@@ -1,7 +1,7 @@
 """Entry used by ``LoRA_ViT_timm.forward`` (reference image_encoder.py:108-109)."""
 import torch
 
-from .engine import ViTEngine, run_encoder, wants_fp8, wants_full_ft
+from .engine import ViTEngine, run_encoder, wants_fp8, wants_fp16, wants_full_ft
 
 
 def vit_forward(module, x):
@@ -13,5 +13,5 @@ def vit_forward(module, x):
         if wants_full_ft(module):   # disable_lora: true -- every parameter trained (hip/engine_ft.py)
             from .engine_ft import ViTEngineFT
             return ViTEngineFT(module, x.device)
-        return ViTEngine(module, x.device, fp8=wants_fp8(module))
+        return ViTEngine(module, x.device, fp8=wants_fp8(module), fp16=wants_fp16(module))
     return run_encoder(module, build, (x,))

@@ -27,13 +27,14 @@ namespace {
 // KB (DROP only): the forward leaves its keep decisions as bit words (attn_common.h KEEP_WORDS) for the backward.  A template parameter,
 // not a test of the pointer: behind a run-time branch the compiler sinks the whole bit computation into the branch and keeps all 80
 // factors (or compare masks) of a query block alive until then (+46 VGPRs at S = 133, spills at S = 197).
-template <int NB, bool DROP, int TAIL = 32, bool V2 = false, bool KB = false>
+template <int NB, bool DROP, int TAIL = 32, bool V2 = false, bool KB = false, bool F16 = false>
 __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, int ld, int S,
                                                                    int heads, const float* __restrict__ key_bias,
                                                                    float scale, bf16_t* __restrict__ ctx, int ld_ctx,
                                                                    float* __restrict__ lse, DropCfg drop, int nqb,
                                                                    bf16_t* __restrict__ ctx_lo = nullptr,
                                                                    unsigned* __restrict__ kbits = nullptr) {
+    static_assert(!F16 || (!DROP && !V2), "fp16 operands: inference forms only (no dropout, no V2 statistics)");
     constexpr int SP = NB * 32;
     BSCLIP_DROP_RESOLVE(drop);
     __shared__ __attribute__((aligned(16))) char smem[2 * SP * ROWB + SP * 4];
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_fwd_kernel(const bf16_
                 for (int i = 0; i < 4; ++i) acc[4 * g + i] = bias[i];
             }
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = mfma32(frag_rm(sK, 32 * kt, ks, lane), qf[ks], acc);
+            for (int ks = 0; ks < 4; ++ks) acc = mfma32<F16>(frag_rm(sK, 32 * kt, ks, lane), qf[ks], acc);
             const int nr = 4 * (kt == NB - 1 ? tail_groups<TAIL>() : 4);   // registers that can hold a valid key
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -158,14 +159,14 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_fwd_kernel(const bf16_
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 if (s2 >= (kt == NB - 1 ? tail_ksteps<TAIL>() : 2)) continue;   // keys past the sequence carry probability 0
-                const bf16x8 pb = pack8(p[kt], s2);
+                const bf16x8 pb = pack8<F16>(p[kt], s2);
                 if constexpr (V2) {
                     const u32x4 pw = __builtin_bit_cast(u32x4, pb);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) zacc = bf_pair_sum(pw[i], zacc);
                 }
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) o[dt] = mfma32(frag_tr(sV, 32 * dt, 32 * kt + 16 * s2, lane), pb, o[dt]);
+                for (int dt = 0; dt < 2; ++dt) o[dt] = mfma32<F16>(frag_tr(sV, 32 * dt, 32 * kt + 16 * s2, lane), pb, o[dt]);
             }
 
         const int q = q0 + (lane & 31);
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_fwd_kernel(const bf16_
                     *reinterpret_cast<f32x4*>(lse + (((size_t)b * heads + hd) * S + q) * 4) = f32x4{nm2, inv, sum / zp, 0.f};
             }
         } else if (q < S) {
-            store_dt(o, 1.0f / sum, ctx + (size_t)(b * S + q) * ld_ctx + hd * 64, lane);
+            store_dt<F16>(o, 1.0f / sum, ctx + (size_t)(b * S + q) * ld_ctx + hd * 64, lane);
             if (h == 0) lse[((size_t)b * heads + hd) * S + q] = (__log2f(sum) - nm2) * LN2;  // natural-log LSE
         }
     }
@@ -635,11 +636,23 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
     case NBV:                                                                                                   \
         ATTN_FWD_PICK(NBV, 32);                                                                                 \
         break;
+// fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the inference forms only -- no dropout, no keep bits (rejected on the host)
+#define ATTN_FWD16_LAUNCH(NBV, TL)                                                                              \
+    hipLaunchKernelGGL((attn_fwd_kernel<NBV, false, TL, false, false, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
+                       static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale, static_cast<bf16_t*>(ctx), ld_ctx, \
+                       lse, drop, nqb, static_cast<bf16_t*>(nullptr), static_cast<unsigned*>(nullptr))
+#define ATTN_FWD16_CASE(NBV)                                                                                    \
+    case NBV:                                                                                                   \
+        ATTN_FWD16_LAUNCH(NBV, 32);                                                                             \
+        break;
 
 extern "C" int bsclip_attn_fwd(const void* qkv, int ld_qkv, int B, int S, int heads, const float* key_bias,
                                float scale, void* ctx, int ld_ctx, float* lse, int q_rows, void* keep_bits, float dropout_p,
                                uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(qkv && ctx && lse, "bsclip_attn_fwd: null pointer");
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(q_rows, f16), "bsclip_attn_fwd: unknown bits in q_rows=0x%x", q_rows);
+    BSCLIP_REQUIRE(!f16 || (dropout_p == 0.f && !keep_bits), "bsclip_attn_fwd: fp16 operands take no dropout / keep_bits (inference only)");
     BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(keep_bits) & 15) == 0, "bsclip_attn_fwd: keep_bits must be 16-byte aligned");
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= 224, "bsclip_attn_fwd: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 8 == 0 && ld_ctx >= heads * 64 && ld_ctx % 4 == 0,
@@ -650,7 +663,18 @@ extern "C" int bsclip_attn_fwd(const void* qkv, int ld_qkv, int B, int S, int he
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the production sequence lengths get the instantiation that knows their last tile holds 5 rows (see tail_groups)
-    if (S == 197) {
+    if (f16) {
+        if (S == 197) {
+            ATTN_FWD16_LAUNCH(7, 5);
+        } else if (S == 133) {
+            ATTN_FWD16_LAUNCH(5, 5);
+        } else {
+            switch ((S + 31) / 32) {
+                ATTN_FWD16_CASE(1) ATTN_FWD16_CASE(2) ATTN_FWD16_CASE(3) ATTN_FWD16_CASE(4) ATTN_FWD16_CASE(5) ATTN_FWD16_CASE(6)
+                ATTN_FWD16_CASE(7)
+            }
+        }
+    } else if (S == 197) {
         ATTN_FWD_PICK(7, 5);
     } else if (S == 133) {
         ATTN_FWD_PICK(5, 5);

@@ -12,8 +12,11 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
+// F16 (bsclip_attn_fwd | BSCLIP_OPERANDS_FP16): the same fragments read as IEEE fp16, v_mfma_f32_32x32x16_f16 (the bf16 rate)
+template <bool F16 = false>
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x16 zero16() {
     f32x16 z;
@@ -21,13 +24,14 @@ __device__ __forceinline__ f32x16 zero16() {
     for (int i = 0; i < 16; ++i) z[i] = 0.f;
     return z;
 }
-// registers [8*s2, 8*s2+8) of an accumulator tile -> bf16x8 operand fragment (element j = register 8*s2 + j)
+// registers [8*s2, 8*s2+8) of an accumulator tile -> bf16x8 operand fragment (element j = register 8*s2 + j); fp16 when F16
+template <bool F16 = false>
 __device__ __forceinline__ bf16x8 pack8(const f32x16& x, int s2) {
     u32x4 u;
-    u[0] = pack_bf2(x[8 * s2 + 0], x[8 * s2 + 1]);
-    u[1] = pack_bf2(x[8 * s2 + 2], x[8 * s2 + 3]);
-    u[2] = pack_bf2(x[8 * s2 + 4], x[8 * s2 + 5]);
-    u[3] = pack_bf2(x[8 * s2 + 6], x[8 * s2 + 7]);
+    u[0] = pack_h2<F16>(x[8 * s2 + 0], x[8 * s2 + 1]);
+    u[1] = pack_h2<F16>(x[8 * s2 + 2], x[8 * s2 + 3]);
+    u[2] = pack_h2<F16>(x[8 * s2 + 4], x[8 * s2 + 5]);
+    u[3] = pack_h2<F16>(x[8 * s2 + 6], x[8 * s2 + 7]);
     return __builtin_bit_cast(bf16x8, u);
 }
 
@@ -101,7 +105,8 @@ __device__ __forceinline__ bf16x8 frag_global(const bf16_t* base, int ld, int ro
 // accumulator row index of register r for lane half h (C/D map of the 32x32 MFMA)
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// store a [64 (d) x 32 (token on lane)] result held as 2 accumulator tiles into out[token][col0 + d]
+// store a [64 (d) x 32 (token on lane)] result held as 2 accumulator tiles into out[token][col0 + d] (fp16 when F16)
+template <bool F16 = false>
 __device__ __forceinline__ void store_dt(const f32x16 (&acc)[2], float mul, bf16_t* out_row, int lane) {
     const int h = lane >> 5;
 #pragma unroll
@@ -109,8 +114,8 @@ __device__ __forceinline__ void store_dt(const f32x16 (&acc)[2], float mul, bf16
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 o;
-            o.x = pack_bf2(acc[dt][4 * g + 0] * mul, acc[dt][4 * g + 1] * mul);
-            o.y = pack_bf2(acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
+            o.x = pack_h2<F16>(acc[dt][4 * g + 0] * mul, acc[dt][4 * g + 1] * mul);
+            o.y = pack_h2<F16>(acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
             *reinterpret_cast<uint2*>(out_row + 32 * dt + 8 * g + 4 * h) = o;
         }
 }

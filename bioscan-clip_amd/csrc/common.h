@@ -65,6 +65,19 @@ __device__ __forceinline__ unsigned pack_h2(float lo, float hi) {
         return pack_bf2(lo, hi);
     }
 }
+template <bool F16>
+__device__ __forceinline__ bf16_t f2h(float f) {
+    if constexpr (F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
+    else return f2bf(f);
+}
+// Host side: an entry point whose integer argument `v` carries BSCLIP_OPERANDS_FP16 (a flag, a boolean or a count < 256 in the
+// low byte).  Returns false on unknown bits; otherwise strips the flag from v and sets f16.
+inline bool take_operands_flag(int& v, bool& f16) {
+    if (v & ~(0xff | BSCLIP_OPERANDS_FP16)) return false;
+    f16 = (v & BSCLIP_OPERANDS_FP16) != 0;
+    v &= 0xff;
+    return true;
+}
 // v_mfma_f32_16x16x32_{bf16,f16}: same cycles on gfx950; the fragments are 16 bytes of either format
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {

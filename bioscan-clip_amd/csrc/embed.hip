@@ -13,7 +13,8 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 // [hi | hi | lo] one bf16 MFMA GEMM with K = 2304 forms hi.hi + lo.hi + hi.lo, i.e. the product to ~2^-16 instead of 2^-8
 // relative (the trick the loss GEMM uses).  The patch embedding is 0.4 % of the step's FLOPs and the one GEMM whose operand
 // rounding (5.3e-3 at its output) every later block amplifies: DESIGN.md 4.
-template <bool SPLIT>
+// F16 (split | BSCLIP_OPERANDS_FP16): the columns are fp16, hi = fp16(x), lo = fp16(x - hi).
+template <bool SPLIT, bool F16 = false>
 __global__ __launch_bounds__(256) void im2col_patch16_kernel(const float* __restrict__ img, int B,
                                                               bf16_t* __restrict__ out, int ld) {
     const long total = (long)B * 196 * 96;
@@ -28,31 +29,32 @@ __global__ __launch_bounds__(256) void im2col_patch16_kernel(const float* __rest
         const f32x4 a = *reinterpret_cast<const f32x4*>(src);
         const f32x4 d = *reinterpret_cast<const f32x4*>(src + 4);
         u32x4 o;
-        o[0] = pack_bf2(a[0], a[1]);
-        o[1] = pack_bf2(a[2], a[3]);
-        o[2] = pack_bf2(d[0], d[1]);
-        o[3] = pack_bf2(d[2], d[3]);
+        o[0] = pack_h2<F16>(a[0], a[1]);
+        o[1] = pack_h2<F16>(a[2], a[3]);
+        o[2] = pack_h2<F16>(d[0], d[1]);
+        o[3] = pack_h2<F16>(d[2], d[3]);
         *reinterpret_cast<u32x4*>(out + (size_t)row * ld + col) = o;
         if constexpr (SPLIT) {
-            auto hi = [](unsigned w, int k) { return bf2f((bf16_t)(k ? w >> 16 : w & 0xffff)); };
+            auto hi = [](unsigned w, int k) { return h2f<F16>((bf16_t)(k ? w >> 16 : w & 0xffff)); };
             u32x4 l;
-            l[0] = pack_bf2(a[0] - hi(o[0], 0), a[1] - hi(o[0], 1));
-            l[1] = pack_bf2(a[2] - hi(o[1], 0), a[3] - hi(o[1], 1));
-            l[2] = pack_bf2(d[0] - hi(o[2], 0), d[1] - hi(o[2], 1));
-            l[3] = pack_bf2(d[2] - hi(o[3], 0), d[3] - hi(o[3], 1));
+            l[0] = pack_h2<F16>(a[0] - hi(o[0], 0), a[1] - hi(o[0], 1));
+            l[1] = pack_h2<F16>(a[2] - hi(o[1], 0), a[3] - hi(o[1], 1));
+            l[2] = pack_h2<F16>(d[0] - hi(o[2], 0), d[1] - hi(o[2], 1));
+            l[3] = pack_h2<F16>(d[2] - hi(o[3], 0), d[3] - hi(o[3], 1));
             *reinterpret_cast<u32x4*>(out + (size_t)row * ld + 768 + col) = l;
             *reinterpret_cast<u32x4*>(out + (size_t)row * ld + 1536 + col) = o;
         }
     }
 }
 
-template <bool X_BF16>
+// X_BF16: a 16-bit stream, fp16 when F16
+template <bool X_BF16, bool F16 = false>
 __global__ void vit_cls_rows_kernel(void* __restrict__ x, const float* __restrict__ cls,
                                     const float* __restrict__ pos, int B, int S, int H) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H) return;
     const int b = i / H, c = i % H;
-    if constexpr (X_BF16) static_cast<bf16_t*>(x)[(size_t)b * S * H + c] = f2bf(cls[c] + pos[c]);
+    if constexpr (X_BF16) static_cast<bf16_t*>(x)[(size_t)b * S * H + c] = f2h<F16>(cls[c] + pos[c]);
     else static_cast<float*>(x)[(size_t)b * S * H + c] = cls[c] + pos[c];
 }
 
@@ -156,24 +158,27 @@ __global__ __launch_bounds__(256) void transpose64_kernel(const bf16_t* __restri
     }
 }
 
+// F16: to IEEE fp16 (bsclip_cast_f32_f16): RNE, subnormals kept, overflow to +-inf
+template <bool F16 = false>
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ in, long n,
                                                              bf16_t* __restrict__ out) {
     const long n4 = n >> 2;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(in + 4 * i);
         uint2 o;
-        o.x = pack_bf2(v[0], v[1]);
-        o.y = pack_bf2(v[2], v[3]);
+        o.x = pack_h2<F16>(v[0], v[1]);
+        o.y = pack_h2<F16>(v[2], v[3]);
         *reinterpret_cast<uint2*>(out + 4 * i) = o;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = (n4 << 2) + threadIdx.x;
-        out[i] = f2bf(in[i]);
+        out[i] = f2h<F16>(in[i]);
     }
 }
 
 // W_aug rows [0,H): cols [H,H+4) = B_q[n,:]; rows [2H,3H): cols [H+4,H+8) = B_v[n,:]
-// for every LoRA layer of an encoder in one launch (blockIdx.y = layer): table[l] = {W_aug, B_q, B_v} device addresses
+// for every LoRA layer of an encoder in one launch (blockIdx.y = layer): table[l] = {W_aug, B_q, B_v} device addresses; fp16 when F16
+template <bool F16 = false>
 __global__ void waug_set_lora_layers_kernel(const int64_t* __restrict__ table, int ld_w, int H) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * H) return;
@@ -183,8 +188,8 @@ __global__ void waug_set_lora_layers_kernel(const int64_t* __restrict__ table, i
     const int n = is_v ? i - H : i;
     const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(is_v ? t[2] : t[1]) + (size_t)n * 4);
     uint2 o;
-    o.x = pack_bf2(v[0], v[1]);
-    o.y = pack_bf2(v[2], v[3]);
+    o.x = pack_h2<F16>(v[0], v[1]);
+    o.y = pack_h2<F16>(v[2], v[3]);
     *reinterpret_cast<uint2*>(w + (size_t)(is_v ? 2 * H + n : n) * ld_w + H + (is_v ? 4 : 0)) = o;
 }
 
@@ -206,12 +211,20 @@ extern "C" int bsclip_mask_to_bias(const int64_t* mask, int n, float* bias, void
 
 extern "C" int bsclip_im2col_patch16(const float* image, int B, void* cols_bf16, int ld_cols, int split, void* stream) {
     BSCLIP_REQUIRE(image && cols_bf16 && B > 0, "bsclip_im2col_patch16: bad args");
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(split, f16), "bsclip_im2col_patch16: unknown bits in split=0x%x", split);
     BSCLIP_REQUIRE(ld_cols % 8 == 0 && ld_cols >= (split ? 2304 : 768) && (((uintptr_t)cols_bf16) & 15) == 0,
                    "bsclip_im2col_patch16: ld_cols=%d (>= %d, multiple of 8, 16-byte aligned rows)", ld_cols, split ? 2304 : 768);
     const long total = (long)B * 196 * 96;
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (split)
+    if (f16 && split)
+        hipLaunchKernelGGL((im2col_patch16_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
+    else if (f16)
+        hipLaunchKernelGGL((im2col_patch16_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
+    else if (split)
         hipLaunchKernelGGL((im2col_patch16_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                            image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
     else
@@ -224,7 +237,13 @@ extern "C" int bsclip_im2col_patch16(const float* image, int B, void* cols_bf16,
 extern "C" int bsclip_vit_cls_rows(void* x, int x_bf16, const float* cls_token, const float* pos_embed, int B, int S, int H,
                                    void* stream) {
     BSCLIP_REQUIRE(x && cls_token && pos_embed && B > 0, "bsclip_vit_cls_rows: bad args");
-    if (x_bf16)
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(x_bf16, f16), "bsclip_vit_cls_rows: unknown bits in x_bf16=0x%x", x_bf16);
+    BSCLIP_REQUIRE(!f16 || x_bf16, "bsclip_vit_cls_rows: fp16 operands need the 16-bit stream (x_bf16)");
+    if (f16)
+        hipLaunchKernelGGL((vit_cls_rows_kernel<true, true>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           x, cls_token, pos_embed, B, S, H);
+    else if (x_bf16)
         hipLaunchKernelGGL((vit_cls_rows_kernel<true>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            x, cls_token, pos_embed, B, S, H);
     else
@@ -283,17 +302,35 @@ extern "C" int bsclip_cast_f32_bf16(const float* in, int64_t n, void* out, void*
     long blocks = (n / 4 + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
+    hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
+                       (long)n, static_cast<bf16_t*>(out));
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// the fp16 form (no integer argument can carry BSCLIP_OPERANDS_FP16 here: n is a 64-bit count)
+extern "C" int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* stream) {
+    BSCLIP_REQUIRE(in && out && n > 0, "bsclip_cast_f32_f16: bad args");
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                        (long)n, static_cast<bf16_t*>(out));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
 
 extern "C" int bsclip_waug_set_lora_layers(const int64_t* table_dev, int layers, int ld_w, int H, void* stream) {
-    BSCLIP_REQUIRE(table_dev && layers > 0 && layers <= 65535 && ld_w >= H + BSCLIP_KPAD && ld_w % 4 == 0 && H % 4 == 0,
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(layers, f16), "bsclip_waug_set_lora_layers: unknown bits in layers=0x%x (count < 256)", layers);
+    BSCLIP_REQUIRE(table_dev && layers > 0 && ld_w >= H + BSCLIP_KPAD && ld_w % 4 == 0 && H % 4 == 0,
                    "bsclip_waug_set_lora_layers: bad args");
-    hipLaunchKernelGGL(waug_set_lora_layers_kernel, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       table_dev, ld_w, H);
+    if (f16)
+        hipLaunchKernelGGL(waug_set_lora_layers_kernel<true>, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), table_dev, ld_w, H);
+    else
+        hipLaunchKernelGGL(waug_set_lora_layers_kernel<false>, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), table_dev, ld_w, H);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -39,7 +39,8 @@ __device__ __forceinline__ float reduce8(float (&p)[8], int lane) {
     return v;
 }
 
-template <int H, bool X_BF16>
+// X_BF16: x is 16-bit -- bf16, or fp16 when F16
+template <int H, bool X_BF16, bool F16 = false>
 __device__ __forceinline__ void load_row(const void* x, int ld_x, int row, int lane, f32x4 (&v)[H / 256]) {
     constexpr int NV = H / 256;
     if constexpr (X_BF16) {
@@ -47,7 +48,7 @@ __device__ __forceinline__ void load_row(const void* x, int ld_x, int row, int l
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const uint2 u = ld_stream(reinterpret_cast<const uint2*>(p + j * 256 + lane * 4));
-            v[j] = f32x4{bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16)};
+            v[j] = f32x4{h2f<F16>(u.x & 0xffff), h2f<F16>(u.x >> 16), h2f<F16>(u.y & 0xffff), h2f<F16>(u.y >> 16)};
         }
     } else {
         const float* p = static_cast<const float*>(x) + (size_t)row * ld_x;
@@ -59,7 +60,9 @@ __device__ __forceinline__ void load_row(const void* x, int ld_x, int row, int l
 // Y_FP8: the GEMM operand is written as OCP fp8 e4m3 (scale 1: LayerNorm outputs are O(1); saturated at +-448) into y_bf16
 // reinterpreted as bytes (row stride ld_y BYTES), and the LoRA t block as bf16 into its own buffer t_aug (row stride ld_t
 // elements, 64 columns: t in [0,8), zeros after) -- the bf16 K-augmentation tile of bsclip_gemm_fp8 (BASELINE configs[4]).
-template <int H, bool X_BF16, bool LORA, bool Y_FP8 = false>
+// F16 (bsclip_layernorm_fwd with x_bf16 | BSCLIP_OPERANDS_FP16): a 16-bit x is fp16, and so are y_bf16 and its LoRA t block; y_f32 and
+// stats unchanged.  No split-operand (y3) or fp8 form.
+template <int H, bool X_BF16, bool LORA, bool Y_FP8 = false, bool F16 = false>
 __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __restrict__ x, int ld_x, int M,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
@@ -71,6 +74,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
                                                                   bf16_t* __restrict__ y3 = nullptr, int ld_y3 = 0) {
     // y3 (exact mode, round 5): the output as the split-bf16 GEMM operand [hi | lo | hi] (bf16 [M, 3H]) -- what a stand-alone
     // split3_rows pass over y_f32 used to produce
+    static_assert(!F16 || !Y_FP8, "fp16 operands: no fp8 output form");
     constexpr int NV = H / 256;
     BSCLIP_DROP_RESOLVE(drop);
     const int lane = threadIdx.x & 63;
@@ -94,12 +98,12 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
 
     // The wave's next row is loaded before the current one is reduced (one row in flight per wave was latency-bound).
     f32x4 nxt[NV];
-    if (wave < M) load_row<H, X_BF16>(x, ld_x, wave, lane, nxt);
+    if (wave < M) load_row<H, X_BF16, F16>(x, ld_x, wave, lane, nxt);
     for (int row = wave; row < M; row += nwaves) {
         f32x4 v[NV];
 #pragma unroll
         for (int j = 0; j < NV; ++j) v[j] = nxt[j];
-        if (row + nwaves < M) load_row<H, X_BF16>(x, ld_x, row + nwaves, lane, nxt);
+        if (row + nwaves < M) load_row<H, X_BF16, F16>(x, ld_x, row + nwaves, lane, nxt);
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
             for (int j = 0; j < NV; ++j)
                 st_stream(y_f32 + (size_t)row * H + j * 256 + lane * 4, v[j]);
         }
-        if (y3) {
+        if (!F16 && y3) {
             bf16_t* r3 = y3 + (size_t)row * ld_y3 + lane * 4;
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
@@ -154,8 +158,8 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
 #pragma unroll
                 for (int j = 0; j < NV; ++j) {
                     uint2 o;
-                    o.x = pack_bf2(v[j][0], v[j][1]);
-                    o.y = pack_bf2(v[j][2], v[j][3]);
+                    o.x = pack_h2<F16>(v[j][0], v[j][1]);
+                    o.y = pack_h2<F16>(v[j][2], v[j][3]);
                     st_stream(yr + j * 256 + lane * 4, o);
                 }
             }
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
                 const int src = ((lane >> 2) & 1) * 32 + ((lane >> 1) & 1) * 16 + (lane & 1) * 8;
                 const float tl = __shfl(t, src, 64);
                 // K-augmentation block: cols [H, H+8) = t, [H+8, H+64) = 0
-                yr[H + lane] = (lane < 8) ? f2bf(tl) : (bf16_t)0;
+                yr[H + lane] = (lane < 8) ? f2h<F16>(tl) : (bf16_t)0;
             }
         }
     }
@@ -381,11 +385,24 @@ int ln_grid(int M, int resident_per_cu = 8) {
     hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, M, \
                        gamma, beta, eps, static_cast<bf16_t*>(y_bf16), ld_y, y_f32, lora_a, stats, drop,               \
                        static_cast<bf16_t*>(nullptr), 0, static_cast<bf16_t*>(y_split3), ld_y3)
+#define LN_FWD16_LAUNCH(HH, XB, LO)                                                                            \
+    hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO, false, true>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, \
+                       M, gamma, beta, eps, static_cast<bf16_t*>(y_bf16), ld_y, y_f32, lora_a, stats, drop,            \
+                       static_cast<bf16_t*>(nullptr), 0, static_cast<bf16_t*>(nullptr), 0)
+#define LN_FWD16_PICK(HH)                                                                                      \
+    do {                                                                                                       \
+        if (x_bf16) { if (lo) LN_FWD16_LAUNCH(HH, true, true); else LN_FWD16_LAUNCH(HH, true, false); }        \
+        else        { if (lo) LN_FWD16_LAUNCH(HH, false, true); else LN_FWD16_LAUNCH(HH, false, false); }      \
+    } while (0)
 
 extern "C" int bsclip_layernorm_fwd(const void* x, int ld_x, int x_bf16, int M, int H, const float* gamma,
                                     const float* beta, float eps, void* y_bf16, int ld_y, float* y_f32, void* y_split3, int ld_y3,
                                     const float* lora_a, float* stats, float dropout_p, uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(x && gamma && beta && M > 0, "bsclip_layernorm_fwd: null/empty input");
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(x_bf16, f16), "bsclip_layernorm_fwd: unknown bits in x_bf16=0x%x", x_bf16);
+    BSCLIP_REQUIRE(!f16 || (!y_split3 && dropout_p == 0.f),
+                   "bsclip_layernorm_fwd: fp16 operands take no y_split3 output and no dropout (inference only)");
     BSCLIP_REQUIRE(H == 768 || H == 512, "bsclip_layernorm_fwd: H=%d (supported: 768, 512)", H);
     BSCLIP_REQUIRE(ld_x >= H && ld_x % 4 == 0, "bsclip_layernorm_fwd: ld_x=%d", ld_x);
     BSCLIP_REQUIRE(!y_bf16 || (ld_y % 4 == 0 && ld_y >= H + (lora_a ? BSCLIP_KPAD : 0)),
@@ -397,7 +414,10 @@ extern "C" int bsclip_layernorm_fwd(const void* x, int ld_x, int x_bf16, int M, 
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lo = lora_a != nullptr;
-    if (H == 768) {
+    if (f16) {
+        if (H == 768) LN_FWD16_PICK(768);
+        else LN_FWD16_PICK(512);
+    } else if (H == 768) {
         if (x_bf16) { if (lo) LN_FWD_LAUNCH(768, true, true); else LN_FWD_LAUNCH(768, true, false); }
         else        { if (lo) LN_FWD_LAUNCH(768, false, true); else LN_FWD_LAUNCH(768, false, false); }
     } else {
@@ -417,6 +437,7 @@ extern "C" int bsclip_layernorm_fwd_fp8(const void* x, int ld_x, int x_bf16, int
                                         float* y_f32, const float* lora_a, float* stats, float dropout_p,
                                         uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(x && gamma && beta && y_fp8 && M > 0, "bsclip_layernorm_fwd_fp8: null/empty input");
+    BSCLIP_REQUIRE(!(x_bf16 & BSCLIP_OPERANDS_FP16), "bsclip_layernorm_fwd_fp8: fp16 operands have no fp8 output form");
     BSCLIP_REQUIRE(H == 768 || H == 512, "bsclip_layernorm_fwd_fp8: H=%d (supported: 768, 512)", H);
     BSCLIP_REQUIRE(ld_x >= H && ld_x % 4 == 0 && ld_y >= H && ld_y % 16 == 0, "bsclip_layernorm_fwd_fp8: ld_x=%d ld_y=%d", ld_x, ld_y);
     BSCLIP_REQUIRE((lora_a == nullptr) == (t_aug == nullptr) && (!t_aug || (ld_t >= BSCLIP_KPAD && ld_t % 8 == 0)),

@@ -163,7 +163,10 @@ def main(argv=None):
     (``model_config.ckpt_path`` unless ``model_config.load_ckpt`` is false, :839-843) -> features of the key / seen / unseen
     splits -> accuracy table.  The HDF5 splits are not available here: the splits come from the synthetic
     evaluation loaders; extracted features are cached as ``.npz`` (h5py is absent) under the reference's directory layout
-    (``extracted_embedding/<dataset>/<model_output_name>/``) and reused with ``load_inference=true`` (:797-833)."""
+    (``extracted_embedding/<dataset>/<model_output_name>/``) and reused with ``load_inference=true`` (:797-833).
+    ``hip_operands=fp16`` (default bf16) runs the three encoders on fp16 operands (``set_operand_format``); the cache records the
+    format it was extracted with and is reused only by a run of the same format."""
+    from bioscanclip.hip.engine import OPERAND_FORMATS, set_operand_format
     from bioscanclip.model.simple_clip import load_clip_model
     from bioscanclip.util.config import load_config
     from bioscanclip.util.synthetic import SyntheticEvalLoader
@@ -179,13 +182,21 @@ def main(argv=None):
     root = str(getattr(args, "project_root_path", "."))
     folder = os.path.join(root, "extracted_embedding", str(getattr(mc, "dataset", "synthetic")), str(mc.model_output_name))
     feats_path = os.path.join(folder, "extracted_feature_from_val_split.npz")
+    operands = str(getattr(args, "hip_operands", "bf16"))
+    if operands not in OPERAND_FORMATS:
+        raise ValueError(f"hip_operands must be one of {OPERAND_FORMATS}, not {operands!r}")
     splits = None
     if getattr(args, "load_inference", False) and os.path.exists(feats_path):
         z = np.load(feats_path, allow_pickle=True)
-        splits = [z[k].item() for k in ("keys", "seen", "unseen")]
+        cached = str(z["operands"]) if "operands" in z.files else "bf16"   # caches from before the switch were extracted on bf16
+        if cached == operands:
+            splits = [z[k].item() for k in ("keys", "seen", "unseen")]
+        else:
+            print(f"Cached features were extracted with {cached} operands, this run uses {operands}: extracting again")
     if splits is None:
         print("Initialize model...")
         model = load_clip_model(args, device)
+        set_operand_format(model, operands)
         if hasattr(mc, "load_ckpt") and mc.load_ckpt is False:
             pass
         else:
@@ -199,7 +210,7 @@ def main(argv=None):
         if getattr(args, "save_inference", False):
             os.makedirs(folder, exist_ok=True)
             np.savez(feats_path, keys=np.array(splits[0], dtype=object), seen=np.array(splits[1], dtype=object),
-                     unseen=np.array(splits[2], dtype=object))
+                     unseen=np.array(splits[2], dtype=object), operands=np.array(operands))
     keys_dict, seen_dict, unseen_dict = splits
     return inference_and_print_result(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
 

@@ -76,6 +76,16 @@ enum bsclip_epilogue {
  * +-inf.  Same requirements as the bf16 form; the LoRA branch rides in K as there.  Library releases before this flag reject it
  * (unknown epilogue). */
 #define BSCLIP_OPERANDS_FP16 0x100
+/* The forward's other 16-bit entry points take the same flag or-ed into one integer argument (inference only: fp16 with dropout, keep
+ * bits, the split-operand or the fp8 outputs is rejected, as are unknown bits; the low byte keeps the argument's own value):
+ *   bsclip_attn_fwd        q_rows     qkv, ctx fp16; QK^T and PV on v_mfma_f32_32x32x16_f16, P rounded to fp16; lse f32
+ *   bsclip_layernorm_fwd   x_bf16     a 16-bit x is fp16; y_bf16 and its LoRA t block fp16 (y_f32, stats unchanged)
+ *   bsclip_layernorm_fwd_fp8  x_bf16  rejects the flag (no fp8 output form)
+ *   bsclip_im2col_patch16  split      fp16 columns; split rows [hi | lo | hi] with lo = fp16(x - hi)
+ *   bsclip_vit_cls_rows    x_bf16     the cls rows of an fp16 residual stream (x_bf16 must be set)
+ *   bsclip_waug_set_lora_layers  layers  fp16 LoRA-B columns (the layer count must then be < 256)
+ *   bsclip_count_nonfinite is_bf16    1 | BSCLIP_OPERANDS_FP16: the 16-bit elements are fp16
+ * and bsclip_cast_f32_f16 is the fp16 form of bsclip_cast_f32_bf16 (its only integer argument is the 64-bit count). */
 typedef struct bsclip_epi_args {
     uint32_t struct_size; /* = sizeof(bsclip_epi_args) = bsclip_epi_args_size(); a mismatch is rejected (ABI drift guard) */
     const float* bias;    /* [N] or NULL */
@@ -431,6 +441,8 @@ int64_t bsclip_transpose_colsum_workspace_floats(int R, int C);
 int bsclip_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum,
                                  float* workspace, void* stream);
 int bsclip_cast_f32_bf16(const float* in, int64_t n, void* out, void* stream);
+/* out fp16 [n] = in f32 [n]: round to nearest even, subnormals kept, overflow to +-inf (the head weight of an fp16-operand forward) */
+int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* stream);
 /* W_aug[3H, H+KPAD] bf16: cols [H,H+4) of rows [0,H) = B_q, cols [H+4,H+8) of rows [2H,3H) = B_v (refreshed
  * every step from the f32 masters; the frozen [3H,H] block is written once at pack time).
  * One launch for every LoRA layer of an encoder: table_dev[l] = {W_aug, B_q, B_v} as three 64-bit device addresses (the buffers live

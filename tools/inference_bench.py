@@ -1,5 +1,5 @@
 """Forward-only throughput of the HIP encoders (the feature-extraction half of the retrieval evaluation):
-eval mode, no autograd, L2-normalised features left in HBM.  python tools/inference_bench.py [--batch 256] [--text]"""
+eval mode, no autograd, L2-normalised features left in HBM.  python tools/inference_bench.py [--batch 256] [--text] [--operands fp16]"""
 import argparse
 import json
 import os
@@ -19,9 +19,12 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--text", action="store_true")
+    ap.add_argument("--operands", choices=("bf16", "fp16"), default="bf16", help="16-bit operand format of the encoders")
     a = ap.parse_args()
+    from bioscanclip.hip.engine import set_operand_format
     dev = torch.device("cuda", 0)
     model = bench.build_model(a.text, dev).eval()
+    set_operand_format(model, a.operands)
     image, dna, text = bench.synthetic_batch(a.batch, a.text, dev, seed=1)
     with torch.no_grad():
         for _ in range(3):
@@ -33,7 +36,7 @@ def main():
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
     print(json.dumps({"metric": "forward-only pairs/s (eval mode, I+D%s)" % ("+T" if a.text else ""),
-                      "value": round(a.batch / dt, 1), "ms_per_batch": round(dt * 1e3, 3), "batch": a.batch,
+                      "value": round(a.batch / dt, 1), "ms_per_batch": round(dt * 1e3, 3), "batch": a.batch, "operands": a.operands,
                       "unit_norm_check": float(out[0].norm(dim=-1).mean())}))
 
 
