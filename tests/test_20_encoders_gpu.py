@@ -212,32 +212,39 @@ def test_parity_mode_against_the_f32_oracle(which, monkeypatch):
     assert worst < TOL[name][1] / 1.3, worst    # in both towers the gradients are closer than the default configuration's
 
 
-@pytest.mark.parametrize("which", ["vit_L12", "dna_L12", "txt_L4", "vit_L2"])
-def test_exact_forward_meets_north_star_tolerance(which, monkeypatch):
-    """BSCLIP_PARITY=2 (hip/engine.py EXACT_FORWARD, csrc/exact.hip): every trunk GEMM on split-bf16 operands (hi + lo, K tripled),
-    LoRA folded in f32, exact-erf GELU, f32 attention, f32 streams.  north_star: "outputs (embeddings ...) match the reference CPU
-    path within 1e-3" -- here the embeddings of the full-depth encoders against the f32 oracle AND the golden fixtures the imported
-    reference produced, at 1e-3 (measured: see the log line / DESIGN.md 4).  The backward is exact as well (f32 gradients, dX / dW
-    GEMMs on split operands, f32 attention backward and LoRA gradients): EVERY trainable tensor's gradient within 1e-3 of the
-    oracle's autograd."""
+# BSCLIP_PARITY=2 distances to the f32 oracle (embedding, worst trainable-gradient tensor), gated at EXACT_FACTOR x measured on top of
+# north_star's 1e-3.  Measured 2026-10-16 on one MI355X (profiles/r07_exact_gates.jsonl); a second run gave
+# bit-identical distances (the mode's reductions run in a fixed order), so no run-to-run band is added.  Round 5 measured the same
+# values for the four cases it had.  Dropping the lo term of a single split operand lands between these gates and 1e-3 in 6 of the
+# 23 cases of tests/test_22_exact_gates_gpu.py.
+EXACT_MEASURED = {"vit_L12": (4.325e-5, 1.581e-4), "dna_L12": (1.437e-5, 4.851e-5), "txt_L4": (6.341e-6, 3.036e-5),
+                  "vit_L2": (2.131e-5, 5.768e-5), "dna_L2": (7.255e-6, 3.331e-5)}
+EXACT_FACTOR = 1.5
+
+
+def exact_encoder_distances(which, monkeypatch, log_name=None, keep=None):
+    """One exact-mode (BSCLIP_PARITY=2) forward + backward of encoder case ``which`` on seeded synthetic weights and inputs, against the
+    f32 oracle: returns (embedding distance, worst trainable-gradient distance) and logs both.  ``keep`` (a dict) receives the
+    embedding, the named parameters, the gradient keys, the prefix and the golden keys, for the golden-fixture checks."""
     from bioscanclip.hip import engine
     from bioscanclip.model import arch
     monkeypatch.setattr(engine, "RESID_STREAM_BF16", False)
     monkeypatch.setattr(engine, "GRAD_STREAM_BF16", False)
     monkeypatch.setattr(engine, "EXACT_FORWARD", True)
-    gold_all = load_golden("encoders")
     if which.startswith("vit"):
         depth = int(which[5:])
         from bioscanclip.model.image_encoder import LoRA_ViT_timm
         m, prefix, seed = LoRA_ViT_timm(arch.VisionTransformerParams(depth=depth), r=4, num_classes=768), "image_encoder.", 13
         x, _, _, _ = synth.synth_batch(2, seed=23)
         fn, cot, hip_in, gkey = (lambda s: refcpu.vit_encoder(s, x)), f"vit.cot.{depth}", x.cuda(), f"vit.out.{depth}"
-    elif which == "dna_L12":
+    elif which.startswith("dna"):
+        layers = int(which[5:])
         from bioscanclip.model.dna_encoder import LoRA_barcode_bert
-        m = LoRA_barcode_bert(arch.BertForMaskedLMParams(arch.barcode_bert_config(num_hidden_layers=12, **NODROP)), r=4, num_classes=768)
+        m = LoRA_barcode_bert(arch.BertForMaskedLMParams(arch.barcode_bert_config(num_hidden_layers=layers, **NODROP)), r=4,
+                              num_classes=768)
         prefix, seed = "dna_encoder.", 11
         _, x, _, _ = synth.synth_batch(2, seed=21)
-        fn, cot, hip_in, gkey = (lambda s: refcpu.barcode_bert_encoder(s, x)), "dna.cot.12", x.cuda(), "dna.out.12"
+        fn, cot, hip_in, gkey = (lambda s: refcpu.barcode_bert_encoder(s, x)), f"dna.cot.{layers}", x.cuda(), f"dna.out.{layers}"
     else:
         from bioscanclip.model.language_encoder import LoRA_bert
         m = LoRA_bert(arch.BertModelParams(arch.bert_small_config(**NODROP)), r=4, num_classes=768)
@@ -256,12 +263,31 @@ def test_exact_forward_meets_north_star_tolerance(which, monkeypatch):
     named = dict(m.named_parameters())
     e = rel_err(y, yo)
     worst = max(rel_err(named[k[len(prefix):]].grad, go[k]) for k in keys)
-    _log({"test": f"exact_forward_{which}", "emb_vs_f32_oracle": e, "worst_grad": worst})
+    _log({"test": log_name or f"exact_forward_{which}", "emb_vs_f32_oracle": e, "worst_grad": worst})
+    if keep is not None:
+        keep.update(y=y, named=named, keys=keys, prefix=prefix, gkey=gkey)
+    return e, worst
+
+
+@pytest.mark.parametrize("which", ["vit_L12", "dna_L12", "txt_L4", "vit_L2", "dna_L2"])
+def test_exact_forward_meets_north_star_tolerance(which, monkeypatch):
+    """BSCLIP_PARITY=2 (hip/engine.py EXACT_FORWARD, csrc/exact.hip): every trunk GEMM on split-bf16 operands (hi + lo, K tripled),
+    LoRA folded in f32, exact-erf GELU, f32 attention, f32 streams.  north_star: "outputs (embeddings ...) match the reference CPU
+    path within 1e-3" -- here the embeddings of the full-depth encoders against the f32 oracle AND the golden fixtures the imported
+    reference produced, at 1e-3 (measured: see the log line / DESIGN.md 4).  The backward is exact as well (f32 gradients, dX / dW
+    GEMMs on split operands, f32 attention backward and LoRA gradients): EVERY trainable tensor's gradient within 1e-3 of the
+    oracle's autograd.  On top of that, both distances within EXACT_FACTOR x their measured values (EXACT_MEASURED)."""
+    gold_all = load_golden("encoders")
+    r = {}
+    e, worst = exact_encoder_distances(which, monkeypatch, keep=r)
+    y, named, keys, prefix, gkey = r["y"], r["named"], r["keys"], r["prefix"], r["gkey"]
     assert e < 1e-3, e                                                   # north_star's tolerance, on the embeddings
     check_summary(gkey, y, gold_all[which]["out"], 1e-3, what=which + " exact ")   # ... and against the imported reference's own output
     assert worst < 1e-3, worst                                           # ... and on every gradient tensor
     for k in keys:                                                       # ... which the imported reference's autograd confirms
         check_summary(k, named[k[len(prefix):]].grad, gold_all[which]["grads"][k], 1e-3, what=which + " exact ")
+    m_e, m_g = EXACT_MEASURED[which]
+    assert e <= EXACT_FACTOR * m_e and worst <= EXACT_FACTOR * m_g, (which, e, worst, EXACT_MEASURED[which])
 
 
 def _build_clip(*a, **k):
@@ -302,8 +328,10 @@ def test_training_trajectory_matches_reference(with_text):
 
 # the same trajectories in the exact mode: north_star's "outputs (embeddings, loss, gradients) match the reference CPU path within
 # 1e-3" on the first step's embeddings and gradient fingerprints and on the loss of EVERY step (the late steps carry whatever the
-# early ones differed by, amplified by a loss that falls 50 x; measured values in gpurun_out/parity.jsonl)
-TRAJ_TOL_EXACT = dict(emb=1e-3, grad=1e-3, loss=1e-3, params=1e-3)
+# early ones differed by, amplified by a loss that falls 50 x).  Each quantity at min(1e-3, 2 x measured), the rule of TRAJ_TOL;
+# measured 2026-10-16, worst of the two trajectories and of the train_epoch run: emb 1.58e-5, grad 1.25e-4, loss 8.10e-5 (per step;
+# epoch means 7.57e-5), params 5.91e-4 (so params stays at 1e-3)
+TRAJ_TOL_EXACT = dict(emb=3.2e-5, grad=2.51e-4, loss=1.63e-4, params=1e-3)
 
 
 @pytest.mark.parametrize("with_text", [False, True])
