@@ -116,6 +116,12 @@ def _anomaly_check(engine, phase, out=None):
             if count_nonfinite(t):
                 raise RuntimeError(f"{who} forward: non-finite values first appear in {name} (BSCLIP_DETECT_ANOMALY)")
         raise RuntimeError(f"{who} forward: non-finite values in the encoder output (BSCLIP_DETECT_ANOMALY)")
+    if getattr(engine, "fp16", False) and hasattr(engine, "backward_probes"):
+        # the fp16 backward's scaled gradient stream: an overflow there is the finding, whether or not it reached .grad
+        for name, t in engine.backward_probes():
+            if count_nonfinite(t):
+                raise RuntimeError(f"{who} backward: non-finite values in {name} (fp16 gradient scale 2^{engine.FP16_GRAD_SCALE_LOG2}; "
+                                   "BSCLIP_DETECT_ANOMALY)")
     if count_nonfinite(engine.flat.grad) == 0:
         return
     owner = getattr(engine, "_owner", None)
@@ -201,18 +207,18 @@ class FlatParams:
                 p.grad = self.grad[o:o + p.numel()].view(p.shape)
 
 
-def _pack_qkv(w_qkv, b_qkv, H, dev, h16=BF16):
-    """W_aug [3H, H+KPAD] (LoRA-B columns refreshed every step) and W^T [H, 3H] for dX, both in the 16-bit format h16.  An fp16
-    engine runs no backward: it gets no transposed copy (None)."""
+def _pack_qkv(w_qkv, b_qkv, H, dev, h16=BF16, transposed=True):
+    """W_aug [3H, H+KPAD] (LoRA-B columns refreshed every step) and W^T [H, 3H] for dX, both in the 16-bit format h16.  An engine
+    that runs no backward (the fp16 BERT engines) gets no transposed copy (transposed=False: None)."""
     w = w_qkv.detach().to(dev, F32)
     waug = torch.zeros(3 * H, H + KPAD, dtype=h16, device=dev)
     waug[:, :H] = w.to(h16)
-    return waug, None if h16 == F16 else w.t().contiguous().to(BF16), _f32(b_qkv, dev)
+    return waug, w.t().contiguous().to(h16) if transposed else None, _f32(b_qkv, dev)
 
 
-def _pack_linear(lin, dev, h16=BF16):
+def _pack_linear(lin, dev, h16=BF16, transposed=True):
     w = lin.weight.detach().to(dev, F32)
-    return w.to(h16).contiguous(), None if h16 == F16 else w.t().contiguous().to(BF16), _f32(lin.bias, dev)
+    return w.to(h16).contiguous(), w.t().contiguous().to(h16) if transposed else None, _f32(lin.bias, dev)
 
 
 class _Layer:
@@ -237,7 +243,12 @@ class EncoderEngineBase:
         self._trunk_index = len(params)
         params += list(self._trunk_trainables())   # full fine-tuning (hip/engine_ft.py): every trunk tensor, in its order
         ops.init_tables()
-        self.flat = FlatParams(params, dev)
+        prev = _REUSE_FLAT[0] if _REUSE_FLAT else None
+        if (prev is not None and len(prev.params) == len(params) and all(p is q for p, q in zip(prev.params, params))
+                and prev.data.device.type == torch.device(dev).type and torch.device(dev).index in (None, prev.data.device.index)):
+            self.flat = prev   # an engine rebuilt for another operand format / frozen weights keeps the trained values and .grad
+        else:
+            self.flat = FlatParams(params, dev)
         self._zero_a = torch.zeros(8, H, dtype=F32, device=dev)
 
     full_ft = False
@@ -283,8 +294,9 @@ class EncoderEngineBase:
     h16 = BF16
 
     def _set_format(self, fp16):
-        """fp16 operands (set_operand_format): every frozen weight the forward reads, the head weight's per-forward cast and the
-        workspace's 16-bit buffers are IEEE fp16; the kernels get BSCLIP_OPERANDS_FP16.  Inference only in this release."""
+        """fp16 operands (set_operand_format): every frozen weight the forward (and, for the ViT, the backward) reads, the head
+        weight's per-forward cast and the workspace's 16-bit buffers are IEEE fp16; the kernels get BSCLIP_OPERANDS_FP16.  The ViT
+        trains on them; the BERT engines are inference-only."""
         self.fp16 = bool(fp16)
         self.h16 = F16 if self.fp16 else BF16
 
@@ -383,6 +395,7 @@ class ViTEngine(EncoderEngineBase):
             else:
                 base = q
                 qv.append(None)
+            # the transposed weights of the dX GEMMs in the operand format (the fp16 ViT trains too)
             lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(base.weight, base.bias, H, dev, h16)
             lay.src = (base.weight, blk.attn.proj.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight)   # f32 masters (exact forward)
             lay.ln1 = (_f32(blk.norm1.weight, dev), _f32(blk.norm1.bias, dev))
@@ -399,7 +412,7 @@ class ViTEngine(EncoderEngineBase):
         assert self.out_dim % 128 == 0, "head width must be a multiple of 128 for the HIP GEMM"
         self._setup_lora(qv, H, dev, [vit.head.weight, vit.head.bias])
         self.w_head_bf = torch.empty(self.out_dim, H, dtype=h16, device=dev)     # the head weight in the operand format, cast every forward
-        self.w_head_t = None if self.fp16 else torch.empty(H, self.out_dim, dtype=BF16, device=dev)
+        self.w_head_t = torch.empty(H, self.out_dim, dtype=h16, device=dev)
         self.ws = None
 
     # ------------------------------------------------------------------------------------------ workspace
@@ -447,13 +460,12 @@ class ViTEngine(EncoderEngineBase):
         ws["clsn"] = z(B, H)
         ws["st_f"] = z(B, 2, dt=F32)
         ws["h2_c"], ws["act_c"], ws["z_c"], ws["st_c"] = z(B, H), z(B, FF), z(B, FF, dt=torch.uint8), z(B, 2, dt=F32)   # last-block token-0 path
-        if self.fp16:    # inference only: no backward temporaries
-            self.ws = ws
-            return ws
-        # backward temporaries
+        # backward temporaries (16-bit ones in the operand format: an fp16 engine's gradient stream and dX operands are fp16, in
+        # units of the tower's static gradient scale 2^FP16_GRAD_SCALE_LOG2)
         ws["grad_bf16"] = GRAD_STREAM_BF16 and not self.full_ft
+        assert ws["grad_bf16"] or not self.fp16, "the fp16 backward runs on the 16-bit gradient stream"
         ws["dx"] = None if ws["grad_bf16"] else torch.zeros(M, H, dtype=F32, device=dev)
-        ws["dxb"] = torch.zeros(M, H, dtype=BF16, device=dev)
+        ws["dxb"] = torch.zeros(M, H, dtype=h16, device=dev)
         ws["dz"] = z(M, FF)
         ws["dh"] = z(M, H)
         ws["dctx"] = z(M, H)
@@ -461,13 +473,23 @@ class ViTEngine(EncoderEngineBase):
         ws["dt"] = z(M, 8, dt=F32)
         ws["dtp"], ws["dbp"] = z(self.heads, 2, M, 4, dt=F32), z(B * self.heads, 2, 4, 64, dt=F32)   # LoRA partial sums (ATTN_LORA)
         Bp = _pad64(B)
-        ws["dout_bf"] = torch.zeros(B, self.out_dim, dtype=BF16, device=dev)
-        ws["dout_t"] = torch.zeros(self.out_dim, Bp, dtype=BF16, device=dev)
-        ws["clsn_t"] = torch.zeros(H, Bp, dtype=BF16, device=dev)
+        ws["dout_bf"] = torch.zeros(B, self.out_dim, dtype=h16, device=dev)
+        ws["dout_t"] = torch.zeros(self.out_dim, Bp, dtype=h16, device=dev)
+        ws["clsn_t"] = torch.zeros(H, Bp, dtype=h16, device=dev)
+        if self.fp16:   # the head's dW in 2^s units, before bsclip_add_scaled_f32 takes the scale off into .grad
+            ws["gw_head"] = torch.empty(self.out_dim, H, dtype=F32, device=dev)
         ws["dclsn"] = z(B, H)
         ws["dz_c"], ws["dh_c"] = z(B, FF), z(B, H)
         self.ws = ws
         return ws
+
+    def backward_probes(self):
+        """(name, tensor) of the backward's 16-bit gradient buffers (BSCLIP_DETECT_ANOMALY on an fp16 engine: the scaled gradient
+        stream is where an fp16 overflow would show first).  What the last backward left in them: the shared temporaries hold
+        block 0's values (the head's for dout)."""
+        ws = self.ws
+        for name in ("dout_bf", "dxb", "dz", "dh", "dctx", "dqkv"):
+            yield f"the fp16 backward's {name}", ws[name]
 
     def anomaly_probes(self):
         """(name, tensor) of the forward's saved activations in execution order (BSCLIP_DETECT_ANOMALY).  The last block's
@@ -585,8 +607,17 @@ class ViTEngine(EncoderEngineBase):
         return out
 
     # ------------------------------------------------------------------------------------------- backward
+    # Static gradient scale of the fp16 backward (part 3a; profiles/r08_fp16_vit_training.jsonl): dL/dz of the head is
+    # multiplied by 2^s where it becomes the fp16 dout, so the whole gradient stream lives 2^s up, clear of fp16's subnormals; each
+    # trainable gradient is brought back by 2^-s (exact) before it is added into .grad.  s is the largest that leaves the largest
+    # scaled |gradient| of any site >= 2^4 under 65 504 at unit-sized cotangents (tests/test_20's: 1627 at s = 13, so 3254 at s = 14);
+    # a B = 256 InfoNCE step's cotangents are ~2^8 smaller (largest 6.9 at s = 13), and a share of its smallest values is subnormal.
+    FP16_GRAD_SCALE_LOG2 = 14
+    # measurement hook (tools/fp16_grad_scale.py, tests): a callable (site, tensor) called after each backward site writes its 16-bit
+    # gradient -- it may read the tensor back (host sync), so only eager runs set it.  None: no calls.
+    grad_probe = None
+
     def backward(self, dout):
-        self._no_fp16_backward()
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
@@ -595,12 +626,23 @@ class ViTEngine(EncoderEngineBase):
         self.flat.bind_grads()
         x = ws["x"]
         dx, dxb = ws["dx"], ws["dxb"]
-        # head: dW = dout^T clsn, db = colsum(dout), dclsn = dout W
-        ops.cast_f32_bf16(dout, ws["dout_bf"])
+        f16 = self.fp16
+        gs = self.FP16_GRAD_SCALE_LOG2 if f16 else None
+        # head: dW = dout^T clsn, db = colsum(dout), dclsn = dout W  (fp16: dout enters 2^s up; db is summed from the f32 dout)
+        if f16:
+            ops.cast_f32_f16_scaled(dout, ws["dout_bf"], gs)
+        else:
+            ops.cast_f32_bf16(dout, ws["dout_bf"])
+        probe = self.grad_probe or (lambda site, t: None)
+        probe("dout", ws["dout_bf"])
         ops.transpose_bf16(ws["dout_bf"], B, self.out_dim, ws["dout_t"])
         ops.transpose_bf16(ws["clsn"], B, H, ws["clsn_t"])
         gw = self.extra(0, grad=True)
-        ops.gemm(ws["dout_t"], ws["clsn_t"], gw, EPI_RESID_F32, resid=gw)
+        if f16:
+            ops.gemm(ws["dout_t"], ws["clsn_t"], ws["gw_head"], EPI_F32)
+            ops.add_scaled_f32(ws["gw_head"], gw, -gs)
+        else:
+            ops.gemm(ws["dout_t"], ws["clsn_t"], gw, EPI_RESID_F32, resid=gw)
         ops.colsum(dout, B, self.out_dim, self.extra(1, grad=True))
         ops.transpose_bf16(self.w_head_bf, self.out_dim, H, self.w_head_t)
         ops.gemm(ws["dout_bf"], self.w_head_t, ws["dclsn"], EPI_BF16)
@@ -623,34 +665,47 @@ class ViTEngine(EncoderEngineBase):
                 # token-0 rows only (row stride S*H), 1/197 of the work.
                 FF = self.FF
                 dxb_c = dxb.view(B, S * H)[:, :H]
+                probe("grad_stream", dxb_c)
                 ops.gemm(dxb_c, lay.w_fc2_t, ws["dz_c"], EPI_DGELU_BF16, aux=ws["z_c"])
+                probe("dfc1_out", ws["dz_c"])
                 ops.gemm(ws["dz_c"], lay.w_fc1_t, ws["dh_c"], EPI_BF16)
+                probe("dln2_out", ws["dh_c"])
                 dx_c = R.view(B, S * H)[:, :H]
                 ops.layernorm_bwd(x[2 * l + 1].view(B, S * H)[:, :H], ws["st_c"], lay.ln2[0], 0, g_resid=dx_c,
                                   g_gemm=ws["dh_c"], dx_f32=None if g16 else dx_c, dx_bf16=dxb_c)
+                probe("grad_stream", dxb_c)
                 ws["dctx"].zero_()
                 ops.gemm(dxb_c, lay.w_proj_t, ws["dctx"].view(B, S * H)[:, :H], EPI_BF16)
             else:
+                probe("grad_stream", dxb)
                 ops.gemm(dxb, lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
+                probe("dfc1_out", ws["dz"])
                 ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
+                probe("dln2_out", ws["dh"])
                 ops.layernorm_bwd(x[2 * l + 1], ws["st2"][l], lay.ln2[0], 0, g_resid=R, g_gemm=ws["dh"],
                                   dx_f32=None if g16 else dx, dx_bf16=dxb)
+                probe("grad_stream", dxb)
                 ops.gemm(dxb, lay.w_proj_t, ws["dctx"], EPI_BF16)
+            probe("dattn_out", ws["dctx"])
             lb = self.lora_b(l)
-            part = lb is not None and ATTN_LORA and not self.fp8    # dt / dB partial sums out of the attention backward
+            # dt / dB partial sums out of the attention backward (the fp16 backward has this form only)
+            part = lb is not None and (ATTN_LORA or f16) and not self.fp8
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
                          q_rows=1 if l == L - 1 else 0, lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
+            probe("dqkv", ws["dqkv"])
             if lb is not None:
                 gb = self.lora_b(l, grad=True)
                 if self.fp8:
                     ops.lora_grad_fp8(ws["dqkv"], ws["h1_8"][l], ws["t"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True),
                                       gb[0], gb[1])
                 elif part:
-                    ops.lora_grad_heads(ws["h1"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1])
+                    ops.lora_grad_heads(ws["h1"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1],
+                                        grad_scale_log2=gs)
                 else:
                     ops.lora_grad(ws["dqkv"], ws["h1"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1])
             if l > 0:  # nothing trainable sits below block 0 (patch-embed, cls, pos are frozen)
                 ops.gemm(ws["dqkv"], lay.wqkv_t, ws["dh"], EPI_BF16)
+                probe("dln1_out", ws["dh"])
                 ops.layernorm_bwd(x[2 * l], ws["st1"][l], lay.ln1[0], 0, g_resid=R, g_gemm=ws["dh"],
                                   dt=ws["dt"] if lb is not None else None,
                                   lora_a=self.lora_a(l) if lb is not None else None, dx_f32=None if g16 else dx, dx_bf16=dxb)
@@ -747,12 +802,12 @@ class BertEngine(EncoderEngineBase):
                 qb, vb = q, v
             w = torch.cat([qb.weight.detach(), k.weight.detach(), vb.weight.detach()], 0)
             b = torch.cat([qb.bias.detach(), k.bias.detach(), vb.bias.detach()], 0)
-            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(w, b, H, dev, h16)
+            lay.waug, lay.wqkv_t, lay.b_qkv = _pack_qkv(w, b, H, dev, h16, transposed=not self.fp16)
             lay.src = (w, layer.attention.output.dense.weight, layer.intermediate.dense.weight, layer.output.dense.weight)   # f32 masters
-            lay.w_o, lay.w_o_t, lay.b_o = _pack_linear(layer.attention.output.dense, dev, h16)
+            lay.w_o, lay.w_o_t, lay.b_o = _pack_linear(layer.attention.output.dense, dev, h16, transposed=not self.fp16)
             lay.ln_a = (_f32(layer.attention.output.LayerNorm.weight, dev), _f32(layer.attention.output.LayerNorm.bias, dev))
-            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(layer.intermediate.dense, dev, h16)
-            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(layer.output.dense, dev, h16)
+            lay.w_fc1, lay.w_fc1_t, lay.b_fc1 = _pack_linear(layer.intermediate.dense, dev, h16, transposed=not self.fp16)
+            lay.w_fc2, lay.w_fc2_t, lay.b_fc2 = _pack_linear(layer.output.dense, dev, h16, transposed=not self.fp16)
             lay.ln_b = (_f32(layer.output.LayerNorm.weight, dev), _f32(layer.output.LayerNorm.bias, dev))
             if self.fp8:
                 self._pack_fp8(lay, w, layer.intermediate.dense.weight, layer.output.dense.weight, dev)
@@ -761,7 +816,7 @@ class BertEngine(EncoderEngineBase):
         self.head = head
         if head == "mlm_softmax_mean":
             tr, dec = head_modules
-            self.w_tr, self.w_tr_t, self.b_tr = _pack_linear(tr.dense, dev, h16)
+            self.w_tr, self.w_tr_t, self.b_tr = _pack_linear(tr.dense, dev, h16, transposed=not self.fp16)
             self.src_tr = tr.dense.weight
             self.ln_t = (_f32(tr.LayerNorm.weight, dev), _f32(tr.LayerNorm.bias, dev))
             self.eps_t = float(tr.LayerNorm.eps)
@@ -1255,26 +1310,44 @@ OPERAND_FORMATS = ("bf16", "fp16")
 
 
 def wants_fp16(module):
-    """``module.hip_operands = "fp16"`` (set_operand_format): the encoder's forward runs on fp16 operands (inference only)."""
+    """``module.hip_operands = "fp16"`` (set_operand_format): the encoder runs on fp16 operands -- the LoRA ViT forward and backward
+    (training included), the BarcodeBERT and text encoders' forward only (inference)."""
     return getattr(module, "hip_operands", "bf16") == "fp16"
 
 
-def set_operand_format(model, fmt):
+# set_operand_format's tower names -> the attribute that marks the encoder module of that tower
+OPERAND_TOWERS = {"image": "lora_vit", "dna": "lora_barcode_bert", "language": "lora_bert"}
+
+
+def set_operand_format(model, fmt, towers=None):
     """Select the 16-bit operand format of the ViT, BarcodeBERT and text encoders under ``model``: "bf16" (default) or "fp16".
-    fp16 runs every GEMM, attention product and LayerNorm output of the forward on IEEE fp16 (same MFMA rate, 3 more mantissa bits:
-    DESIGN.md 4); its engines are inference-only in this release -- eval() and torch.no_grad().  Engines are rebuilt on the next
-    forward."""
+    fp16 runs every GEMM, attention product and LayerNorm output on IEEE fp16 (same MFMA rate, 3 more mantissa bits: DESIGN.md 4).
+    The image tower (LoRA ViT) also trains on fp16: its backward runs on fp16 operands with a static gradient scale, and .grad holds
+    the true gradient.  The DNA and text towers' fp16 engines are inference-only -- eval() and torch.no_grad() -- until their fp16
+    backward (dropout forms) exists.  ``towers``: a subset of ("image", "dna", "language"), default None = every tower; the others
+    keep their format (a mixed step: image on fp16, DNA and text on bf16).  Engines are rebuilt on the next forward; their flat
+    trainable buffers (LoRA, heads, the optimizer's moments keyed on them) carry over."""
     if fmt not in OPERAND_FORMATS:
         raise ValueError(f"operand format must be 'bf16' or 'fp16', not {fmt!r}")
+    if towers is None:
+        towers = tuple(OPERAND_TOWERS)
+    elif isinstance(towers, str):
+        towers = (towers,)
+    bad = [t for t in towers if t not in OPERAND_TOWERS]
+    if bad or not towers:
+        raise ValueError(f"towers must be a non-empty subset of {tuple(OPERAND_TOWERS)}, not {towers!r}")
+    marks = [OPERAND_TOWERS[t] for t in towers]
     for m in model.modules():
-        if hasattr(m, "lora_vit") or hasattr(m, "lora_barcode_bert") or hasattr(m, "lora_bert"):
+        if any(hasattr(m, a) for a in marks):
             m.hip_operands = fmt
+            if getattr(m, "_engine", None) is not None:
+                m._engine_prev = m._engine   # its flat buffer goes to the rebuilt engine (_engine_for)
             m._engine = None
 
 
 def _check_fp16(module):
-    """fp16 operands: an inference-only forward of the LoRA-regime engines on the 16-bit streams -- everything else is refused
-    before an engine is built."""
+    """fp16 operands: the LoRA-regime engines on the 16-bit streams -- the ViT in train or eval mode, the BERT engines for inference
+    only; everything else is refused before an engine is built."""
     who = type(module).__name__
     if wants_fp8(module):
         raise ValueError(f"{who}: fp16 operands cannot be combined with set_precision(..., 'fp8')")
@@ -1283,7 +1356,12 @@ def _check_fp16(module):
     if EXACT_FORWARD or not RESID_STREAM_BF16:
         raise ValueError(f"{who}: fp16 operands run on the 16-bit residual stream: not with BSCLIP_PARITY=1 / 2 "
                          "(set_parity_mode) or BSCLIP_RESID_STREAM=f32")
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
+    trains = module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()))
+    if hasattr(module, "lora_vit"):
+        if trains and not GRAD_STREAM_BF16:
+            raise ValueError(f"{who}: the fp16 backward runs on the 16-bit gradient stream: not with BSCLIP_GRAD_STREAM=f32")
+        return
+    if trains:
         raise RuntimeError(f"{who}: the fp16-operand forward is inference-only (the fp16 backward is not built yet): call "
                            "model.eval() and run it under torch.no_grad(), or set_operand_format(model, 'bf16')")
 
@@ -1291,6 +1369,9 @@ def _check_fp16(module):
 def wants_full_ft(module):
     """``module.hip_full_ft`` (set by load_clip_model for ``disable_lora: true``): every parameter is trained."""
     return bool(getattr(module, "hip_full_ft", False))
+
+
+_REUSE_FLAT = []   # the flat buffer of the engine being replaced (_engine_for -> _setup_lora): reused when it holds the same tensors
 
 
 def _engine_for(module, build):
@@ -1304,7 +1385,13 @@ def _engine_for(module, build):
         if not torch.cuda.is_available():
             raise RuntimeError("bioscanclip needs a ROCm GPU: all arithmetic runs in libbsclip_hip.so "
                                "(there is no CPU/torch fallback)")
-        eng = build()
+        old = getattr(module, "_engine", None) or getattr(module, "_engine_prev", None)
+        _REUSE_FLAT[:] = [old.flat] if old is not None and old.flat.valid() else []
+        try:
+            eng = build()
+        finally:
+            _REUSE_FLAT.clear()
+        module._engine_prev = None
         eng._frozen_sig = _frozen_signature(module, eng)
         module._engine = eng
     return eng

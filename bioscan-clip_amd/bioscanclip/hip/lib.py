@@ -98,11 +98,14 @@ SIGNATURES = {
     "bsclip_lora_grad_workspace_floats": (L, [I]),
     "bsclip_lora_grad": (I, [P, I, P, I, I, I, P, P, P, P, P, P, P]),
     "bsclip_lora_grad_heads": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "bsclip_lora_grad_heads_f16": (I, [P, I, I, I, I, P, P, P, P, P, P, P, I, P]),
+    "bsclip_add_scaled_f32": (I, [P, L, I, P, P]),
     "bsclip_lora_grad_fp8": (I, [P, I, P, I, P, I, I, I, P, P, P, P, P, P, P]),
     "bsclip_colsum": (I, [P, I, I, I, I, P, P]),
     "bsclip_transpose_bf16": (I, [P, I, I, I, P, I, P]),
     "bsclip_cast_f32_bf16": (I, [P, L, P, P]),
     "bsclip_cast_f32_f16": (I, [P, L, P, P]),
+    "bsclip_cast_f32_f16_scaled": (I, [P, L, I, P, P]),
     "bsclip_waug_set_lora_layers": (I, [P, I, I, I, P]),
     "bsclip_ln_param_grad_workspace_floats": (L, [I]),
     "bsclip_ln_param_grad": (I, [P, I, I, P, I, I, P, I, P, I, P, P, I, F, U, P, P, P, P]),

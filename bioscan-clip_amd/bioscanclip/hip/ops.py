@@ -229,42 +229,52 @@ def layernorm_bwd(x, stats, gamma, mode, g_resid=None, g_gemm=None, dt=None, lor
     """``g_resid`` / ``dx_f32`` are the residual-gradient stream in / out: f32, or bf16 (half the bytes; the dtype of each
     tensor is passed on as ``resid_flags``).  ``dx_bf16`` is the next dX GEMM's operand (carries ``dropout``'s mask); the exact
     backward passes ``g_gemm`` and ``dx_bf16`` as f32 tensors, or takes the operand as ``dx_split3``: bf16 [M, >= 3H] = [hi | lo | hi],
-    the A operand of the next split-bf16 dX GEMM (instead of ``dx_bf16``)."""
+    the A operand of the next split-bf16 dX GEMM (instead of ``dx_bf16``).
+    fp16 operands (BSCLIP_OPERANDS_FP16, the LoRA ViT's backward): x fp16, and every 16-bit tensor passed (g_resid, g_gemm, dx_f32,
+    dx_bf16) fp16 as well; no dropout, no f32 / split operand forms."""
     ld_x = _rowmajor(x, "x")
     H = gamma.numel()
     M = x.shape[0] if M is None else M
-    _req(x.dtype in (F32, BF16) and x.shape[1] >= H and M <= x.shape[0], "layernorm_bwd: bad x")
+    _req(x.dtype in (F32, BF16, F16) and x.shape[1] >= H and M <= x.shape[0], "layernorm_bwd: bad x")
+    f16 = x.dtype == F16
+    if f16:
+        _req(dropout is None and in_dropout is None and dx_split3 is None
+             and all(t is None or t.dtype == F16 for t in (g_resid, g_gemm, dx_f32, dx_bf16)),
+             "layernorm_bwd: fp16 operands take fp16 g_resid / g_gemm / dx_f32 / dx_bf16, no dropout, no split output")
+    else:
+        _req(all(t is None or t.dtype != F16 for t in (g_resid, g_gemm, dx_f32, dx_bf16)), "layernorm_bwd: fp16 tensors need an fp16 x")
+    b16 = (BF16, F16)
     _req(stats.dtype == F32 and stats.numel() >= 2 * M, "layernorm_bwd: stats")
     ld_g = ld_dxb = ld_gr = ld_dx = 0
     if g_resid is not None:
         ld_gr = _rowmajor(g_resid, "g_resid")
-        _req(g_resid.dtype in (F32, BF16) and g_resid.shape[0] >= M and g_resid.shape[1] >= H, "g_resid must be f32 / bf16 [M,>=H]")
+        _req(g_resid.dtype in (F32, BF16, F16) and g_resid.shape[0] >= M and g_resid.shape[1] >= H, "g_resid must be f32 / bf16 [M,>=H]")
     if g_gemm is not None:
         ld_g = _rowmajor(g_gemm, "g_gemm")
-        _req(g_gemm.dtype in (BF16, F32) and g_gemm.shape[0] >= M and g_gemm.shape[1] >= H, "g_gemm must be bf16 / f32 [M,>=H]")
+        _req(g_gemm.dtype in (BF16, F32, F16) and g_gemm.shape[0] >= M and g_gemm.shape[1] >= H, "g_gemm must be bf16 / f32 [M,>=H]")
     if dt is not None:
         _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt must be f32 [M,8]")
         _req(lora_a is not None and tuple(lora_a.shape) == (8, H) and lora_a.dtype == F32 and lora_a.is_contiguous(),
              "lora_a must be f32 [8,H]")
     if dx_f32 is not None:
         ld_dx = _rowmajor(dx_f32, "dx_f32")
-        _req(dx_f32.dtype in (F32, BF16) and dx_f32.shape[0] >= M and dx_f32.shape[1] >= H, "dx_f32 must be f32 / bf16 [M,>=H]")
+        _req(dx_f32.dtype in (F32, BF16, F16) and dx_f32.shape[0] >= M and dx_f32.shape[1] >= H, "dx_f32 must be f32 / bf16 [M,>=H]")
     if dx_split3 is not None:
         _req(dx_bf16 is None and dx_split3.dtype == BF16 and dx_split3.shape[0] >= M and dx_split3.shape[1] >= 3 * H,
              "dx_split3: bf16 [M, >= 3H], instead of dx_bf16")
         dx_bf16 = dx_split3
     if dx_bf16 is not None:
         ld_dxb = _rowmajor(dx_bf16, "dx_bf16")
-        _req(dx_bf16.dtype in (BF16, F32) and dx_bf16.shape[0] >= M and dx_bf16.shape[1] >= H, "dx_bf16 (bf16 / f32 operand) too small")
-    check(_l.load().bsclip_layernorm_bwd(_p(x), ld_x, int(x.dtype == BF16), _p(stats), _p(gamma), M, H, _p(g_resid),
+        _req(dx_bf16.dtype in (BF16, F32, F16) and dx_bf16.shape[0] >= M and dx_bf16.shape[1] >= H, "dx_bf16 (bf16 / f32 operand) too small")
+    check(_l.load().bsclip_layernorm_bwd(_p(x), ld_x, (1 | OPERANDS_FP16) if f16 else int(x.dtype == BF16), _p(stats), _p(gamma), M, H, _p(g_resid),
                                          ld_gr, _p(g_gemm), ld_g, _p(dt), _p(lora_a) if dt is not None else None,
                                          int(mode), _p(dx_f32), ld_dx, _p(dx_bf16), ld_dxb,
                                          0.0 if dropout is None else float(dropout[0]),
                                          0 if dropout is None else int(dropout[1]) & 0xFFFFFFFF,
                                          0.0 if in_dropout is None else float(in_dropout[0]),
                                          0 if in_dropout is None else int(in_dropout[1]) & 0xFFFFFFFF,
-                                         (1 if g_resid is not None and g_resid.dtype == BF16 else 0)
-                                         | (2 if dx_f32 is not None and dx_f32.dtype == BF16 else 0)
+                                         (1 if g_resid is not None and g_resid.dtype in b16 else 0)
+                                         | (2 if dx_f32 is not None and dx_f32.dtype in b16 else 0)
                                          | (4 if g_gemm is not None and g_gemm.dtype == F32 else 0)
                                          | (8 if dx_bf16 is not None and dx_bf16.dtype == F32 else 0)
                                          | (16 if dx_split3 is not None else 0), _stream()))
@@ -300,10 +310,14 @@ def attn_bwd(qkv, dctx, lse, B, S, heads, scale, dqkv, key_bias=None, dropout=No
     """``keep_bits``: the words the forward of the SAME (seed, step) left; None = re-hash the decisions (same masks, slower).
     ``lora`` = (t_aug, lora_b, dt_partial, db_partial): also leave the LoRA gradients' partial sums (``lora_grad_heads`` reduces them):
     t_aug bf16 [>= B S, >= 8] with t in columns 0..7 (a view of the LayerNorm output's t block), lora_b f32 [2, H, 4], dt_partial f32
-    [heads, 2, B S, 4], db_partial f32 [B heads, 2, 4, 64]."""
+    [heads, 2, B S, 4], db_partial f32 [B heads, 2, 4, 64].
+    fp16 operands (BSCLIP_OPERANDS_FP16, the LoRA ViT's backward): qkv, dctx, dqkv (and t_aug) fp16; S = 197, no dropout / keep_bits."""
     ld_qkv, ld_ctx, ld_d = _rowmajor(qkv, "qkv"), _rowmajor(dctx, "dctx"), _rowmajor(dqkv, "dqkv")
     _keep_bits_ok(keep_bits, B, S, heads, "attn_bwd")
-    _req(all(t.dtype == BF16 for t in (qkv, dctx, dqkv)) and lse.dtype == F32, "attn_bwd dtypes")
+    h16 = qkv.dtype
+    _req(h16 in (BF16, F16) and all(t.dtype == h16 for t in (qkv, dctx, dqkv)) and lse.dtype == F32, "attn_bwd dtypes")
+    fmt = OPERANDS_FP16 if h16 == F16 else 0
+    _req(not fmt or (dropout is None and keep_bits is None), "attn_bwd: fp16 operands take no dropout / keep_bits")
     _req(min(qkv.shape[0], dctx.shape[0], dqkv.shape[0]) >= B * S, "attn_bwd: rows")
     _req(qkv.shape[1] >= 3 * heads * 64 and dqkv.shape[1] >= 3 * heads * 64 and dctx.shape[1] >= heads * 64
          and lse.numel() >= B * heads * S, "attn_bwd: cols")
@@ -313,17 +327,17 @@ def attn_bwd(qkv, dctx, lse, B, S, heads, scale, dqkv, key_bias=None, dropout=No
     if lora is not None:
         t_aug, lora_b, dtp, dbp = lora
         ld_t = _rowmajor(t_aug, "t_aug")
-        _req(t_aug.dtype == BF16 and t_aug.shape[0] >= B * S and t_aug.shape[1] >= 8, "attn_bwd: t_aug bf16 [>= B S, >= 8]")
+        _req(t_aug.dtype == h16 and t_aug.shape[0] >= B * S and t_aug.shape[1] >= 8, "attn_bwd: t_aug 16-bit [>= B S, >= 8] (qkv's format)")
         _req(lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, heads * 64, 4), "attn_bwd: lora_b f32 [2,H,4]")
         _req(dtp.dtype == F32 and dtp.is_contiguous() and dtp.numel() >= heads * B * S * 8
              and dbp.dtype == F32 and dbp.is_contiguous() and dbp.numel() >= B * heads * 512, "attn_bwd: dt_partial / db_partial sizes")
         _req(dp == 0.0 or keep_bits is not None, "attn_bwd: the LoRA partials under dropout need the forward's keep_bits")
         check(_l.load().bsclip_attn_bwd_lora(_p(qkv), ld_qkv, _p(dctx), ld_ctx, _p(lse), B, S, heads, _p(key_bias), float(scale), _p(dqkv),
-                                             ld_d, int(q_rows), _p(keep_bits), _p(t_aug), ld_t, _p(lora_b), _p(dtp), _p(dbp), dp, ds,
+                                             ld_d, int(q_rows) | fmt, _p(keep_bits), _p(t_aug), ld_t, _p(lora_b), _p(dtp), _p(dbp), dp, ds,
                                              _stream()))
         return
     check(_l.load().bsclip_attn_bwd(_p(qkv), ld_qkv, _p(dctx), ld_ctx, _p(lse), B, S, heads, _p(key_bias),
-                                    float(scale), _p(dqkv), ld_d, int(q_rows), _p(keep_bits), dp, ds, _stream()))
+                                    float(scale), _p(dqkv), ld_d, int(q_rows) | fmt, _p(keep_bits), dp, ds, _stream()))
 
 
 def split3_rows(src, dst, M=None, K=None):
@@ -640,15 +654,25 @@ def lora_grad(dqkv, h_aug, M, H, lora_b, dt, dA, dBq, dBv):
                                      _p(_lora_grad_workspace(H, dqkv.device)), _stream()))
 
 
-def lora_grad_heads(h_aug, M, H, B, dt_partial, db_partial, dt, dA, dBq, dBv):
-    """``lora_grad`` from the partial sums ``attn_bwd(..., lora=...)`` left: dt [M, 8], dBq / dBv and dA accumulate as ``lora_grad`` (dt_partial f32 [heads, 2, M, 4], db_partial f32 [B heads, 2, 4, 64])."""
+def lora_grad_heads(h_aug, M, H, B, dt_partial, db_partial, dt, dA, dBq, dBv, grad_scale_log2=None):
+    """``lora_grad`` from the partial sums ``attn_bwd(..., lora=...)`` left: dt [M, 8], dBq / dBv and dA accumulate as ``lora_grad`` (dt_partial f32 [heads, 2, M, 4], db_partial f32 [B heads, 2, 4, 64]).
+    fp16 ``h_aug`` (bsclip_lora_grad_heads_f16): the partials and dt hold 2^grad_scale_log2 times the gradient; dA / dB get the true one."""
     heads = H // 64
-    _req(h_aug.dtype == BF16 and h_aug.shape[0] >= M and h_aug.shape[1] >= H and M % B == 0, "lora_grad_heads: h_aug bf16 [M, >= H]")
+    if h_aug.dtype == F16:
+        _req(grad_scale_log2 is not None and 0 <= int(grad_scale_log2) <= 64, "lora_grad_heads: fp16 h_aug needs grad_scale_log2 in [0, 64]")
+    else:
+        _req(grad_scale_log2 is None, "lora_grad_heads: grad_scale_log2 is for the fp16 form")
+    _req(h_aug.dtype in (BF16, F16) and h_aug.shape[0] >= M and h_aug.shape[1] >= H and M % B == 0, "lora_grad_heads: h_aug bf16 [M, >= H]")
     _req(dt_partial.dtype == F32 and dt_partial.is_contiguous() and dt_partial.numel() >= heads * M * 8
          and db_partial.dtype == F32 and db_partial.is_contiguous() and db_partial.numel() >= B * heads * 512, "lora_grad_heads: partials")
     _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
     _req(dA.dtype == F32 and dA.is_contiguous() and tuple(dA.shape) == (8, H), "dA f32 [8,H]")
     _req(all(t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (H, 4) for t in (dBq, dBv)), "dB f32 [H,4]")
+    if h_aug.dtype == F16:
+        check(_l.load().bsclip_lora_grad_heads_f16(_p(h_aug), _rowmajor(h_aug, "h_aug"), M, H, B, _p(dt_partial), _p(db_partial), _p(dt),
+                                                   _p(dA), _p(dBq), _p(dBv), _p(_lora_grad_workspace(H, h_aug.device)),
+                                                   OPERANDS_FP16 | int(grad_scale_log2), _stream()))
+        return
     check(_l.load().bsclip_lora_grad_heads(_p(h_aug), _rowmajor(h_aug, "h_aug"), M, H, B, _p(dt_partial), _p(db_partial), _p(dt), _p(dA),
                                            _p(dBq), _p(dBv), _p(_lora_grad_workspace(H, h_aug.device)), _stream()))
 
@@ -673,7 +697,8 @@ def colsum(g, M, N, out):
 
 
 def transpose_bf16(src, R, C, dst):
-    _req(src.dtype == BF16 and dst.dtype == BF16, "transpose_bf16 dtypes")
+    """dst[C, R] = src[R, C]^T for 16-bit words: bf16, or fp16 (the kernel only moves the words)."""
+    _req(src.dtype in (BF16, F16) and dst.dtype == src.dtype, "transpose_bf16 dtypes (bf16 or fp16, both the same)")
     _req(src.shape[0] >= R and src.shape[1] >= C and dst.shape[0] >= C and dst.shape[1] >= R, "transpose_bf16 shapes")
     check(_l.load().bsclip_transpose_bf16(_p(src), _rowmajor(src, "src"), R, C, _p(dst), _rowmajor(dst, "dst"), _stream()))
 
@@ -702,6 +727,20 @@ def cast_f32_bf16(src, dst):
          and dst.numel() >= src.numel(), "cast_f32_bf16")
     fn = _l.load().bsclip_cast_f32_f16 if dst.dtype == F16 else _l.load().bsclip_cast_f32_bf16
     check(fn(_p(src), src.numel(), _p(dst), _stream()))
+
+
+def cast_f32_f16_scaled(src, dst, scale_log2):
+    """dst fp16 = RNE(src * 2^scale_log2): the scaled dout of the fp16-operand backward (one static power of two per tower)."""
+    _req(src.dtype == F32 and dst.dtype == F16 and src.is_contiguous() and dst.is_contiguous() and dst.numel() >= src.numel(),
+         "cast_f32_f16_scaled")
+    check(_l.load().bsclip_cast_f32_f16_scaled(_p(src), src.numel(), int(scale_log2), _p(dst), _stream()))
+
+
+def add_scaled_f32(src, dst, scale_log2):
+    """dst += src * 2^scale_log2 (f32, same size, contiguous): exact removal of a static gradient scale."""
+    _req(src.dtype == F32 and dst.dtype == F32 and src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel(),
+         "add_scaled_f32")
+    check(_l.load().bsclip_add_scaled_f32(_p(src), src.numel(), int(scale_log2), _p(dst), _stream()))
 
 
 def waug_set_lora_layers(table, layers, ld_w, H, dtype=BF16):

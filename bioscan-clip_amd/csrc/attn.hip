@@ -222,7 +222,12 @@ __device__ __forceinline__ bf16x8 small_frag(const bf16_t* tab, int len, int c0,
     return __builtin_bit_cast(bf16x8, u32x4{a.x, a.y, b.x, b.y});
 }
 
-template <int NB, bool DROP, bool DIAG = false, int TAIL = 32, bool BITS = false, bool PRE = false, bool LORA = false>
+// F16 (bsclip_attn_bwd[_lora] with q_rows | BSCLIP_OPERANDS_FP16): q, k, v, dO, dq | dk | dv and the t block are IEEE fp16 and every
+// product (S, dP, dQ, dK, dV and the LoRA partials) runs on v_mfma_f32_32x32x16_f16; P and dS are rounded to fp16 (RNE), lse, delta and
+// the softmax arithmetic stay f32.  The LoRA-B rows enter as hi + lo fp16 parts of 2^LORA_B_SHIFT B (undone in f32 on the dt sums), so
+// that B's small entries stay clear of fp16's subnormal range.  No dropout (the ViT's forms only).
+constexpr float LORA_B_UP = 256.f, LORA_B_DOWN = 1.f / 256.f;   // 2^LORA_B_SHIFT, LORA_B_SHIFT = 8: exact in both directions
+template <int NB, bool DROP, bool DIAG = false, int TAIL = 32, bool BITS = false, bool PRE = false, bool LORA = false, bool F16 = false>
 __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_t* __restrict__ qkv, int ld,
                                                                    const bf16_t* __restrict__ dctx, int ld_ctx,
                                                                    const float* __restrict__ lse, int S, int heads,
@@ -232,6 +237,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
                                                                    const unsigned* __restrict__ kbits = nullptr,
                                                                    LoraPart lp = LoraPart{}) {
     static_assert(!(BITS && !DROP) && !(PRE && DROP), "BITS needs dropout, PRE excludes it");
+    static_assert(!F16 || !DROP, "fp16 operands: no dropout form");
     constexpr int SP = NB * 32;
     constexpr int RM = SP * ROWB;
     BSCLIP_DROP_RESOLVE(drop);
@@ -287,9 +293,10 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             const int is_v = tid >> 6, d = tid & 63;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bf16_t hi = f2bf(b_row[j]);
+                const float bj = F16 ? b_row[j] * LORA_B_UP : b_row[j];
+                const bf16_t hi = f2h<F16>(bj);
                 sBt[((is_v * 2 + 0) * 4 + j) * 64 + d] = hi;
-                sBt[((is_v * 2 + 1) * 4 + j) * 64 + d] = f2bf(b_row[j] - bf2f(hi));
+                sBt[((is_v * 2 + 1) * 4 + j) * 64 + d] = f2h<F16>(bj - h2f<F16>(hi));
             }
         }
         if (tid < SP) {    // t^T of the item: [8 j][SP tokens], zero past S
@@ -307,8 +314,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
 #pragma unroll
             for (int g = 0; g < 4; ++g) {   // [token][d - 32 dt] bf16, 72-byte rows
                 uint2 o;
-                o.x = pack_bf2(acc[dt][4 * g + 0], acc[dt][4 * g + 1]);
-                o.y = pack_bf2(acc[dt][4 * g + 2], acc[dt][4 * g + 3]);
+                o.x = pack_h2<F16>(acc[dt][4 * g + 0], acc[dt][4 * g + 1]);
+                o.y = pack_h2<F16>(acc[dt][4 * g + 2], acc[dt][4 * g + 3]);
                 *reinterpret_cast<uint2*>(tile + (lane & 31) * 72 + (8 * g + 4 * h) * 2) = o;
             }
         };
@@ -316,7 +323,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             f32x16 dbacc = zero16();
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
-                dbacc = mfma32(small_frag(tt, SP, tok0 + 16 * s2, lane), frag_tr_lin(tile, 72, 0, 16 * s2, lane), dbacc);
+                dbacc = mfma32<F16>(small_frag(tt, SP, tok0 + 16 * s2, lane), frag_tr_lin(tile, 72, 0, 16 * s2, lane), dbacc);
             kacc[dt] += f32x4{dbacc[0], dbacc[1], dbacc[2], dbacc[3]};
         };
         put_tile(0);
@@ -325,16 +332,18 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 xb = pack8(acc[dt], s2);   // k = d = 32 dt + 16 s2 + (pack8 order)
-                dtacc = mfma32(small_frag(bt, 64, 32 * dt + 16 * s2, lane), xb, dtacc);
-                dtacc2 = mfma32(small_frag(bt + 4 * 64, 64, 32 * dt + 16 * s2, lane), xb, dtacc2);
+                const bf16x8 xb = pack8<F16>(acc[dt], s2);   // k = d = 32 dt + 16 s2 + (pack8 order)
+                dtacc = mfma32<F16>(small_frag(bt, 64, 32 * dt + 16 * s2, lane), xb, dtacc);
+                dtacc2 = mfma32<F16>(small_frag(bt + 4 * 64, 64, 32 * dt + 16 * s2, lane), xb, dtacc2);
             }
         db_half(0);
         put_tile(1);
         const int tok = tok0 + (lane & 31);
-        if (h == 0 && tok < S)   // accumulator rows 0..3 = j, on lane half 0
-            *reinterpret_cast<f32x4*>(lp.dtp + ((((size_t)hd * 2 + is_v) * (gridDim.x / heads) + b) * S + tok) * 4) =
-                f32x4{dtacc[0] + dtacc2[0], dtacc[1] + dtacc2[1], dtacc[2] + dtacc2[2], dtacc[3] + dtacc2[3]};
+        if (h == 0 && tok < S) {   // accumulator rows 0..3 = j, on lane half 0
+            f32x4 dts = f32x4{dtacc[0] + dtacc2[0], dtacc[1] + dtacc2[1], dtacc[2] + dtacc2[2], dtacc[3] + dtacc2[3]};
+            if constexpr (F16) dts *= LORA_B_DOWN;
+            *reinterpret_cast<f32x4*>(lp.dtp + ((((size_t)hd * 2 + is_v) * (gridDim.x / heads) + b) * S + tok) * 4) = dts;
+        }
         db_half(1);
     };
     // a phase's dB^T sums of the 4 waves -> db_partial[item][is_v][j][d]; call with all the workgroup's threads
@@ -422,8 +431,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                s = mfma32(frag_rm(sR0, 32 * kt, ks, lane), qf[ks], s);     // S^T[key, q] + bias / scale
-                dp = mfma32(frag_rm(sR1, 32 * kt, ks, lane), dof[ks], dp);  // dP^T[key, q]
+                s = mfma32<F16>(frag_rm(sR0, 32 * kt, ks, lane), qf[ks], s);     // S^T[key, q] + bias / scale
+                dp = mfma32<F16>(frag_rm(sR1, 32 * kt, ks, lane), dof[ks], dp);  // dP^T[key, q]
             }
             const int ng = kt == NB - 1 ? tail_groups<TAIL>() : 4;   // register groups that can hold a valid key (compile time)
 #pragma unroll
@@ -443,8 +452,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
                     s[4 * g + i] = pr;
                 }
             }
-            p16[kt][0] = pack8(s, 0);
-            p16[kt][1] = pack8(s, 1);
+            p16[kt][0] = pack8<F16>(s, 0);
+            p16[kt][1] = pack8<F16>(s, 1);
         }
         const float delta_q = dpart + __shfl_xor(dpart, 32, 64);
         if (h == 0) sDelta[q0 + (lane & 31)] = PRE ? -delta_q : delta_q;
@@ -456,7 +465,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             asm volatile("" ::: "memory");
             f32x16 dp = zero16();
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) dp = mfma32(frag_rm(sR1, 32 * kt, ks, lane), dof[ks], dp);
+            for (int ks = 0; ks < 4; ++ks) dp = mfma32<F16>(frag_rm(sR1, 32 * kt, ks, lane), dof[ks], dp);
             const int ng = kt == NB - 1 ? tail_groups<TAIL>() : 4, ns2 = kt == NB - 1 ? tail_ksteps<TAIL>() : 2;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -475,7 +484,9 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const unsigned w = pu[2 * g2 + (i >> 1)];
-                        const float pr = __uint_as_float((i & 1) ? (w & 0xffff0000u) : (w << 16));
+                        float pr;
+                        if constexpr (F16) pr = h2f<true>((bf16_t)((i & 1) ? (w >> 16) : (w & 0xffffu)));
+                        else pr = __uint_as_float((i & 1) ? (w & 0xffff0000u) : (w << 16));
                         if constexpr (DROP) dp[4 * g + i] = pr * (dp[4 * g + i] * k4[i] - delta_q);
                         else dp[4 * g + i] = pr * (dp[4 * g + i] - delta_q);
                     }
@@ -484,10 +495,10 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 if (s2 >= ns2) continue;
-                const bf16x8 dsb = pack8(dp, s2);
+                const bf16x8 dsb = pack8<F16>(dp, s2);
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
-                    dq[dt] = mfma32(frag_tr(sR0, 32 * dt, 32 * kt + 16 * s2, lane), dsb, dq[dt]);  // K^T dS^T
+                    dq[dt] = mfma32<F16>(frag_tr(sR0, 32 * dt, 32 * kt + 16 * s2, lane), dsb, dq[dt]);  // K^T dS^T
             }
         }
         const int q = q0 + (lane & 31);
@@ -497,9 +508,9 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
 #pragma unroll
                 for (int r = 0; r < 16; ++r) dq[dt][r] *= scale;
             lora_part(dq, 0, q0, kacc);
-            if (q < S) store_dt(dq, 1.0f, dqb + (size_t)q * ld_d, lane);
+            if (q < S) store_dt<F16>(dq, 1.0f, dqb + (size_t)q * ld_d, lane);
         } else {
-            if (q < S) store_dt(dq, scale, dqb + (size_t)q * ld_d, lane);
+            if (q < S) store_dt<F16>(dq, scale, dqb + (size_t)q * ld_d, lane);
         }
         if (blk == wave) stamp(7);
     }
@@ -558,8 +569,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                s = mfma32(frag_rm(sR0, 32 * qt, ks, lane), kf[ks], s);    // S[q, key] + bias / scale
-                dp = mfma32(frag_rm(sR1, 32 * qt, ks, lane), vf[ks], dp);  // dP[q, key]
+                s = mfma32<F16>(frag_rm(sR0, 32 * qt, ks, lane), kf[ks], s);    // S[q, key] + bias / scale
+                dp = mfma32<F16>(frag_rm(sR1, 32 * qt, ks, lane), vf[ks], dp);  // dP[q, key]
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -597,11 +608,11 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
             }
 #pragma unroll
             for (int s2 = 0; s2 < ns2; ++s2) {
-                const bf16x8 pb = pack8(s, s2), dsb = pack8(dp, s2);
+                const bf16x8 pb = pack8<F16>(s, s2), dsb = pack8<F16>(dp, s2);
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    dv[dt] = mfma32(frag_tr(sR1, 32 * dt, 32 * qt + 16 * s2, lane), pb, dv[dt]);   // dO^T P
-                    dk[dt] = mfma32(frag_tr(sR0, 32 * dt, 32 * qt + 16 * s2, lane), dsb, dk[dt]);  // Q^T dS
+                    dv[dt] = mfma32<F16>(frag_tr(sR1, 32 * dt, 32 * qt + 16 * s2, lane), pb, dv[dt]);   // dO^T P
+                    dk[dt] = mfma32<F16>(frag_tr(sR0, 32 * dt, 32 * qt + 16 * s2, lane), dsb, dk[dt]);  // Q^T dS
                 }
             }
         };
@@ -612,8 +623,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
         const int key = k0 + (lane & 31);
         if constexpr (LORA) lora_part(dv, 1, k0, kacc);
         if (key < S) {
-            store_dt(dk, scale, dqb + (size_t)key * ld_d + HW, lane);
-            store_dt(dv, 1.0f, dqb + (size_t)key * ld_d + 2 * HW, lane);
+            store_dt<F16>(dk, scale, dqb + (size_t)key * ld_d + HW, lane);
+            store_dt<F16>(dv, 1.0f, dqb + (size_t)key * ld_d + 2 * HW, lane);
         }
     }
     if constexpr (LORA) lora_flush(kacc, 1);
@@ -754,10 +765,22 @@ extern "C" int bsclip_attn_fwd2(const void* qkv, int ld_qkv, int B, int S, int h
 // A/B switch of the round-5 "row constant as the initial accumulator" form of the no-dropout key-owner phase (default on)
 static const bool g_attn_preload = !(getenv("BSCLIP_ATTN_PRELOAD") && atoi(getenv("BSCLIP_ATTN_PRELOAD")) == 0);
 
+// fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the ViT's forms -- S = 197, no dropout, no keep bits (rejected on the host); the key-owner
+// phase with the preloaded delta, with or without the LoRA partial products
+#define ATTN_BWD16_LAUNCH(PR, LR)                                                                                \
+    hipLaunchKernelGGL((attn_bwd_kernel<7, false, false, 32, false, PR, LR, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
+                       static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_ctx, lse, S, heads, \
+                       key_bias, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, nqb, static_cast<unsigned long long*>(nullptr), \
+                       static_cast<const unsigned*>(nullptr), lp)
+
 static int attn_bwd_launch(const void* qkv, int ld_qkv, const void* dctx, int ld_ctx, const float* lse, int B, int S, int heads,
                            const float* key_bias, float scale, void* dqkv, int ld_dqkv, int q_rows, const void* keep_bits,
                            float dropout_p, uint32_t dropout_seed, LoraPart lp, void* stream) {
     BSCLIP_REQUIRE(qkv && dctx && lse && dqkv, "bsclip_attn_bwd: null pointer");
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(q_rows, f16), "bsclip_attn_bwd: unknown bits in q_rows=0x%x", q_rows);
+    BSCLIP_REQUIRE(!f16 || (dropout_p == 0.f && !keep_bits), "bsclip_attn_bwd: fp16 operands take no dropout / keep_bits");
+    BSCLIP_REQUIRE(!f16 || S == 197, "bsclip_attn_bwd: fp16 operands are built for S = 197 (the ViT), not S=%d", S);
     BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(keep_bits) & 15) == 0, "bsclip_attn_bwd: keep_bits must be 16-byte aligned");
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= 224, "bsclip_attn_bwd: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 8 == 0 && ld_dqkv >= 3 * heads * 64 && ld_dqkv % 4 == 0 &&
@@ -770,7 +793,11 @@ static int attn_bwd_launch(const void* qkv, int ld_qkv, const void* dctx, int ld
     BSCLIP_REQUIRE(!lp.dtp || !drop.thr16 || keep_bits, "bsclip_attn_bwd_lora: with dropout the forward's keep_bits are required");
     hipStream_t s = static_cast<hipStream_t>(stream);
     // S = 133 gains 5 % from the trimmed last tile; at S = 197 the trimmed instantiation schedules worse (268.6 vs 265.0 us)
-    if (S == 133) {
+    if (f16) {
+        if (lp.dtp) ATTN_BWD16_LAUNCH(true, true);
+        else if (g_attn_preload) ATTN_BWD16_LAUNCH(true, false);
+        else ATTN_BWD16_LAUNCH(false, false);
+    } else if (S == 133) {
         ATTN_BWD_PICK(5, 5);
     } else {
         switch ((S + 31) / 32) {

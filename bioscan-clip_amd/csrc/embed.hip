@@ -176,6 +176,24 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restr
     }
 }
 
+// out = fp16(in * 2^k) (bsclip_cast_f32_f16_scaled: the static gradient scale of an fp16-operand backward): the product is exact in f32
+// (a power of two, no f32 overflow for |k| <= 64 on gradients), so the one rounding is the RNE f32 -> fp16 conversion
+__global__ __launch_bounds__(256) void cast_f32_f16_scaled_kernel(const float* __restrict__ in, long n, float scale,
+                                                                   bf16_t* __restrict__ out) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(in + 4 * i) * scale;
+        uint2 o;
+        o.x = pack_h2<true>(v[0], v[1]);
+        o.y = pack_h2<true>(v[2], v[3]);
+        *reinterpret_cast<uint2*>(out + 4 * i) = o;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        out[i] = f2h<true>(in[i] * scale);
+    }
+}
+
 // W_aug rows [0,H): cols [H,H+4) = B_q[n,:]; rows [2H,3H): cols [H+4,H+8) = B_v[n,:]
 // for every LoRA layer of an encoder in one launch (blockIdx.y = layer): table[l] = {W_aug, B_q, B_v} device addresses; fp16 when F16
 template <bool F16 = false>
@@ -316,6 +334,21 @@ extern "C" int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* 
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                        (long)n, static_cast<bf16_t*>(out));
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// bsclip_cast_f32_f16 of in * 2^scale_log2 (the head's f32 dL/dz -> the 16-bit dout of an fp16-operand backward)
+extern "C" int bsclip_cast_f32_f16_scaled(const float* in, int64_t n, int scale_log2, void* out, void* stream) {
+    BSCLIP_REQUIRE(in && out && n > 0, "bsclip_cast_f32_f16_scaled: bad args");
+    BSCLIP_REQUIRE(scale_log2 >= -64 && scale_log2 <= 64, "bsclip_cast_f32_f16_scaled: scale_log2=%d (|k| <= 64)", scale_log2);
+    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+                   "bsclip_cast_f32_f16_scaled: in and out must be 16-byte aligned");
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(cast_f32_f16_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
+                       ldexpf(1.f, scale_log2), static_cast<bf16_t*>(out));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

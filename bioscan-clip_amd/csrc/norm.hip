@@ -186,7 +186,10 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_fwd_kernel(const void* __r
     }
 }
 
-template <int H, bool X_BF16, bool LORA>
+// F16 (bsclip_layernorm_bwd with x_bf16 | BSCLIP_OPERANDS_FP16): x, the 16-bit residual-gradient stream (g_resid, dx_res) and the
+// 16-bit GEMM gradient / operand output are IEEE fp16; the operand output is the RNE rounding of its f32 value.  No dropout, no f32 or
+// split operand forms (rejected on the host).
+template <int H, bool X_BF16, bool LORA, bool F16 = false>
 __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __restrict__ x, int ld_x,
                                                                   const float* __restrict__ stats,
                                                                   const float* __restrict__ gamma, int M,
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
     for (int row = wave; row < M; row += nwaves) {
         if constexpr (LORA) asm volatile("" ::: "memory");   // sA is loop-invariant: keep its 24 reads out of the registers
         f32x4 v[NV], dy[NV], res[NV];
-        load_row<H, X_BF16>(x, ld_x, row, lane, v);
+        load_row<H, X_BF16, F16>(x, ld_x, row, lane, v);
         const float mean = stats[2 * (size_t)row], rstd = stats[2 * (size_t)row + 1];
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
 #pragma unroll
                 for (int j = 0; j < NV; ++j) {
                     const uint2 u = ld_stream(reinterpret_cast<const uint2*>(p + j * 256 + lane * 4));
-                    res[j] = f32x4{bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16)};
+                    res[j] = f32x4{h2f<F16>(u.x & 0xffff), h2f<F16>(u.x >> 16), h2f<F16>(u.y & 0xffff), h2f<F16>(u.y >> 16)};
                 }
             } else {
 #pragma unroll
@@ -253,7 +256,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 const uint2 u = ld_stream(reinterpret_cast<const uint2*>(p + j * 256 + lane * 4));
-                dy[j] = f32x4{bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16)};
+                dy[j] = f32x4{h2f<F16>(u.x & 0xffff), h2f<F16>(u.x >> 16), h2f<F16>(u.y & 0xffff), h2f<F16>(u.y >> 16)};
             }
         }
         if constexpr (LORA) {
@@ -292,8 +295,8 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
             if (dx_res) {
                 if (dr_bf16) {
                     uint2 o;
-                    o.x = pack_bf2(d[0], d[1]);
-                    o.y = pack_bf2(d[2], d[3]);
+                    o.x = pack_h2<F16>(d[0], d[1]);
+                    o.y = pack_h2<F16>(d[2], d[3]);
                     st_stream(static_cast<bf16_t*>(dx_res) + (size_t)row * ld_dx + j * 256 + lane * 4, o);
                 } else {
                     st_stream(static_cast<float*>(dx_res) + (size_t)row * ld_dx + j * 256 + lane * 4, d);
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
             if (dx_bf16) {
                 // gradient w.r.t. the output of the Linear whose forward result was dropped with this (p, seed)
                 if (drop.thr16) d = drop4(drop, (unsigned)row * H + j * 256 + lane * 4, d);
-                if (op_s3) {
+                if (!F16 && op_s3) {
                     bf16_t* r3 = static_cast<bf16_t*>(dx_bf16) + (size_t)row * ld_dxb + j * 256 + lane * 4;
                     uint2 hi, lo;
                     hi.x = pack_bf2(d[0], d[1]);
@@ -314,13 +317,13 @@ __global__ __launch_bounds__(LN_BLOCK) void layernorm_bwd_kernel(const void* __r
                     st_stream(r3 + 2 * H, hi);
                     continue;
                 }
-                if (op_f32) {
+                if (!F16 && op_f32) {
                     st_stream(static_cast<float*>(dx_bf16) + (size_t)row * ld_dxb + j * 256 + lane * 4, d);
                     continue;
                 }
                 uint2 o;
-                o.x = pack_bf2(d[0], d[1]);
-                o.y = pack_bf2(d[2], d[3]);
+                o.x = pack_h2<F16>(d[0], d[1]);
+                o.y = pack_h2<F16>(d[2], d[3]);
                 st_stream(static_cast<bf16_t*>(dx_bf16) + (size_t)row * ld_dxb + j * 256 + lane * 4, o);
             }
         }
@@ -461,6 +464,10 @@ extern "C" int bsclip_layernorm_fwd_fp8(const void* x, int ld_x, int x_bf16, int
     hipLaunchKernelGGL((layernorm_bwd_kernel<HH, XB, LO>), dim3(ln_grid(M, LO ? 4 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, stats, \
                        gamma, M, g_resid, ld_gr, g_gemm, ld_g, dt, lora_a, mode, dx_f32, \
                        ld_dx, dx_bf16, ld_dxb, drop, in_drop, resid_flags)
+#define LN_BWD16_LAUNCH(LO)                                                                                      \
+    hipLaunchKernelGGL((layernorm_bwd_kernel<768, true, LO, true>), dim3(ln_grid(M, LO ? 4 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, \
+                       stats, gamma, M, g_resid, ld_gr, g_gemm, ld_g, dt, lora_a, mode, dx_f32, ld_dx, dx_bf16, ld_dxb, drop, in_drop, \
+                       resid_flags)
 
 extern "C" int bsclip_layernorm_bwd(const void* x, int ld_x, int x_bf16, const float* stats, const float* gamma, int M,
                                     int H, const void* g_resid, int ld_gr, const void* g_gemm, int ld_g,
@@ -468,6 +475,14 @@ extern "C" int bsclip_layernorm_bwd(const void* x, int ld_x, int x_bf16, const f
                                     void* dx_bf16, int ld_dxb, float dropout_p, uint32_t dropout_seed, float in_dropout_p,
                                     uint32_t in_dropout_seed, int resid_flags, void* stream) {
     BSCLIP_REQUIRE(x && stats && gamma && M > 0, "bsclip_layernorm_bwd: null/empty input");
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(x_bf16, f16), "bsclip_layernorm_bwd: unknown bits in x_bf16=0x%x", x_bf16);
+    BSCLIP_REQUIRE(!f16 || (dropout_p == 0.f && in_dropout_p == 0.f),
+                   "bsclip_layernorm_bwd: fp16 operands take no dropout (the ViT's backward only)");
+    BSCLIP_REQUIRE(!f16 || (H == 768 && x_bf16 == 1 && (resid_flags & ~3) == 0 && (!dx_f32 || (resid_flags & 2)) &&
+                            (!g_resid || (resid_flags & 1))),
+                   "bsclip_layernorm_bwd: fp16 operands: H = 768, 16-bit x, g_resid and dx_f32 on the 16-bit stream, 16-bit g_gemm and "
+                   "operand output (H=%d x_bf16=%d resid_flags=%d)", H, x_bf16, resid_flags);
     BSCLIP_REQUIRE(H == 768 || H == 512, "bsclip_layernorm_bwd: H=%d (supported: 768, 512)", H);
     BSCLIP_REQUIRE(g_resid || g_gemm, "bsclip_layernorm_bwd: no incoming gradient");
     BSCLIP_REQUIRE(mode == 0 || mode == 1, "bsclip_layernorm_bwd: mode=%d", mode);
@@ -483,7 +498,10 @@ extern "C" int bsclip_layernorm_bwd(const void* x, int ld_x, int x_bf16, const f
     const DropCfg in_drop = make_drop(in_dropout_p, in_dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lo = lora_a != nullptr;
-    if (H == 768) {
+    if (f16) {
+        if (lo) LN_BWD16_LAUNCH(true);
+        else LN_BWD16_LAUNCH(false);
+    } else if (H == 768) {
         if (x_bf16) { if (lo) LN_BWD_LAUNCH(768, true, true); else LN_BWD_LAUNCH(768, true, false); }
         else        { if (lo) LN_BWD_LAUNCH(768, false, true); else LN_BWD_LAUNCH(768, false, false); }
     } else {

@@ -196,8 +196,8 @@ __global__ __launch_bounds__(LG_BLOCK) void lora_grad_dt_db_kernel(const void* _
         partial[(size_t)blockIdx.x * (2 * NV * 16 * 64) + idx] = red[idx];
 }
 
-// pass 2: dA[8,H] += dt^T y.  Y_FP8: y is the fp8 e4m3 LN output (row stride ld_h bytes) instead of bf16.
-template <int H, bool Y_FP8 = false, bool Y_F32 = false>
+// pass 2: dA[8,H] += dt^T y.  Y_FP8: y is the fp8 e4m3 LN output (row stride ld_h bytes) instead of bf16; F16: y is IEEE fp16.
+template <int H, bool Y_FP8 = false, bool Y_F32 = false, bool F16 = false>
 __global__ __launch_bounds__(LG_BLOCK) void lora_grad_da_kernel(const void* __restrict__ haug_, int ld_h, int M,
                                                                  const float* __restrict__ dt,
                                                                  float* __restrict__ partial) {
@@ -247,7 +247,8 @@ __global__ __launch_bounds__(LG_BLOCK) void lora_grad_da_kernel(const void* __re
                 else if constexpr (Y_FP8)
                     y = f32x4{fp8_to_f32(yr[p][j].x, 0), fp8_to_f32(yr[p][j].x, 1), fp8_to_f32(yr[p][j].x, 2), fp8_to_f32(yr[p][j].x, 3)};
                 else
-                    y = f32x4{bf2f(yr[p][j].x & 0xffff), bf2f(yr[p][j].x >> 16), bf2f(yr[p][j].y & 0xffff), bf2f(yr[p][j].y >> 16)};
+                    y = f32x4{h2f<F16>(yr[p][j].x & 0xffff), h2f<F16>(yr[p][j].x >> 16), h2f<F16>(yr[p][j].y & 0xffff),
+                              h2f<F16>(yr[p][j].y >> 16)};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     acc[r][j] += splat4(d0[p][r]) * y;
@@ -313,11 +314,13 @@ __global__ __launch_bounds__(LG_BLOCK) void lora_t_f32_kernel(const float* __res
 // over 8 groups of 96 slabs took 13 us for the step's 19 MB of dA slabs.)
 // first_block = SLAB / 32 with a grid of SLAB / 32 workgroups sums the dA slabs only (bsclip_lora_grad_heads: dB comes from the
 // attention kernel's partials).
-template <int H>
+// UNSCALE (fp16-operand backward, bsclip_lora_grad_heads_f16): the slabs hold 2^s times the gradient; each sum is multiplied by
+// unscale = 2^-s (exact) before it is added to the gradient.
+template <int H, bool UNSCALE = false>
 __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __restrict__ pa,
                                                                 const float* __restrict__ pb, int nblocks,
                                                                 float* __restrict__ dA, float* __restrict__ dBq,
-                                                                float* __restrict__ dBv, int first_block = 0) {
+                                                                float* __restrict__ dBv, int first_block = 0, float unscale = 1.f) {
     constexpr int NV = H / 256;
     constexpr int SLAB = 8 * H;
     __shared__ f32x4 red[32][8];
@@ -342,6 +345,7 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
     s = red[0][q];
 #pragma unroll
     for (int g = 1; g < 32; ++g) s += red[g][q];
+    if constexpr (UNSCALE) s *= unscale;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int ec = e + c;
@@ -364,9 +368,11 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
 //   workgroups [0, nA):  dt[row][4 half : 4 half + 4] = sum_head dt_partial[head][half][row][0:4]   (thread = (row, half); 12 loads in flight)
 //   the rest:            dB[q | v][head * 64 + d][j] += sum_item db_partial[item][q | v][j][d]   (as lora_grad_reduce_kernel: 32
 //                        consecutive elements x 8 item groups per workgroup, combined in group order through LDS)
+// UNSCALE: as lora_grad_reduce_kernel's, on the dB sums (dt stays in the scaled units of the gradient stream it feeds)
+template <bool UNSCALE = false>
 __global__ __launch_bounds__(256) void lora_heads_reduce_kernel(const float* __restrict__ dtp, const float* __restrict__ dbp, int M,
                                                                  int heads, int items, int nA, float* __restrict__ dt,
-                                                                 float* __restrict__ dBq, float* __restrict__ dBv) {
+                                                                 float* __restrict__ dBq, float* __restrict__ dBv, float unscale = 1.f) {
     if ((int)blockIdx.x < nA) {
         const int g = blockIdx.x * 256 + threadIdx.x, row = g >> 1, half = g & 1;
         if (row >= M) return;
@@ -400,6 +406,7 @@ __global__ __launch_bounds__(256) void lora_heads_reduce_kernel(const float* __r
     __syncthreads();
     if (p != 0) return;
     s = ((red[0][i] + red[1][i]) + (red[2][i] + red[3][i])) + ((red[4][i] + red[5][i]) + (red[6][i] + red[7][i]));
+    if constexpr (UNSCALE) s *= unscale;
     const int hd = e >> 9, is_v = (e >> 8) & 1, j = (e >> 6) & 3, d = e & 63;
     float* dst = (is_v ? dBv : dBq) + (size_t)(hd * 64 + d) * 4 + j;
     *dst += s;
@@ -590,7 +597,7 @@ extern "C" int bsclip_lora_grad_heads(const void* h, int ld_h, int M, int H, int
     const bf16_t* hh = static_cast<const bf16_t*>(h);
     float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
     const int nA = ceil_div(2 * M, 256);
-    hipLaunchKernelGGL(lora_heads_reduce_kernel, dim3(nA + heads * 512 / 32), dim3(256), 0, s, dt_partial, db_partial, M, heads, B, nA,
+    hipLaunchKernelGGL(lora_heads_reduce_kernel<false>, dim3(nA + heads * 512 / 32), dim3(256), 0, s, dt_partial, db_partial, M, heads, B, nA,
                        dt, dBq, dBv);
     if (H == 768) {
         hipLaunchKernelGGL((lora_grad_da_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
@@ -601,6 +608,71 @@ extern "C" int bsclip_lora_grad_heads(const void* h, int ld_h, int M, int H, int
         hipLaunchKernelGGL((lora_grad_reduce_kernel<512>), dim3(8 * 512 / 32), dim3(256), 0, s, (const float*)nullptr, pb, blocks, dA,
                            dBq, dBv, 8 * 512 / 32);
     }
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// bsclip_lora_grad_heads on fp16 operands with the static gradient scale 2^s of the fp16 backward: operands = BSCLIP_OPERANDS_FP16 | s
+// (s in the low byte, <= 64).  h (LN output) is fp16; the partials, dt and the dA slabs hold 2^s times the gradient; dt is left scaled
+// (the LayerNorm backward's dt.A term adds it to the scaled gradient stream), dA / dBq / dBv receive the sums times 2^-s (exact in f32).
+extern "C" int bsclip_lora_grad_heads_f16(const void* h, int ld_h, int M, int H, int B, const float* dt_partial,
+                                          const float* db_partial, float* dt, float* dA, float* dBq, float* dBv, float* workspace,
+                                          int operands, void* stream) {
+    bool f16 = false;
+    BSCLIP_REQUIRE(take_operands_flag(operands, f16), "bsclip_lora_grad_heads_f16: unknown bits in operands=0x%x", operands);
+    BSCLIP_REQUIRE(f16 && operands <= 64, "bsclip_lora_grad_heads_f16: operands=0x%x must be BSCLIP_OPERANDS_FP16 | s, s <= 64",
+                   operands);
+    BSCLIP_REQUIRE(h && dt_partial && db_partial && dt && dA && dBq && dBv && workspace && M > 0 && B > 0 && M % B == 0,
+                   "bsclip_lora_grad_heads_f16: null/empty input (M=%d B=%d)", M, B);
+    BSCLIP_REQUIRE(H == 768, "bsclip_lora_grad_heads_f16: H=%d (the ViT's 768)", H);
+    BSCLIP_REQUIRE(ld_h >= H && ld_h % 8 == 0, "bsclip_lora_grad_heads_f16: ld_h=%d", ld_h);
+    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(dt_partial) | reinterpret_cast<uintptr_t>(dt) | reinterpret_cast<uintptr_t>(workspace) |
+                     reinterpret_cast<uintptr_t>(h)) & 15) == 0,
+                   "bsclip_lora_grad_heads_f16: h, dt_partial, dt and workspace must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float unscale = ldexpf(1.f, -operands);
+    const int heads = H / 64;
+    int blocks = ceil_div(M, 4 * 8);
+    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    const bf16_t* hh = static_cast<const bf16_t*>(h);
+    float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
+    const int nA = ceil_div(2 * M, 256);
+    hipLaunchKernelGGL(lora_heads_reduce_kernel<true>, dim3(nA + heads * 512 / 32), dim3(256), 0, s, dt_partial, db_partial, M, heads, B,
+                       nA, dt, dBq, dBv, unscale);
+    hipLaunchKernelGGL((lora_grad_da_kernel<768, false, false, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
+    hipLaunchKernelGGL((lora_grad_reduce_kernel<768, true>), dim3(8 * 768 / 32), dim3(256), 0, s, (const float*)nullptr, pb, blocks, dA,
+                       dBq, dBv, 8 * 768 / 32, unscale);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// out[i] += 2^scale_log2 * in[i] (f32, 16-byte aligned): a weight gradient of the fp16-operand backward, formed in the 2^s units of its
+// scaled operands, enters the gradient buffer at its true size (the multiply by a power of two is exact)
+__global__ __launch_bounds__(256) void add_scaled_f32_kernel(const float* __restrict__ in, long n, float scale, float* __restrict__ out) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(in + 4 * i);
+        f32x4 o = *reinterpret_cast<const f32x4*>(out + 4 * i);
+        o += v * scale;
+        *reinterpret_cast<f32x4*>(out + 4 * i) = o;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        out[i] += in[i] * scale;
+    }
+}
+
+extern "C" int bsclip_add_scaled_f32(const float* in, int64_t n, int scale_log2, float* out, void* stream) {
+    BSCLIP_REQUIRE(in && out && n > 0, "bsclip_add_scaled_f32: bad args");
+    BSCLIP_REQUIRE(scale_log2 >= -64 && scale_log2 <= 64, "bsclip_add_scaled_f32: scale_log2=%d (|k| <= 64)", scale_log2);
+    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+                   "bsclip_add_scaled_f32: in and out must be 16-byte aligned");
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(add_scaled_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
+                       ldexpf(1.f, scale_log2), out);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

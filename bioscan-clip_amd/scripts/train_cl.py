@@ -108,7 +108,27 @@ def build_scheduler(args, optimizer, total_steps):
     return None
 
 
+def fp16_towers(args):
+    """``hip_fp16_towers=image``: the towers that train on fp16 operands (set_operand_format(..., towers=...)); default empty = bf16
+    everywhere.  Only the image tower has an fp16 backward: naming dna or language is refused here, before any GPU work."""
+    raw = getattr(args, "hip_fp16_towers", None)
+    if raw is None or raw == "":
+        return ()
+    items = [str(t).strip() for t in (raw.split(",") if isinstance(raw, str) else raw)]
+    towers = tuple(t for t in items if t)
+    from bioscanclip.hip.engine import OPERAND_TOWERS
+    bad = [t for t in towers if t not in OPERAND_TOWERS]
+    if bad:
+        raise ValueError(f"hip_fp16_towers: unknown tower(s) {bad}; choose from {tuple(OPERAND_TOWERS)}")
+    no_bwd = [t for t in towers if t != "image"]
+    if no_bwd:
+        raise ValueError(f"hip_fp16_towers: {', '.join(no_bwd)} cannot train on fp16 operands -- the fp16 backward of the BarcodeBERT / "
+                         "text towers is not built (their dropout forms); only 'image' is available")
+    return towers
+
+
 def main_process(rank: int, world_size: int, args):
+    towers16 = fp16_towers(args)
     if getattr(args, "debug_flag", False) or rank != 0:
         args.activate_wandb = False
         args.save_inference = False
@@ -144,6 +164,9 @@ def main_process(rank: int, world_size: int, args):
         args.allow_random_init = True
     model = load_clip_model(args)
     model = model.to(device)
+    if towers16:
+        from bioscanclip.hip.engine import set_operand_format
+        set_operand_format(model, "fp16", towers=towers16)   # the image tower's forward and backward on fp16 operands
 
     total_steps = len(pre_train_dataloader) * mc.epochs
     lr = 0.001
@@ -213,6 +236,7 @@ def main(argv=None):
     args = load_config(config_dir, argv)
     if "model_config" not in args:
         raise SystemExit("usage: train_cl.py 'model_config=<name>' [key=value ...]")
+    fp16_towers(args)   # refuse an unbuilt fp16 backward before any GPU work
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     print_when_rank_zero(f'world_size: {world_size}', rank)

@@ -85,7 +85,20 @@ enum bsclip_epilogue {
  *   bsclip_vit_cls_rows    x_bf16     the cls rows of an fp16 residual stream (x_bf16 must be set)
  *   bsclip_waug_set_lora_layers  layers  fp16 LoRA-B columns (the layer count must then be < 256)
  *   bsclip_count_nonfinite is_bf16    1 | BSCLIP_OPERANDS_FP16: the 16-bit elements are fp16
- * and bsclip_cast_f32_f16 is the fp16 form of bsclip_cast_f32_bf16 (its only integer argument is the 64-bit count). */
+ * and bsclip_cast_f32_f16 is the fp16 form of bsclip_cast_f32_bf16 (its only integer argument is the 64-bit count).
+ * The backward of the LoRA ViT on fp16 operands (training; no dropout anywhere, so the flag is rejected together with dropout or keep
+ * bits) carries the same flag:
+ *   bsclip_attn_bwd        q_rows     qkv, dctx, dqkv fp16; S, dP, dQ, dK, dV on v_mfma_f32_32x32x16_f16, P and dS rounded to fp16;
+ *                                     lse, delta, softmax f32.  S = 197 only.
+ *   bsclip_attn_bwd_lora   q_rows     the same, t_aug fp16; the dt / dB partials stay f32 up to accumulation order (B enters as hi + lo
+ *                                     fp16 parts of 2^8 B, the 2^8 is taken off the f32 dt sums)
+ *   bsclip_layernorm_bwd   x_bf16     x, g_resid / dx_f32 (resid_flags bits 0 / 1 required when given), g_gemm and dx_bf16 fp16;
+ *                                     dx_bf16 = RNE of its f32 value.  H = 768, 16-bit x, resid_flags bits 2-4 rejected.
+ *   bsclip_lora_grad_heads_f16  operands  BSCLIP_OPERANDS_FP16 | s (s <= 64 in the low byte, the flag is required): h fp16, the
+ *                                     partials and dt in 2^s units; dA / dBq / dBv += 2^-s x the sums (exact)
+ * Gradient scale of that backward: one static power of two 2^s per tower, put on where the head's f32 dL/dz becomes the fp16 dout
+ * (bsclip_cast_f32_f16_scaled) and taken off, exactly, before each trainable gradient is added (bsclip_lora_grad_heads_f16,
+ * bsclip_add_scaled_f32 for the head's dW); the bias gradient is summed from the unscaled f32 dL/dz. */
 typedef struct bsclip_epi_args {
     uint32_t struct_size; /* = sizeof(bsclip_epi_args) = bsclip_epi_args_size(); a mismatch is rejected (ABI drift guard) */
     const float* bias;    /* [N] or NULL */
@@ -253,7 +266,8 @@ int bsclip_attn_bwd(const void* qkv, int ld_qkv, const void* dctx, int ld_ctx, c
  *   db_partial f32 [B*heads, 2, 4, 64]:   [b*heads+h][q|v][j][d] = sum over the tokens of sequence b of t[m][j (+4 for v)] * dq|dv[m][64 h + d]
  * t_aug: bf16 [B*S, ld_t], t = y A^T in columns 0..7 (the LayerNorm's block of the QKV operand), 16-byte aligned, ld_t % 8 == 0;
  * lora_b f32 [2, heads*64, 4] as bsclip_lora_grad.  With dropout the forward's keep_bits are required.  The products run on the matrix
- * pipe with B as hi + lo bf16 parts: f32 results up to accumulation order.  bsclip_lora_grad_heads reduces the partials. */
+ * pipe with B as hi + lo bf16 parts: f32 results up to accumulation order.  bsclip_lora_grad_heads reduces the partials.
+ * q_rows | BSCLIP_OPERANDS_FP16 (both backward entry points): fp16 operands, S = 197, no dropout -- see BSCLIP_OPERANDS_FP16. */
 int bsclip_attn_bwd_lora(const void* qkv, int ld_qkv, const void* dctx, int ld_ctx, const float* lse, int B, int S, int heads,
                          const float* key_bias, float scale, void* dqkv, int ld_dqkv, int q_rows, const void* keep_bits,
                          const void* t_aug, int ld_t, const float* lora_b, float* dt_partial, float* db_partial, float dropout_p,
@@ -428,6 +442,12 @@ int bsclip_lora_grad(const void* dqkv, int ld_dqkv, const void* h, int ld_h, int
  * summation order (bitwise reproducible). */
 int bsclip_lora_grad_heads(const void* h, int ld_h, int M, int H, int B, const float* dt_partial, const float* db_partial, float* dt,
                            float* dA, float* dBq, float* dBv, float* workspace, void* stream);
+/* the same on fp16 operands with the static gradient scale 2^s (operands = BSCLIP_OPERANDS_FP16 | s; see BSCLIP_OPERANDS_FP16): h fp16
+ * [M, ld_h], H = 768; dt stays in 2^s units, dA / dBq / dBv receive the true gradient.  h, dt_partial, dt, workspace 16-byte aligned. */
+int bsclip_lora_grad_heads_f16(const void* h, int ld_h, int M, int H, int B, const float* dt_partial, const float* db_partial,
+                               float* dt, float* dA, float* dBq, float* dBv, float* workspace, int operands, void* stream);
+/* out[i] += 2^scale_log2 in[i], f32, |scale_log2| <= 64, 16-byte aligned (exact: a weight gradient formed from 2^s-scaled operands) */
+int bsclip_add_scaled_f32(const float* in, int64_t n, int scale_log2, float* out, void* stream);
 /* lora_grad with the fp8 operand layout: y_fp8 [M, ld_y bytes] (LN output, e4m3) and t_aug bf16 [M, ld_t] (t in cols [0,8)) */
 int bsclip_lora_grad_fp8(const void* dqkv, int ld_dqkv, const void* y_fp8, int ld_y, const void* t_aug, int ld_t, int M,
                          int H, const float* lora_b, float* dt, float* dA, float* dBq, float* dBv, float* workspace,
@@ -443,6 +463,8 @@ int bsclip_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* 
 int bsclip_cast_f32_bf16(const float* in, int64_t n, void* out, void* stream);
 /* out fp16 [n] = in f32 [n]: round to nearest even, subnormals kept, overflow to +-inf (the head weight of an fp16-operand forward) */
 int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* stream);
+/* out fp16 [n] = RNE(in [n] * 2^scale_log2), |scale_log2| <= 64, 16-byte aligned: the scaled dout of an fp16-operand backward */
+int bsclip_cast_f32_f16_scaled(const float* in, int64_t n, int scale_log2, void* out, void* stream);
 /* W_aug[3H, H+KPAD] bf16: cols [H,H+4) of rows [0,H) = B_q, cols [H+4,H+8) of rows [2H,3H) = B_v (refreshed
  * every step from the f32 masters; the frozen [3H,H] block is written once at pack time).
  * One launch for every LoRA layer of an encoder: table_dev[l] = {W_aug, B_q, B_v} as three 64-bit device addresses (the buffers live
