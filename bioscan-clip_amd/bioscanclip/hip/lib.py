@@ -86,6 +86,12 @@ SIGNATURES = {
     "bsclip_infonce_fwd_bwd": (I, [POINTER(c_void_p), I, P, I, I, F, I, I, P, POINTER(c_void_p), P, P]),
     "bsclip_topk_ip_workspace_floats": (L, [I, I, I]),
     "bsclip_topk_ip": (I, [P, I, P, I, I, I, P, P, P, P]),
+    "bsclip_retrieval_index_floats": (L, [I, I]),
+    "bsclip_retrieval_index_build": (I, [P, I, I, P, P]),
+    "bsclip_topk_ip_indexed_workspace_floats": (L, [I, I, I]),
+    "bsclip_topk_ip_indexed": (I, [P, I, P, I, I, I, P, P, P, P]),
+    "bsclip_retrieval_hit_ranks": (I, [P, I, I, P, I, P, I, P, P, P]),
+    "bsclip_retrieval_class_counts": (I, [P, P, I, I, P, P, I, P, P, P, P]),
     "bsclip_comm_unique_id_bytes": (I, []),
     "bsclip_comm_unique_id": (I, [P]),
     "bsclip_comm_init": (I, [POINTER(c_void_p), P, I, I]),

@@ -629,6 +629,97 @@ def topk_ip(queries, keys, k):
     return scores, idx
 
 
+I32 = torch.int32
+
+
+def retrieval_index_build(keys):
+    """The key operand of ``topk_ip`` built once (faiss ``index.add``): returns the f32-typed buffer ``topk_ip_indexed`` searches."""
+    _req(keys.dim() == 2 and keys.dtype == F32 and keys.is_contiguous() and keys.is_cuda, "retrieval_index_build: contiguous f32 GPU [K,D]")
+    K, D = keys.shape
+    _req(K >= 1 and D % 64 == 0, "retrieval_index_build: K >= 1, D % 64 == 0")
+    index = torch.empty(_l.load().bsclip_retrieval_index_floats(K, D), dtype=F32, device=keys.device)
+    check(_l.load().bsclip_retrieval_index_build(_p(keys), K, D, _p(index), _stream()))
+    return index
+
+
+def topk_ip_indexed(queries, index, K, k):
+    """``topk_ip`` against a prebuilt index of K keys (``retrieval_index_build``): same kernels, bit-identical outputs."""
+    _req(queries.dim() == 2 and queries.dtype == F32 and queries.is_contiguous() and queries.is_cuda,
+         "topk_ip_indexed: contiguous f32 GPU [Q,D]")
+    Q, D = queries.shape
+    _req(Q >= 1 and 1 <= k <= min(16, K) and D % 64 == 0, "topk_ip_indexed: Q >= 1, 1 <= k <= 16, k <= K, D % 64 == 0")
+    _req(index.dtype == F32 and index.is_contiguous() and index.device == queries.device
+         and index.numel() == _l.load().bsclip_retrieval_index_floats(K, D), "topk_ip_indexed: index is not that of [K,D] keys")
+    ws = torch.empty(_l.load().bsclip_topk_ip_indexed_workspace_floats(Q, K, D), dtype=F32, device=queries.device)
+    scores = torch.empty(Q, k, dtype=F32, device=queries.device)
+    idx = torch.empty(Q, k, dtype=torch.int64, device=queries.device)
+    check(_l.load().bsclip_topk_ip_indexed(_p(queries), Q, _p(index), K, D, k, _p(scores), _p(idx), _p(ws), _stream()))
+    return scores, idx
+
+
+def _eval_flag(flag, device):
+    if flag is None:
+        return torch.zeros(1, dtype=I32, device=device), True
+    _req(flag.dtype == I32 and flag.numel() == 1 and flag.device == device, "flag: int32 [1] on the same GPU")
+    return flag, False
+
+
+def check_retrieval_flag(word):
+    """Raise for the error bits the scoring kernels OR into their flag word (``word``: its value on the host)."""
+    if word & 1:
+        raise ValueError("retrieval_hit_ranks: an idx entry lies outside [0, K)")
+    if word & 2:
+        raise ValueError("retrieval_class_counts: a query label lies outside its level's class range")
+
+
+def retrieval_hit_ranks(idx, key_labels, query_labels, flag=None):
+    """hit_rank int32 [Q,L]: the first rank r < k with key_labels[idx[q,r], l] == query_labels[q,l], or k.  Without ``flag`` the
+    error word is read back here and a bad idx raises; with a caller's ``flag`` (int32 [1], cleared by the caller) nothing
+    synchronises and the caller runs ``check_retrieval_flag`` on it."""
+    _req(idx.dim() == 2 and idx.dtype == torch.int64 and idx.is_contiguous() and idx.is_cuda, "retrieval_hit_ranks: idx int64 GPU [Q,k]")
+    Q, k = idx.shape
+    dev = idx.device
+    _req(key_labels.dim() == 2 and query_labels.dim() == 2 and key_labels.dtype == I32 and query_labels.dtype == I32
+         and key_labels.is_contiguous() and query_labels.is_contiguous() and key_labels.device == dev and query_labels.device == dev,
+         "retrieval_hit_ranks: labels int32 contiguous [K,L], [Q,L] on idx's GPU")
+    K, L = key_labels.shape
+    _req(Q >= 1 and K >= 1 and 1 <= k <= 16 and 1 <= L <= 8 and tuple(query_labels.shape) == (Q, L),
+         "retrieval_hit_ranks: 1 <= k <= 16, 1 <= L <= 8, query_labels [Q,L]")
+    flag, own = _eval_flag(flag, dev)
+    hit_rank = torch.empty(Q, L, dtype=I32, device=dev)
+    check(_l.load().bsclip_retrieval_hit_ranks(_p(idx), Q, k, _p(key_labels), K, _p(query_labels), L, _p(hit_rank), _p(flag), _stream()))
+    if own:
+        check_retrieval_flag(int(flag.item()))
+    return hit_rank
+
+
+def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=None, out=None):
+    """(seen int32 [C], right int32 [nk,C]) with C = level_offsets[-1]: queries per class and those hit within k_list[j].
+    ``level_offsets`` / ``k_list`` are host sequences.  ``out``: an int32 buffer of (1 + nk) * C elements to hold both."""
+    _req(hit_rank.dim() == 2 and hit_rank.dtype == I32 and hit_rank.is_contiguous() and hit_rank.is_cuda
+         and query_labels.dtype == I32 and query_labels.is_contiguous() and query_labels.shape == hit_rank.shape
+         and query_labels.device == hit_rank.device, "retrieval_class_counts: hit_rank, query_labels int32 GPU [Q,L]")
+    Q, L = hit_rank.shape
+    offs, ks = [int(o) for o in level_offsets], [int(k) for k in k_list]
+    nk = len(ks)
+    _req(Q >= 1 and 1 <= L <= 8 and len(offs) == L + 1 and 1 <= nk <= 8, "retrieval_class_counts: L <= 8 levels, L + 1 offsets, nk <= 8")
+    _req(offs[0] == 0 and all(a <= b for a, b in zip(offs, offs[1:])) and offs[-1] >= 1 and min(ks) >= 1,
+         "retrieval_class_counts: offsets start at 0 and do not decrease, k >= 1")
+    C = offs[-1]
+    dev = hit_rank.device
+    flag, own = _eval_flag(flag, dev)
+    if out is None:
+        out = torch.empty((1 + nk) * C, dtype=I32, device=dev)
+    _req(out.dtype == I32 and out.is_contiguous() and out.numel() == (1 + nk) * C and out.device == dev, "retrieval_class_counts: out int32 [(1+nk)*C]")
+    seen, right = out[:C], out[C:].view(nk, C)
+    c_offs, c_ks = (ctypes.c_int32 * (L + 1))(*offs), (ctypes.c_int32 * nk)(*ks)
+    check(_l.load().bsclip_retrieval_class_counts(_p(hit_rank), _p(query_labels), Q, L, ctypes.cast(c_offs, ctypes.c_void_p),
+                                                  ctypes.cast(c_ks, ctypes.c_void_p), nk, _p(seen), _p(right), _p(flag), _stream()))
+    if own:
+        check_retrieval_flag(int(flag.item()))
+    return seen, right
+
+
 _LG_WS = {}
 
 

@@ -1,0 +1,157 @@
+"""GPU-resident retrieval evaluation: a key index built once per key set (faiss ``index.add`` once, many ``search``), label matching
+and per-class counting as HIP kernels on integer label ids, and the host assembly of the accuracy tables from those integers.
+
+What the reference does per (query type, key type, split) cell in ``make_prediction`` / ``top_k_micro_accuracy`` /
+``top_k_macro_accuracy`` (scripts/inference_and_eval.py:414-511) on lists of strings happens here on int32 ids:
+
+    index = RetrievalIndex(keys)                                      # normalise + split the keys once
+    (key_ids, query_ids), vocab = encode_labels(key_labels, query_labels)
+    acc, per_class = evaluate(index, key_ids, queries, query_ids, [1, 3, 5], vocab=vocab)
+
+The kernels return integers only (first hit rank per query and level, per-class histograms); the ratios are formed here in float64
+in the reference's order of operations, so the tables equal the string path's bit for bit.  There is no CPU path for the search
+and the counting: without the HIP library or a GPU they raise.
+"""
+import numpy as np
+import torch
+
+from . import ops
+
+LEVELS = ["order", "family", "genus", "species"]
+
+
+def encode_labels(*label_lists, levels=None):
+    """Map the strings of each level to dense int32 ids shared by all the given label lists (each a list of ``{level: name}``).
+
+    Returns ``(arrays, vocab)``: one int32 ``[N, L]`` array per label list and ``vocab[level]`` = the names in id order (ids are
+    handed out in order of first appearance, per level).  No name is special: equal strings get equal ids and nothing else does.
+    """
+    levels = list(LEVELS if levels is None else levels)
+    table = {lv: {} for lv in levels}
+    arrays = []
+    for labels in label_lists:
+        ids = np.empty((len(labels), len(levels)), dtype=np.int32)
+        for j, lv in enumerate(levels):
+            t = table[lv]
+            ids[:, j] = [t.setdefault(lab[lv], len(t)) for lab in labels]
+        arrays.append(ids)
+    return arrays, {lv: list(table[lv]) for lv in levels}
+
+
+def decode_labels(ids, vocab, levels=None):
+    """Inverse of ``encode_labels`` for one array: the list of ``{level: name}``."""
+    levels = list(vocab if levels is None else levels)
+    return [{lv: vocab[lv][i] for lv, i in zip(levels, row)} for row in np.asarray(ids).tolist()]
+
+
+class Labels:
+    """One split's label ids, int32 ``[N, L]``: the host copy, the GPU copy (uploaded once) and, for the query role, what the
+    assembly needs of them -- per level the class range and the classes in order of first appearance."""
+
+    def __init__(self, ids, device=None):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim != 2 or not 1 <= ids.shape[1] <= 8:
+            raise ValueError("label ids must be [N, L] with 1 <= L <= 8")
+        if ids.size and ids.min() < 0:
+            raise ValueError("label ids must be >= 0")
+        self.ids = ids
+        self.dev = torch.from_numpy(ids).to(torch.device(device if device is not None else "cuda"))
+        self._order = None
+
+    @property
+    def level_offsets(self):
+        sizes = (self.ids.max(axis=0) + 1) if len(self.ids) else np.zeros(self.ids.shape[1], dtype=np.int64)
+        return [0] + np.cumsum(sizes, dtype=np.int64).tolist()
+
+    @property
+    def class_order(self):
+        if self._order is None:
+            self._order = [first_appearance_order(self.ids[:, j]) for j in range(self.ids.shape[1])]
+        return self._order
+
+
+def first_appearance_order(ids):
+    """The distinct values of a 1-D id array in order of first appearance (the iteration order of the reference's ``seen`` dict)."""
+    u, first = np.unique(ids, return_index=True)
+    return u[np.argsort(first, kind="stable")]
+
+
+class RetrievalIndex:
+    """``faiss.IndexFlatIP(d).add(normalize(keys))`` kept on the GPU: the keys (f32 GPU tensor or numpy array, ``[K, D]``) are
+    uploaded, L2-normalised and split into the search kernels' operand once; ``search`` only reads it."""
+
+    def __init__(self, keys, device=None):
+        if not torch.is_tensor(keys):
+            keys = torch.as_tensor(np.ascontiguousarray(keys, dtype=np.float32)).to(torch.device(device if device is not None else "cuda"))
+        self.K, self.D = int(keys.shape[0]), int(keys.shape[1])
+        self.device = keys.device
+        self.index = ops.retrieval_index_build(keys.contiguous())
+
+    def search(self, queries, k):
+        """(similarities f32 ``[Q, k]``, indices int64 ``[Q, k]``) as GPU tensors -- what ``ops.topk_ip(queries, keys, k)`` returns."""
+        if not torch.is_tensor(queries):
+            queries = torch.as_tensor(np.ascontiguousarray(queries, dtype=np.float32)).to(self.device)
+        return ops.topk_ip_indexed(queries.contiguous(), self.index, self.K, int(k))
+
+
+def assemble_accuracy(seen, right, query_ids, level_offsets, k_list, class_order=None, vocab=None, levels=None):
+    """Micro / macro / per-class accuracy from the integer counts, in the reference's arithmetic (:448-511).
+
+    ``seen`` int ``[C]`` and ``right`` int ``[nk, C]`` are the per-class histograms over the flat class range laid out by
+    ``level_offsets``; ``query_ids`` int ``[Q, L]``.  Per level: micro = (sum of ``right`` over the level) * 1.0 / Q; per class
+    ``right * 1.0 / seen``; macro = the running sum of those in order of first appearance among the queries, divided by the number
+    of classes seen -- float64 throughout, as Python does on the reference's ints.  Classes are named through ``vocab`` (else by id).
+    """
+    query_ids = np.asarray(query_ids)
+    Q, L = query_ids.shape
+    levels = list((vocab if vocab is not None else LEVELS[:L]) if levels is None else levels)
+    if len(levels) != L:
+        raise ValueError(f"{L} label columns but {len(levels)} level names")
+    if class_order is None:
+        class_order = [first_appearance_order(query_ids[:, j]) for j in range(L)]
+    seen, right = np.asarray(seen), np.asarray(right)
+    micro, macro, per_class = {}, {}, {}
+    for i, k in enumerate(k_list):
+        micro[k], macro[k], per_class[k] = {}, {}, {}
+        for j, lv in enumerate(levels):
+            lo, hi = level_offsets[j], level_offsets[j + 1]
+            micro[k][lv] = int(right[i, lo:hi].sum()) * 1.0 / Q
+            order = class_order[j]
+            ratios = right[i, lo + order].astype(np.float64) / seen[lo + order].astype(np.float64)
+            names = [vocab[lv][c] for c in order.tolist()] if vocab is not None else order.tolist()
+            per_class[k][lv] = dict(zip(names, ratios.tolist()))
+            macro[k][lv] = float(np.cumsum(ratios)[-1]) / len(order)   # cumsum adds left to right, like the reference's loop
+    return {"micro_acc": micro, "macro_acc": macro}, per_class
+
+
+def evaluate(index, key_label_ids, queries, query_label_ids, k_list, max_k=None, vocab=None, levels=None, return_indices=False):
+    """One cell of the accuracy table on the GPU: search ``queries`` in ``index``, match labels, count per class.
+
+    ``key_label_ids`` / ``query_label_ids``: int32 ``[K', L]`` (K' >= the index's K) / ``[Q, L]`` as numpy arrays or ``Labels``
+    (uploaded once, reusable across cells).  ``max_k`` (default ``max(k_list)``) is the search depth; a k above it counts hits in
+    the whole list, like the reference's ``pred[:k]``.  Returns ``({"micro_acc": {k: {level: float}}, "macro_acc": {...}},
+    per_class)`` with ``per_class[k][level][class] = float`` -- the structures of ``top_k_micro_accuracy`` /
+    ``top_k_macro_accuracy`` -- and, with ``return_indices``, the int64 ``[Q, max_k]`` GPU tensor of key indices as a third item.
+    """
+    k_list = list(k_list)
+    if not 1 <= len(k_list) <= 8 or min(k_list) < 1:
+        raise ValueError("k_list: 1 to 8 values, each >= 1")
+    max_k = max(k_list) if max_k is None else int(max_k)
+    kl = key_label_ids if isinstance(key_label_ids, Labels) else Labels(key_label_ids, index.device)
+    ql = query_label_ids if isinstance(query_label_ids, Labels) else Labels(query_label_ids, index.device)
+    if kl.ids.shape[0] < index.K:
+        raise ValueError(f"{kl.ids.shape[0]} key labels for an index of {index.K} keys")
+    _, idx = index.search(queries, max_k)
+    if idx.shape[0] != ql.ids.shape[0] or kl.ids.shape[1] != ql.ids.shape[1]:
+        raise ValueError("query labels do not match the queries, or key and query labels differ in levels")
+    offsets = ql.level_offsets
+    C, nk = offsets[-1], len(k_list)
+    buf = torch.empty(1 + (1 + nk) * C, dtype=torch.int32, device=idx.device)   # [flag | seen | right]: one download per cell
+    flag = buf[:1].zero_()
+    hit_rank = ops.retrieval_hit_ranks(idx, kl.dev, ql.dev, flag=flag)
+    ops.retrieval_class_counts(hit_rank, ql.dev, offsets, [min(k, max_k) for k in k_list], flag=flag, out=buf[1:])
+    host = buf.cpu().numpy()
+    ops.check_retrieval_flag(int(host[0]))
+    acc, per_class = assemble_accuracy(host[1:1 + C], host[1 + C:].reshape(nk, C), ql.ids, offsets, k_list,
+                                       class_order=ql.class_order, vocab=vocab, levels=levels)
+    return (acc, per_class, idx) if return_indices else (acc, per_class)

@@ -187,20 +187,15 @@ extern "C" int64_t bsclip_topk_ip_workspace_floats(int Q, int K, int D) {
     return al4(Kp * 2 * D) + al4(Qs * 2 * D) + al4(Qs * Kp);
 }
 
-extern "C" int bsclip_topk_ip(const float* queries, int Q, const float* keys, int K, int D, int k, float* scores_out,
-                              int64_t* idx_out, float* workspace, void* stream) {
-    BSCLIP_REQUIRE(queries && keys && scores_out && idx_out && workspace, "bsclip_topk_ip: null pointer");
-    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "bsclip_topk_ip: Q=%d K=%d D=%d (D %% 64 == 0)", Q, K, D);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "bsclip_topk_ip: k=%d (1..16, <= K)", k);
-    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0, "bsclip_topk_ip: workspace must be 16-B aligned");
+// The query side shared by bsclip_topk_ip and bsclip_topk_ip_indexed: slabs of <= TOPK_SLAB queries against the prepared key
+// operand kP (bf16 [pad_keys(K), 4 D]); ws holds the query operand and one score slab.
+static int topk_search(const float* queries, int Q, const bf16_t* kP, int K, int D, int k, float* scores_out, int64_t* idx_out,
+                       float* ws, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int Kp = pad_keys(K);
     const int Qs = Q < TOPK_SLAB ? Q : TOPK_SLAB;
-    float* ws = workspace;
-    bf16_t* kP = reinterpret_cast<bf16_t*>(ws); ws += al4((int64_t)Kp * 2 * D);
     bf16_t* qP = reinterpret_cast<bf16_t*>(ws); ws += al4((int64_t)Qs * 2 * D);
     float* sc = ws;
-    hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(Kp, 4)), dim3(256), 0, s, keys, K, Kp, D, kP);
     for (int q0 = 0; q0 < Q; q0 += TOPK_SLAB) {
         const int nq = Q - q0 < TOPK_SLAB ? Q - q0 : TOPK_SLAB;
         hipLaunchKernelGGL((normalize_split4_kernel<false>), dim3(ceil_div(nq, 4)), dim3(256), 0, s,
@@ -214,6 +209,178 @@ extern "C" int bsclip_topk_ip(const float* queries, int Q, const float* keys, in
         else
             hipLaunchKernelGGL((topk_rows_kernel<16>), dim3(ceil_div(nq, 4)), dim3(256), 0, s, sc, Kp, nq, K, k, so, io, k);
     }
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_topk_ip(const float* queries, int Q, const float* keys, int K, int D, int k, float* scores_out,
+                              int64_t* idx_out, float* workspace, void* stream) {
+    BSCLIP_REQUIRE(queries && keys && scores_out && idx_out && workspace, "bsclip_topk_ip: null pointer");
+    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "bsclip_topk_ip: Q=%d K=%d D=%d (D %% 64 == 0)", Q, K, D);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "bsclip_topk_ip: k=%d (1..16, <= K)", k);
+    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0, "bsclip_topk_ip: workspace must be 16-B aligned");
+    const int Kp = pad_keys(K);
+    bf16_t* kP = reinterpret_cast<bf16_t*>(workspace);
+    hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(Kp, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       keys, K, Kp, D, kP);
+    return topk_search(queries, Q, kP, K, D, k, scores_out, idx_out, workspace + al4((int64_t)Kp * 2 * D), stream);
+}
+
+// ---- key index: the key operand of bsclip_topk_ip, built once and searched many times ------------------------------------------
+
+extern "C" int64_t bsclip_retrieval_index_floats(int K, int D) {
+    if (K <= 0 || D <= 0) return -1;
+    return al4((int64_t)pad_keys(K) * 2 * D);
+}
+
+extern "C" int bsclip_retrieval_index_build(const float* keys, int K, int D, float* index, void* stream) {
+    BSCLIP_REQUIRE(keys && index, "bsclip_retrieval_index_build: null pointer");
+    BSCLIP_REQUIRE(K > 0 && D > 0 && D % 64 == 0, "bsclip_retrieval_index_build: K=%d D=%d (D %% 64 == 0)", K, D);
+    BSCLIP_REQUIRE((((uintptr_t)keys) & 15) == 0 && (((uintptr_t)index) & 15) == 0,
+                   "bsclip_retrieval_index_build: keys and index must be 16-B aligned");
+    const int Kp = pad_keys(K);
+    hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(Kp, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       keys, K, Kp, D, reinterpret_cast<bf16_t*>(index));
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int64_t bsclip_topk_ip_indexed_workspace_floats(int Q, int K, int D) {
+    if (Q <= 0 || K <= 0 || D <= 0) return -1;
+    const int64_t Kp = pad_keys(K), Qs = Q < TOPK_SLAB ? Q : TOPK_SLAB;
+    return al4(Qs * 2 * D) + al4(Qs * Kp);  // query operand bf16 [Qs, 4D] + one f32 score slab [Qs, Kp]
+}
+
+extern "C" int bsclip_topk_ip_indexed(const float* queries, int Q, const float* index, int K, int D, int k, float* scores_out,
+                                      int64_t* idx_out, float* workspace, void* stream) {
+    BSCLIP_REQUIRE(queries && index && scores_out && idx_out && workspace, "bsclip_topk_ip_indexed: null pointer");
+    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "bsclip_topk_ip_indexed: Q=%d K=%d D=%d (D %% 64 == 0)", Q, K, D);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "bsclip_topk_ip_indexed: k=%d (1..16, <= K)", k);
+    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0 && (((uintptr_t)index) & 15) == 0,
+                   "bsclip_topk_ip_indexed: index and workspace must be 16-B aligned");
+    return topk_search(queries, Q, reinterpret_cast<const bf16_t*>(index), K, D, k, scores_out, idx_out, workspace, stream);
+}
+
+// ---- scoring on integer label ids (make_prediction's label lookup + top_k_micro_accuracy / top_k_macro_accuracy counts) -------
+
+namespace {
+
+constexpr int EVAL_MAX_LEVELS = 8;
+constexpr int EVAL_MAX_K = 8;
+constexpr int EVAL_FLAG_BAD_IDX = 1;    // an idx entry outside [0, K)
+constexpr int EVAL_FLAG_BAD_LABEL = 2;  // a query label outside its level's class range
+
+// 16 lanes per query (4 queries per wave, 16 per block); lane r < k owns rank r: it gathers the L labels of key idx[q, r] and a
+// ballot per level finds the first rank whose label equals the query's.  An idx outside [0, K) is flagged, never dereferenced.
+__global__ __launch_bounds__(256) void hit_ranks_kernel(const int64_t* __restrict__ idx, int Q, int k,
+                                                         const int* __restrict__ key_labels, int K,
+                                                         const int* __restrict__ query_labels, int L, int* __restrict__ hit_rank,
+                                                         int* __restrict__ flag) {
+    const int lane = threadIdx.x & 63, sub = lane >> 4, r = lane & 15;
+    const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool inq = q < Q && r < k;
+    const int64_t id = inq ? idx[(size_t)q * k + r] : 0;
+    const bool ok = inq && id >= 0 && id < K;
+    if (inq && !ok) atomicOr(flag, EVAL_FLAG_BAD_IDX);
+    int kl[EVAL_MAX_LEVELS];
+#pragma unroll
+    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) kl[l] = (ok && l < L) ? key_labels[(size_t)id * L + l] : 0;
+#pragma unroll
+    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) {
+        if (l >= L) break;  // wave-uniform
+        const int ql = q < Q ? query_labels[(size_t)q * L + l] : 0;
+        const unsigned long long b = __ballot(ok && kl[l] == ql);
+        const unsigned g = (unsigned)(b >> (sub * 16)) & 0xffffu;
+        if (r == l && q < Q) hit_rank[(size_t)q * L + l] = g ? __ffs(g) - 1 : k;
+    }
+}
+
+struct CountCfg {
+    int off[EVAL_MAX_LEVELS + 1];
+    int kl[EVAL_MAX_K];
+};
+
+// blockIdx.y = level, one lane per query.  The lanes of a wave that hold the same class are counted with ballots and their
+// first lane adds the sums, so a level with few classes (order) does not serialise Q atomics on a handful of addresses.
+__global__ __launch_bounds__(256) void class_counts_kernel(const int* __restrict__ hit_rank, const int* __restrict__ query_labels,
+                                                            int Q, int L, CountCfg cfg, int nk, int* __restrict__ seen,
+                                                            int* __restrict__ right, int* __restrict__ flag) {
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const int C = cfg.off[L];
+    int c = -1, h = 0;
+    if (q < Q) {
+        const int lab = query_labels[(size_t)q * L + l];
+        if (lab >= 0 && lab < cfg.off[l + 1] - cfg.off[l]) {
+            c = cfg.off[l] + lab;
+            h = hit_rank[(size_t)q * L + l];
+        } else {
+            atomicOr(flag, EVAL_FLAG_BAD_LABEL);
+        }
+    }
+    unsigned long long todo = __ballot(c >= 0);  // wave-uniform loop: every lane runs every trip
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int c0 = __shfl(c, lead, 64);
+        const bool same = c == c0;
+        const unsigned long long m = __ballot(same);
+        if (lane == lead) atomicAdd(seen + c0, __popcll(m));
+        for (int j = 0; j < nk; ++j) {
+            const unsigned long long hit = __ballot(same && h < cfg.kl[j]);
+            if (lane == lead && hit) atomicAdd(right + (size_t)j * C + c0, __popcll(hit));
+        }
+        todo &= ~m;
+    }
+}
+
+}  // namespace
+
+extern "C" int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K,
+                                          const int32_t* query_labels, int L, int32_t* hit_rank, int32_t* flag, void* stream) {
+    BSCLIP_REQUIRE(idx && key_labels && query_labels && hit_rank && flag, "bsclip_retrieval_hit_ranks: null pointer");
+    BSCLIP_REQUIRE(Q > 0 && K > 0, "bsclip_retrieval_hit_ranks: Q=%d K=%d", Q, K);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_hit_ranks: k=%d (1..16)", k);
+    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_hit_ranks: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    BSCLIP_REQUIRE((((uintptr_t)idx) & 7) == 0 && ((((uintptr_t)key_labels) | ((uintptr_t)query_labels) | ((uintptr_t)hit_rank) |
+                                                    ((uintptr_t)flag)) & 3) == 0,
+                   "bsclip_retrieval_hit_ranks: idx must be 8-B aligned, the int32 buffers 4-B aligned");
+    hipLaunchKernelGGL(hit_ranks_kernel, dim3(ceil_div(Q, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), idx, Q, k,
+                       key_labels, K, query_labels, L, hit_rank, flag);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int32_t* query_labels, int Q, int L,
+                                             const int32_t* level_offsets, const int32_t* k_list, int nk, int32_t* seen,
+                                             int32_t* right, int32_t* flag, void* stream) {
+    BSCLIP_REQUIRE(hit_rank && query_labels && level_offsets && k_list && seen && right && flag,
+                   "bsclip_retrieval_class_counts: null pointer");
+    BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_class_counts: Q=%d", Q);
+    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_class_counts: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    BSCLIP_REQUIRE(nk >= 1 && nk <= EVAL_MAX_K, "bsclip_retrieval_class_counts: nk=%d (1..%d)", nk, EVAL_MAX_K);
+    BSCLIP_REQUIRE(((((uintptr_t)hit_rank) | ((uintptr_t)query_labels) | ((uintptr_t)seen) | ((uintptr_t)right) | ((uintptr_t)flag)) &
+                    3) == 0, "bsclip_retrieval_class_counts: the int32 buffers must be 4-B aligned");
+    CountCfg cfg = {};
+    BSCLIP_REQUIRE(level_offsets[0] == 0, "bsclip_retrieval_class_counts: level_offsets[0] must be 0");
+    for (int l = 0; l <= L; ++l) {
+        cfg.off[l] = level_offsets[l];
+        BSCLIP_REQUIRE(l == 0 || cfg.off[l] >= cfg.off[l - 1], "bsclip_retrieval_class_counts: level_offsets must not decrease");
+    }
+    BSCLIP_REQUIRE(cfg.off[L] > 0, "bsclip_retrieval_class_counts: no classes");
+    for (int j = 0; j < nk; ++j) {
+        cfg.kl[j] = k_list[j];
+        BSCLIP_REQUIRE(cfg.kl[j] >= 1, "bsclip_retrieval_class_counts: k_list[%d]=%d (>= 1)", j, cfg.kl[j]);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t C = (size_t)cfg.off[L];
+    if (hipMemsetAsync(seen, 0, C * sizeof(int32_t), s) != hipSuccess ||
+        hipMemsetAsync(right, 0, C * nk * sizeof(int32_t), s) != hipSuccess) {
+        bsclip_set_error("bsclip_retrieval_class_counts: clearing the outputs failed: %s", hipGetErrorString(hipGetLastError()));
+        return BSCLIP_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(class_counts_kernel, dim3(ceil_div(Q, 256), L), dim3(256), 0, s, hit_rank, query_labels, Q, L, cfg, nk,
+                       seen, right, flag);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

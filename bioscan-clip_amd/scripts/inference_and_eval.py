@@ -9,6 +9,10 @@ Mirrored entry points (same names, argument meaning and return shapes as the ref
     get_features_and_label     :734-784
     main                       :786-871   (config -> load_clip_model -> checkpoint unless load_ckpt=false -> features -> table;
                                            splits from the synthetic evaluation loaders, feature cache as .npz)
+
+``hip_eval=gpu`` (default ``host``) selects ``inference_and_print_result_gpu``: the same cell table with one key index per key type
+(built once, searched by every query type and both splits), labels as int32 ids, and hit matching / per-class counting as HIP
+kernels (``bioscanclip/hip/retrieval.py``); the tables are equal to the host path's, bit for bit.
 """
 import os
 import sys
@@ -158,6 +162,76 @@ def inference_and_print_result(keys_dict, seen_dict, unseen_dict, args=None, sma
     return acc_dict, per_class_acc, pred_dict
 
 
+HIP_EVAL_MODES = ("host", "gpu")
+
+
+def select_eval(args):
+    """``hip_eval=host`` (default): ``inference_and_print_result``; ``hip_eval=gpu``: ``inference_and_print_result_gpu``."""
+    mode = str(getattr(args, "hip_eval", "host"))
+    if mode not in HIP_EVAL_MODES:
+        raise ValueError(f"hip_eval must be one of {HIP_EVAL_MODES}, not {mode!r}")
+    return inference_and_print_result_gpu if mode == "gpu" else inference_and_print_result
+
+
+def inference_and_print_result_gpu(keys_dict, seen_dict, unseen_dict, args=None, small_species_list=None, k_list=None,
+                                   with_predictions=False):
+    """``inference_and_print_result`` with the evaluation resident on the GPU: same cell loop, skip rules, printed table, ``acc_dict``
+    and ``per_class_acc``.  Every key type's index is built once and every query feature uploaded once; the labels are encoded to
+    int32 ids once per call.  ``pred_dict[q][kf]`` holds the int64 ``[Q, max_k]`` GPU index tensors (``curr_seen_indices`` /
+    ``curr_unseen_indices``); ``with_predictions=True`` builds the host path's string lists from them instead."""
+    from bioscanclip.hip.retrieval import Labels, RetrievalIndex, encode_labels, evaluate
+    if k_list is None:
+        k_list = [1, 3, 5]
+    max_k = k_list[-1]
+    acc_dict, per_class_acc, pred_dict = {}, {}, {}
+    label_lists = {"label_list": keys_dict["label_list"], "all_key_features_label": keys_dict.get("all_key_features_label") or [],
+                   "seen": seen_dict["label_list"], "unseen": unseen_dict["label_list"]}
+    arrays, vocab = encode_labels(*label_lists.values(), levels=LEVELS)
+    label_ids = dict(zip(label_lists, arrays))
+    uploaded, indices, queries = {}, {}, {}
+
+    def labels_of(name):
+        if name not in uploaded:
+            uploaded[name] = Labels(label_ids[name])
+        return uploaded[name]
+
+    def query_of(split, q, feature):
+        if (split, q) not in queries:
+            queries[split, q] = torch.as_tensor(np.ascontiguousarray(feature, dtype=np.float32)).to("cuda")
+        return queries[split, q]
+
+    keys_label = "label_list"
+    for q in All_TYPE_OF_FEATURES_OF_QUERY:
+        if q not in seen_dict:
+            continue
+        acc_dict[q], per_class_acc[q], pred_dict[q] = {}, {}, {}
+        for kf in All_TYPE_OF_FEATURES_OF_KEY:
+            if kf not in keys_dict:
+                continue
+            acc_dict[q][kf], per_class_acc[q][kf], pred_dict[q][kf] = {}, {}, {}
+            keys, seen, unseen = keys_dict[kf], seen_dict[q], unseen_dict[q]
+            if keys is None:
+                continue
+            if kf == "all_key_features":
+                keys_label = "all_key_features_label"  # sticks for later key types, as in the reference (:666)
+            if seen is None or unseen is None or keys.shape[-1] != seen.shape[-1] or keys.shape[-1] != unseen.shape[-1]:
+                continue
+            if kf not in indices:
+                indices[kf] = RetrievalIndex(keys)
+            for s, feature in (("seen", seen), ("unseen", unseen)):
+                acc, per_class, idx = evaluate(indices[kf], labels_of(keys_label), query_of(s, q, feature), labels_of(s), k_list,
+                                               max_k=max_k, vocab=vocab, levels=LEVELS, return_indices=True)
+                acc_dict[q][kf][s], per_class_acc[q][kf][s] = acc, per_class
+                if with_predictions:
+                    names = label_lists[keys_label]
+                    pred_dict[q][kf][f"curr_{s}_pred_list"] = [{level: [names[i][level] for i in row] for level in LEVELS}
+                                                              for row in idx.cpu().numpy()]
+                else:
+                    pred_dict[q][kf][f"curr_{s}_indices"] = idx
+    print_micro_and_macro_acc(acc_dict, k_list, args)
+    return acc_dict, per_class_acc, pred_dict
+
+
 def main(argv=None):
     """Reference entry (scripts/inference_and_eval.py:786-871): config -> ``load_clip_model`` -> checkpoint
     (``model_config.ckpt_path`` unless ``model_config.load_ckpt`` is false, :839-843) -> features of the key / seen / unseen
@@ -165,7 +239,8 @@ def main(argv=None):
     evaluation loaders; extracted features are cached as ``.npz`` (h5py is absent) under the reference's directory layout
     (``extracted_embedding/<dataset>/<model_output_name>/``) and reused with ``load_inference=true`` (:797-833).
     ``hip_operands=fp16`` (default bf16) runs the three encoders on fp16 operands (``set_operand_format``); the cache records the
-    format it was extracted with and is reused only by a run of the same format."""
+    format it was extracted with and is reused only by a run of the same format.  ``hip_eval=gpu`` (default host) scores the
+    table with ``inference_and_print_result_gpu``."""
     from bioscanclip.hip.engine import OPERAND_FORMATS, set_operand_format
     from bioscanclip.model.simple_clip import load_clip_model
     from bioscanclip.util.config import load_config
@@ -174,6 +249,7 @@ def main(argv=None):
     here = os.path.dirname(os.path.abspath(__file__))
     args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
     mc = args.model_config
+    evaluate_splits = select_eval(args)
     if not torch.cuda.is_available():
         raise RuntimeError("inference_and_eval needs a ROCm GPU: the encoders and the top-k search run in libbsclip_hip.so")
     device = torch.device("cuda", 0)
@@ -212,7 +288,7 @@ def main(argv=None):
             np.savez(feats_path, keys=np.array(splits[0], dtype=object), seen=np.array(splits[1], dtype=object),
                      unseen=np.array(splits[2], dtype=object), operands=np.array(operands))
     keys_dict, seen_dict, unseen_dict = splits
-    return inference_and_print_result(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
+    return evaluate_splits(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
 
 
 if __name__ == "__main__":

@@ -54,11 +54,13 @@ def broadcast_model(model, rank):
 def eval_phase(model, device, all_keys_dataloader, seen_val_dataloader, unseen_val_dataloader, k_list, args,
                species_to_drop=None, rank=None, for_open_clip=False):
     """Reference train_cl.py:70-83: features of the key / seen / unseen splits on the HIP encoders, then the retrieval
-    accuracy table (``bsclip_topk_ip`` in place of faiss)."""
+    accuracy table (``bsclip_topk_ip`` in place of faiss).  ``args.hip_eval`` = ``gpu`` (default ``host``) scores the table on the GPU
+    (``inference_and_print_result_gpu``: same ``acc_dict``; ``pred_dict`` then holds index tensors instead of string lists)."""
     here = os.path.dirname(os.path.abspath(__file__))
     if here not in sys.path:
         sys.path.insert(0, here)
-    from inference_and_eval import get_features_and_label, inference_and_print_result
+    from inference_and_eval import get_features_and_label, select_eval
+    inference_and_print_result = select_eval(args)   # refuses an unknown hip_eval before any feature is extracted
     keys_dict = get_features_and_label(all_keys_dataloader, model, device, for_key_set=True, for_open_clip=for_open_clip)
     seen_val_dict = get_features_and_label(seen_val_dataloader, model, device, for_open_clip=for_open_clip)
     unseen_val_dict = get_features_and_label(unseen_val_dataloader, model, device, for_open_clip=for_open_clip)

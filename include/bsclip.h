@@ -386,6 +386,32 @@ int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int64_t* label
 int64_t bsclip_topk_ip_workspace_floats(int Q, int K, int D);
 int bsclip_topk_ip(const float* queries, int Q, const float* keys, int K, int D, int k, float* scores_out,
                    int64_t* idx_out, float* workspace, void* stream);
+/* faiss `index.add(keys)` once, many `.search`: bsclip_retrieval_index_build normalises and splits the keys f32 [K, D] into
+ * `index`, a caller-owned 16-B aligned buffer of bsclip_retrieval_index_floats(K, D) floats (the key operand bsclip_topk_ip builds
+ * on every call: bf16 [K padded to 256, 4 D], [lo|hi|lo|hi]).  bsclip_topk_ip_indexed is the query side of bsclip_topk_ip against
+ * that buffer: same kernels, bit-identical outputs; it only reads the index.  workspace: f32, 16-B aligned, at least
+ * bsclip_topk_ip_indexed_workspace_floats(Q, K, D) elements. */
+int64_t bsclip_retrieval_index_floats(int K, int D);
+int bsclip_retrieval_index_build(const float* keys, int K, int D, float* index, void* stream);
+int64_t bsclip_topk_ip_indexed_workspace_floats(int Q, int K, int D);
+int bsclip_topk_ip_indexed(const float* queries, int Q, const float* index, int K, int D, int k, float* scores_out,
+                           int64_t* idx_out, float* workspace, void* stream);
+/* Scoring on integer label ids (make_prediction's label lookup :424-437, top_k_micro_accuracy :448-464, top_k_macro_accuracy
+ * :467-511); integers only, the caller forms the ratios.
+ *   hit_ranks: idx int64 [Q, k] (k <= 16), key_labels int32 [K, L], query_labels int32 [Q, L], L <= 8 levels ->
+ *     hit_rank int32 [Q, L] = the smallest r in [0, k) with key_labels[idx[q, r], l] == query_labels[q, l], or k without one;
+ *     a hit at top-k' (k' <= k) is hit_rank < k'.
+ *   class_counts: level_offsets int32 [L + 1] (HOST memory, level_offsets[0] = 0, non-decreasing) places the class ids of level l
+ *     at [level_offsets[l], level_offsets[l + 1]) of one flat range of C = level_offsets[L] classes; k_list int32 [nk] (HOST
+ *     memory, nk <= 8).  seen int32 [C] = queries per class, right int32 [nk, C] = those with hit_rank < k_list[j]; both are
+ *     cleared by the entry point.  Integer atomics: the result does not depend on their order.
+ * flag: one int32 device word the caller clears; the kernels only OR into it, so one word serves many calls.  Bit 0: an idx
+ * entry outside [0, K) (never dereferenced, counted as no hit); bit 1: a query label outside its level's range (not counted). */
+int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K, const int32_t* query_labels,
+                               int L, int32_t* hit_rank, int32_t* flag, void* stream);
+int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int32_t* query_labels, int Q, int L,
+                                  const int32_t* level_offsets, const int32_t* k_list, int nk, int32_t* seen, int32_t* right,
+                                  int32_t* flag, void* stream);
 
 /* ---- RCCL collectives of the global-batch step ---------------------------------------------------
  * One process per GPU.  bsclip_comm_unique_id on rank 0 -> the caller ships the bsclip_comm_unique_id_bytes() bytes to the
