@@ -159,6 +159,11 @@ def _pad64(n):
     return (n + 63) // 64 * 64
 
 
+def tok0(t, B):
+    """Token 0 of every image: rows 0, S, 2S, ... of a [B * S, w] tensor as a [B, w] view (row stride S * w)."""
+    return t.view(B, -1)[:, :t.shape[1]]
+
+
 def _rank():
     import torch.distributed as dist
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -288,6 +293,33 @@ class EncoderEngineBase:
                 b = self.lora_b(l)
                 if b is not None:
                     ops.lora_baug_set(lay.baug, self.H, b[0], b[1], lay.s_qkv)
+
+    def _lora_grads(self, l, ws, h_aug, h_fp8, part, grad_scale_log2=None):
+        """dA / dB of layer l's LoRA pair, and dt for the LayerNorm backward below it, from ws["dqkv"].  ``h_aug``: the QKV GEMM's
+        operand (LayerNorm output | t); ``h_fp8``: its fp8 form (fp8 engines); ``part``: attn_bwd left the partial sums."""
+        lb = self.lora_b(l)
+        if lb is None:
+            return
+        M, H = ws["M"], self.H
+        dA, dB = self.lora_a(l, grad=True), self.lora_b(l, grad=True)
+        if self.fp8:
+            ops.lora_grad_fp8(ws["dqkv"], h_fp8, ws["t"][l], M, H, lb, ws["dt"], dA, dB[0], dB[1])
+        elif part:
+            ops.lora_grad_heads(h_aug, M, H, ws["B"], ws["dtp"], ws["dbp"], ws["dt"], dA, dB[0], dB[1],
+                                grad_scale_log2=grad_scale_log2)
+        else:
+            ops.lora_grad(ws["dqkv"], h_aug, M, H, lb, ws["dt"], dA, dB[0], dB[1])
+
+    # What full fine-tuning adds to the backward sequences (hip/engine_ft.py implements them): nothing here, where only the LoRA
+    # pairs and the heads are trained.  Their arguments are evaluated in both regimes: no FT-only workspace entry among them.
+    def _dw(self, dY, X, M, N, K, wname, bname, w_n=None):
+        """Weight and bias gradient of a Linear; called in front of the dX GEMM that reads the same dY."""
+
+    def _ln_dw(self, x, stats, mode, wname, bname, **grads):
+        """Gain and bias gradient of a LayerNorm; called in front of its layernorm_bwd."""
+
+    def _below_layer0(self, ws, *grads):
+        """The embeddings' gradients, once the chain has passed layer 0."""
 
     fp8 = False
     fp16 = False
@@ -494,16 +526,18 @@ class ViTEngine(EncoderEngineBase):
     def anomaly_probes(self):
         """(name, tensor) of the forward's saved activations in execution order (BSCLIP_DETECT_ANOMALY).  The last block's
         sub-layers exist on the token-0 rows only."""
-        ws, L, B, S, H = self.ws, len(self.layers), self.ws["B"], self.S, self.H
+        ws, L, B = self.ws, len(self.layers), self.ws["B"]
         qkv, ctx = ("qkv32s", "ctx32s") if self.exact() else ("qkv", "ctx")
         yield "the patch embedding + position table", ws["x"][0]
         for l in range(L):
             yield f"blocks.{l}.attn.qkv output", ws[qkv][l]
             if l < L - 1:
                 yield f"blocks.{l}.attn output", ws[ctx][l]
-            tok0 = (lambda t: t.view(B, S * H)[:, :H]) if l == L - 1 else (lambda t: t)
-            yield f"blocks.{l} residual stream after attention", tok0(ws["x"][2 * l + 1])
-            yield f"blocks.{l} residual stream after the MLP", tok0(ws["x"][2 * l + 2])
+            x1, x2 = ws["x"][2 * l + 1], ws["x"][2 * l + 2]
+            if l == L - 1:
+                x1, x2 = tok0(x1, B), tok0(x2, B)
+            yield f"blocks.{l} residual stream after attention", x1
+            yield f"blocks.{l} residual stream after the MLP", x2
 
     # -------------------------------------------------------------------------------------------- forward
     def _forward_exact(self, image, ws):
@@ -520,7 +554,6 @@ class ViTEngine(EncoderEngineBase):
         ops.im2col_patch16(image, ws["cols"])
         ops.gemm(ws["cols"], self.w_patch3, x[0], EPI_PATCH_F32, bias=self.b_patch, resid=self.pos)
         ops.vit_cls_rows(x[0], self.cls, self.pos, B, S, H)
-        tok0 = lambda t, w: t.view(B, S * w)[:, :w]
         for l, lay in enumerate(self.layers):
             has = self._lora_index[l] is not None
             y32, qkv32, ctx32, z32 = ws["y32s"][l], ws["qkv32s"][l], ws["ctx32s"][l], ws["z32s"][l]
@@ -530,20 +563,20 @@ class ViTEngine(EncoderEngineBase):
             self._ex_gemm3(a3, lay.wqkv3, qkv32, EPI_F32, M, bias=lay.b_qkv)
             ops.attn_fwd_f32(qkv32, B, S, self.heads, scale, ctx32, ws["lse"][l], ctx_split3=a3 if l < L - 1 else None)
             if l == L - 1:   # token-0 rows only, as the default path (and as its backward expects)
-                self._ex_gemm(tok0(ctx32, H), lay.w3[0], tok0(x[2 * l + 1], H), EPI_RESID_F32, a3, bias=lay.b_proj,
-                              resid=tok0(x[2 * l], H))
-                ops.layernorm_fwd(tok0(x[2 * l + 1], H), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"], y_f32=ws["cls32"],
+                self._ex_gemm(tok0(ctx32, B), lay.w3[0], tok0(x[2 * l + 1], B), EPI_RESID_F32, a3, bias=lay.b_proj,
+                              resid=tok0(x[2 * l], B))
+                ops.layernorm_fwd(tok0(x[2 * l + 1], B), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"], y_f32=ws["cls32"],
                                   stats=ws["st_c"])
                 self._ex_gemm(ws["cls32"], lay.w3[1], z32, EPI_F32, a3, bias=lay.b_fc1)
                 g3 = ops.gelu_split3(z32, a3, M=B)
-                ops.gemm(g3, lay.w3[2], tok0(x[2 * l + 2], H), EPI_RESID_F32, bias=lay.b_fc2, resid=tok0(x[2 * l + 1], H), M=B)
+                ops.gemm(g3, lay.w3[2], tok0(x[2 * l + 2], B), EPI_RESID_F32, bias=lay.b_fc2, resid=tok0(x[2 * l + 1], B), M=B)
                 continue
             self._ex_gemm3(a3, lay.w3[0], x[2 * l + 1], EPI_RESID_F32, M, bias=lay.b_proj, resid=x[2 * l])   # a3: written by the attention kernel
             ops.layernorm_fwd(x[2 * l + 1], lay.ln2[0], lay.ln2[1], 1e-6, y_split3=a3, stats=ws["st2"][l])
             self._ex_gemm3(a3, lay.w3[1], z32, EPI_F32, M, bias=lay.b_fc1)
             g3 = ops.gelu_split3(z32, a3)
             ops.gemm(g3, lay.w3[2], x[2 * l + 2], EPI_RESID_F32, bias=lay.b_fc2, resid=x[2 * l + 1])
-        ops.layernorm_fwd(tok0(x[-1], H), self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], y_f32=ws["cls32"], stats=ws["st_f"])
+        ops.layernorm_fwd(tok0(x[-1], B), self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], y_f32=ws["cls32"], stats=ws["st_f"])
         ops.split3_weight(self.extra(0), ws["whead3"])
         out = torch.empty(B, self.out_dim, dtype=F32, device=self.device)
         self._ex_gemm(ws["cls32"], ws["whead3"], out, EPI_F32, a3, bias=self.extra(1))
@@ -579,15 +612,14 @@ class ViTEngine(EncoderEngineBase):
                 # The head reads token 0 of the last block only (timm global_pool='token'), and within a block a token's
                 # output depends on the other tokens through K and V alone: attention for query 0, then proj / LN2 / MLP on
                 # the B token-0 rows (row stride S*H) instead of all B*197.  Same values, 1/197 of the GEMM work.
-                tok0 = lambda t, w: t.view(B, S * w)[:, :w]
                 ops.attn_fwd(ws["qkv"][l], B, S, self.heads, scale, ws["ctx"][l], ws["lse"][l], q_rows=1)
-                ops.gemm(tok0(ws["ctx"][l], H), lay.w_proj, tok0(x[2 * l + 1], H), EPI_R, bias=lay.b_proj,
-                         resid=tok0(x[2 * l], H))
-                ops.layernorm_fwd(tok0(x[2 * l + 1], H), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"],
+                ops.gemm(tok0(ws["ctx"][l], B), lay.w_proj, tok0(x[2 * l + 1], B), EPI_R, bias=lay.b_proj,
+                         resid=tok0(x[2 * l], B))
+                ops.layernorm_fwd(tok0(x[2 * l + 1], B), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"],
                                   stats=ws["st_c"])
                 ops.gemm(ws["h2_c"], lay.w_fc1, ws["act_c"], EPI_GELU_BF16, bias=lay.b_fc1, aux=ws["z_c"])
-                ops.gemm(ws["act_c"], lay.w_fc2, tok0(x[2 * l + 2], H), EPI_R, bias=lay.b_fc2,
-                         resid=tok0(x[2 * l + 1], H))
+                ops.gemm(ws["act_c"], lay.w_fc2, tok0(x[2 * l + 2], B), EPI_R, bias=lay.b_fc2,
+                         resid=tok0(x[2 * l + 1], B))
                 continue
             ops.attn_fwd(ws["qkv"][l], B, S, self.heads, scale, ws["ctx"][l], ws["lse"][l])
             ops.gemm(ws["ctx"][l], lay.w_proj, x[2 * l + 1], EPI_R, bias=lay.b_proj, resid=x[2 * l])
@@ -600,8 +632,7 @@ class ViTEngine(EncoderEngineBase):
             ops.layernorm_fwd(x[2 * l + 1], lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=h2, stats=ws["st2"][l])
             ops.gemm(h2, lay.w_fc1, act, EPI_GELU_BF16, bias=lay.b_fc1, aux=ws["z"][l])
             ops.gemm(act, lay.w_fc2, x[2 * l + 2], EPI_R, bias=lay.b_fc2, resid=x[2 * l + 1])
-        x_cls = x[-1].view(B, S * H)[:, :H]  # token 0 of every image (row stride S*H)
-        ops.layernorm_fwd(x_cls, self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], stats=ws["st_f"])
+        ops.layernorm_fwd(tok0(x[-1], B), self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], stats=ws["st_f"])
         out = torch.empty(B, self.out_dim, dtype=F32, device=self.device)
         ops.gemm(ws["clsn"], self.w_head_bf, out, EPI_F32, bias=self.extra(1))
         return out
@@ -618,15 +649,17 @@ class ViTEngine(EncoderEngineBase):
     grad_probe = None
 
     def backward(self, dout):
+        """The LoRA, fp8, fp16 and full fine-tuning backward.  Full fine-tuning (hip/engine_ft.py) differs by what the hooks
+        ``_dw`` / ``_ln_dw`` / ``_below_layer0`` add -- no-ops here -- and by the chain continuing through block 0."""
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
-        B, M, H, S = ws["B"], ws["M"], self.H, self.S
+        B, M, H, S, FF = ws["B"], ws["M"], self.H, self.S, self.FF
         scale = 64 ** -0.5
         self.flat.bind_grads()
         x = ws["x"]
         dx, dxb = ws["dx"], ws["dxb"]
-        f16 = self.fp16
+        f16, ft = self.fp16, self.full_ft
         gs = self.FP16_GRAD_SCALE_LOG2 if f16 else None
         # head: dW = dout^T clsn, db = colsum(dout), dclsn = dout W  (fp16: dout enters 2^s up; db is summed from the f32 dout)
         if f16:
@@ -654,8 +687,9 @@ class ViTEngine(EncoderEngineBase):
         if not g16:
             dx.zero_()
         dxb.zero_()
-        ops.layernorm_bwd(x[-1].view(B, S * H)[:, :H], ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dclsn"],
-                          dx_f32=None if g16 else dx.view(B, S * H)[:, :H], dx_bf16=dxb.view(B, S * H)[:, :H])
+        dx_c, dxb_c = tok0(R, B), tok0(dxb, B)
+        self._ln_dw(tok0(x[-1], B), ws["st_f"], 0, "norm.w", "norm.b", g_gemm=ws["dclsn"])
+        ops.layernorm_bwd(tok0(x[-1], B), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dclsn"], dx_f32=None if g16 else dx_c, dx_bf16=dxb_c)
         L = len(self.layers)
         for l in range(L - 1, -1, -1):
             lay = self.layers[l]
@@ -663,28 +697,34 @@ class ViTEngine(EncoderEngineBase):
                 # Only token 0 of the last block feeds the head, so the residual gradient entering this block is zero
                 # on the other 196 rows of every image: its MLP backward, LN2 backward and proj backward run on the B
                 # token-0 rows only (row stride S*H), 1/197 of the work.
-                FF = self.FF
-                dxb_c = dxb.view(B, S * H)[:, :H]
                 probe("grad_stream", dxb_c)
+                self._dw(dxb_c, ws["act_c"], B, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
                 ops.gemm(dxb_c, lay.w_fc2_t, ws["dz_c"], EPI_DGELU_BF16, aux=ws["z_c"])
                 probe("dfc1_out", ws["dz_c"])
+                self._dw(ws["dz_c"], ws["h2_c"], B, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
                 ops.gemm(ws["dz_c"], lay.w_fc1_t, ws["dh_c"], EPI_BF16)
                 probe("dln2_out", ws["dh_c"])
-                dx_c = R.view(B, S * H)[:, :H]
-                ops.layernorm_bwd(x[2 * l + 1].view(B, S * H)[:, :H], ws["st_c"], lay.ln2[0], 0, g_resid=dx_c,
+                self._ln_dw(tok0(x[2 * l + 1], B), ws["st_c"], 0, f"{l}.n2.w", f"{l}.n2.b", g_gemm=ws["dh_c"])
+                ops.layernorm_bwd(tok0(x[2 * l + 1], B), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c,
                                   g_gemm=ws["dh_c"], dx_f32=None if g16 else dx_c, dx_bf16=dxb_c)
                 probe("grad_stream", dxb_c)
+                self._dw(dxb_c, tok0(ws["ctx"][l], B), B, H, H, f"{l}.proj.w", f"{l}.proj.b")
                 ws["dctx"].zero_()
-                ops.gemm(dxb_c, lay.w_proj_t, ws["dctx"].view(B, S * H)[:, :H], EPI_BF16)
+                ops.gemm(dxb_c, lay.w_proj_t, tok0(ws["dctx"], B), EPI_BF16)
             else:
+                h2, act = (ws["h2s"][l], ws["acts"][l]) if ft else (ws["h2"], ws["act"])   # the dW hooks' operands, as the forward chose them
                 probe("grad_stream", dxb)
+                self._dw(dxb, act, M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
                 ops.gemm(dxb, lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
                 probe("dfc1_out", ws["dz"])
+                self._dw(ws["dz"], h2, M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
                 ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
                 probe("dln2_out", ws["dh"])
+                self._ln_dw(x[2 * l + 1], ws["st2"][l], 0, f"{l}.n2.w", f"{l}.n2.b", g_gemm=ws["dh"])
                 ops.layernorm_bwd(x[2 * l + 1], ws["st2"][l], lay.ln2[0], 0, g_resid=R, g_gemm=ws["dh"],
                                   dx_f32=None if g16 else dx, dx_bf16=dxb)
                 probe("grad_stream", dxb)
+                self._dw(dxb, ws["ctx"][l], M, H, H, f"{l}.proj.w", f"{l}.proj.b")
                 ops.gemm(dxb, lay.w_proj_t, ws["dctx"], EPI_BF16)
             probe("dattn_out", ws["dctx"])
             lb = self.lora_b(l)
@@ -693,23 +733,16 @@ class ViTEngine(EncoderEngineBase):
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
                          q_rows=1 if l == L - 1 else 0, lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
             probe("dqkv", ws["dqkv"])
-            if lb is not None:
-                gb = self.lora_b(l, grad=True)
-                if self.fp8:
-                    ops.lora_grad_fp8(ws["dqkv"], ws["h1_8"][l], ws["t"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True),
-                                      gb[0], gb[1])
-                elif part:
-                    ops.lora_grad_heads(ws["h1"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1],
-                                        grad_scale_log2=gs)
-                else:
-                    ops.lora_grad(ws["dqkv"], ws["h1"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1])
-            if l > 0:  # nothing trainable sits below block 0 (patch-embed, cls, pos are frozen)
+            self._dw(ws["dqkv"], ws["h1"][l], M, 3 * H, H, f"{l}.qkv.w", f"{l}.qkv.b")
+            self._lora_grads(l, ws, ws["h1"][l], ws["h1_8"][l] if self.fp8 else None, part, gs)
+            if l > 0 or ft:  # LoRA regime: nothing trainable sits below block 0 (patch-embed, cls, pos are frozen)
                 ops.gemm(ws["dqkv"], lay.wqkv_t, ws["dh"], EPI_BF16)
                 probe("dln1_out", ws["dh"])
-                ops.layernorm_bwd(x[2 * l], ws["st1"][l], lay.ln1[0], 0, g_resid=R, g_gemm=ws["dh"],
-                                  dt=ws["dt"] if lb is not None else None,
-                                  lora_a=self.lora_a(l) if lb is not None else None, dx_f32=None if g16 else dx, dx_bf16=dxb)
-
+                dt, la = (ws["dt"], self.lora_a(l)) if lb is not None else (None, None)
+                self._ln_dw(x[2 * l], ws["st1"][l], 0, f"{l}.n1.w", f"{l}.n1.b", g_gemm=ws["dh"], dt=dt, lora_a=la)
+                ops.layernorm_bwd(x[2 * l], ws["st1"][l], lay.ln1[0], 0, g_resid=R, g_gemm=ws["dh"], dt=dt, lora_a=la,
+                                  dx_f32=None if g16 else dx, dx_bf16=dxb)
+        self._below_layer0(ws)
 
     def _backward_exact(self, dout):
         """BSCLIP_PARITY=2: the backward of ``_forward_exact`` with every gradient in f32 -- dX GEMMs on split operands against the
@@ -721,14 +754,13 @@ class ViTEngine(EncoderEngineBase):
         self.flat.bind_grads()
         self._ex_backward_weights()
         x, dx, a3 = ws["x"], ws["dx"], ws["a3"]
-        tok0 = lambda t, w: t.view(B, S * w)[:, :w]
         dout = dout.contiguous()
         self._ex_dw(dout, ws["cls32"], self.extra(0, grad=True), ws)            # cls32 = the final LayerNorm's f32 output
         ops.colsum(dout, B, self.out_dim, self.extra(1, grad=True))
         self._ex_gemm(dout, ops.split3_transpose(self.extra(0), ws["wheadT3"], 1), ws["dcls32"], EPI_F32, a3)
         dx.zero_()
-        dx_c = tok0(dx, H)
-        ops.layernorm_bwd(tok0(x[-1], H), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dcls32"], dx_f32=dx_c)
+        dx_c = tok0(dx, B)
+        ops.layernorm_bwd(tok0(x[-1], B), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dcls32"], dx_f32=dx_c)
         dx3 = False     # a3 holds the split of dx (written by the LayerNorm backward that produced dx: no split3_rows pass)
         for l in range(L - 1, -1, -1):
             lay = self.layers[l]
@@ -736,9 +768,9 @@ class ViTEngine(EncoderEngineBase):
                 self._ex_gemm(dx_c, lay.w3t[2], ws["g32"], EPI_F32, a3, M=B)
                 g3 = ops.dgelu_split3(ws["g32"], ws["z32s"][l], dst=a3, M=B)
                 ops.gemm(g3, lay.w3t[1], ws["dh32"], EPI_F32, M=B)
-                ops.layernorm_bwd(tok0(x[2 * l + 1], H), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c, g_gemm=ws["dh32"], dx_f32=dx_c, M=B)
+                ops.layernorm_bwd(tok0(x[2 * l + 1], B), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c, g_gemm=ws["dh32"], dx_f32=dx_c, M=B)
                 ws["dctx32"].zero_()
-                self._ex_gemm(dx_c, lay.w3t[0], tok0(ws["dctx32"], H), EPI_F32, a3, M=B)
+                self._ex_gemm(dx_c, lay.w3t[0], tok0(ws["dctx32"], B), EPI_F32, a3, M=B)
             else:
                 if dx3:
                     self._ex_gemm3(a3, lay.w3t[2], ws["g32"], EPI_F32, M)
@@ -1158,12 +1190,14 @@ class BertEngine(EncoderEngineBase):
         return out
 
     def backward(self, dout):
+        """The LoRA, fp8 and full fine-tuning backward (see ViTEngine.backward for the hooks)."""
         self._no_fp16_backward()
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
-        B, S, M, H, L = ws["B"], ws["S"], ws["M"], self.H, len(self.layers)
+        B, S, M, H, L, FF = ws["B"], ws["S"], ws["M"], self.H, len(self.layers), self.FF
         scale = 0.125
+        ft = self.full_ft
         self.flat.bind_grads()
         self._begin_dropout(ws, advance=False)   # backward runs on autograd's thread: the pointer is per thread
         gw, gb = self.extra(0, grad=True), self.extra(1, grad=True)
@@ -1172,8 +1206,10 @@ class BertEngine(EncoderEngineBase):
             ops.softmax_meanpool_bwd(ws["logits"], ws["sm"], dout, B, S, ws["dlog"])
             self._decoder_grads(ws, gw, gb)
             ops.gemm(ws["dlog"], self.w_head_t, ws["dtn"], EPI_BF16)                   # d tn
+            self._ln_dw(ws["tg"], ws["st_t"], 0, "lnt.w", "lnt.b", g_gemm=ws["dtn"])
             ops.layernorm_bwd(ws["tg"], ws["st_t"], self.ln_t[0], 0, g_gemm=ws["dtn"], dx_bf16=ws["dtg"])
             ops.dgelu_mul(ws["dtg"], ws["tz"], M, H, ws["dtg"])
+            self._dw(ws["dtg"], ws["yb"][L], M, H, H, "tr.w", "tr.b")
             ops.gemm(ws["dtg"], self.w_tr_t, ws["dh"], EPI_BF16)                       # d (last hidden state)
             g_resid, g_gemm = None, ws["dh"]
         else:
@@ -1189,37 +1225,38 @@ class BertEngine(EncoderEngineBase):
         g16 = ws["grad_bf16"]
         for l in range(L - 1, -1, -1):
             lay = self.layers[l]
+            ymb, act = (ws["ymbs"][l], ws["acts"][l]) if ft else (ws["ymb"], ws["act"])   # the dW hooks' operands, as the forward chose them
             # dsb is the operand of fc2's dX GEMM: it carries the mask fc2's forward output was dropped with.  With the bf16
             # gradient stream and no dropout the operand IS the residual gradient: one output, rewritten in place next time
             drop_b, drop_a = self._drop(ws, self.p_hidden, l, 3), self._drop(ws, self.p_hidden, l, 2)
             one_b, one_a = g16 and drop_b is None, g16 and drop_a is None
+            self._ln_dw(ws["s2"][l], ws["stb"][l], 1, f"{l}.lnb.w", f"{l}.lnb.b", g_resid=g_resid, g_gemm=g_gemm, dt=dt_in, lora_a=a_in)
             ops.layernorm_bwd(ws["s2"][l], ws["stb"][l], lay.ln_b[0], 1, g_resid=g_resid, g_gemm=g_gemm, dt=dt_in,
                               lora_a=a_in, dx_f32=None if one_b else ws["ds"], dx_bf16=ws["dsb"], dropout=drop_b)
+            self._dw(ws["dsb"], act, M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
             ops.gemm(ws["dsb"], lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
+            self._dw(ws["dz"], ymb, M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
             ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
-            ops.layernorm_bwd(ws["s1"][l], ws["sta"][l], lay.ln_a[0], 1, g_resid=ws["dsb"] if one_b else ws["ds"], g_gemm=ws["dh"],
+            r_a = ws["dsb"] if one_b else ws["ds"]
+            self._ln_dw(ws["s1"][l], ws["sta"][l], 1, f"{l}.lna.w", f"{l}.lna.b", g_resid=r_a, g_gemm=ws["dh"])
+            ops.layernorm_bwd(ws["s1"][l], ws["sta"][l], lay.ln_a[0], 1, g_resid=r_a, g_gemm=ws["dh"],
                               dx_f32=None if one_a else ws["ds1"], dx_bf16=ws["dsb"], dropout=drop_a)
+            self._dw(ws["dsb"], ws["ctx"][l], M, H, H, f"{l}.o.w", f"{l}.o.b")
             ops.gemm(ws["dsb"], lay.w_o_t, ws["dctx"], EPI_BF16)
-            drop_p = self._drop(ws, self.p_attn, l, 1)
+            drop_p = self._drop(ws, self.p_attn, l, 1)   # the forward left its keep decisions in ws["kbits"]
             lb = self.lora_b(l)
             kb = ws["kbits"][l] if drop_p is not None and ws["kbits"] is not None else None
             part = lb is not None and ATTN_LORA and not self.fp8 and (drop_p is None or kb is not None)
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
                          key_bias=ws["key_bias"], dropout=drop_p, keep_bits=kb,
                          lora=(ws["yb"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
-            if lb is not None:
-                gbb = self.lora_b(l, grad=True)
-                if self.fp8:
-                    ops.lora_grad_fp8(ws["dqkv"], ws["yb8"][l], ws["t"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True),
-                                      gbb[0], gbb[1])
-                elif part:
-                    ops.lora_grad_heads(ws["yb"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gbb[0], gbb[1])
-                else:
-                    ops.lora_grad(ws["dqkv"], ws["yb"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True), gbb[0], gbb[1])
-            if l > 0:  # embeddings are frozen: nothing to do below layer 0
+            self._dw(ws["dqkv"], ws["yb"][l], M, 3 * H, H, f"{l}.q.w", f"{l}.q.b", w_n=3 * H * H)   # q / k / v are adjacent
+            self._lora_grads(l, ws, ws["yb"][l], ws["yb8"][l] if self.fp8 else None, part)
+            if l > 0 or ft:  # LoRA regime: embeddings are frozen, nothing to do below layer 0
                 ops.gemm(ws["dqkv"], lay.wqkv_t, ws["dh"], EPI_BF16)
                 g_resid, g_gemm = (ws["dsb"] if one_a else ws["ds1"]), ws["dh"]
                 dt_in, a_in = (ws["dt"], self.lora_a(l)) if lb is not None else (None, None)
+        self._below_layer0(ws, g_resid, g_gemm, dt_in, a_in)
         ops.set_dropout_step(None)
 
 

@@ -3,22 +3,24 @@ config/model_config/full_fine_tuning/**) -- every parameter of the towers is tra
 LoRA branch and the ViT keeps LoRA on all blocks (the reference's own quirk: an empty ``lora_layer`` list is falsy in
 image_encoder.py:56-59 and means "all layers").
 
-The forward pass is the LoRA-regime one (same kernels; the bf16 operand copies of the weights are re-packed from the f32
-masters every step, and the inputs of fc1 / fc2 are kept per layer).  The backward pass adds, next to every dX GEMM, the
+This file holds the FT parameter layout, the per-step repacking of the operands and the gradient hooks; the kernel sequences,
+forward and backward, are the LoRA-regime engines' own (hip/engine.py).  The forward re-packs the bf16 operand copies of the
+weights from the f32 masters every step and keeps the inputs of fc1 / fc2 per layer.  The backward calls the hooks below for the
 gradients the LoRA regime never needs:
-  * Linear weights: dW = dY^T X on the same MFMA GEMM with both operands transposed (as the trainable heads always did),
-    accumulated in f32 into the flat gradient buffer; biases by ``bsclip_colsum``;
-  * LayerNorm gains / biases (``bsclip_ln_param_grad``), BertEmbeddings tables (``bsclip_embed_grad``), ViT patch filters
-    (``bsclip_gather_cast_rows`` + the dW GEMM), cls token and position table (ordered column sums);
-  * the dX chain continues through layer 0 into the embeddings.
+  * ``_dw``, in front of every dX GEMM -- Linear weights: dW = dY^T X on the same MFMA GEMM with both operands transposed (as the
+    trainable heads always did), accumulated in f32 into the flat gradient buffer; biases by ``bsclip_colsum``;
+  * ``_ln_dw``, in front of every LayerNorm backward -- gains / biases (``bsclip_ln_param_grad``);
+  * ``_below_layer0`` -- the dX chain continues through layer 0 into the embeddings: BertEmbeddings tables
+    (``bsclip_embed_grad``), ViT patch filters (``bsclip_gather_cast_rows`` + the dW GEMM), cls token and position table
+    (ordered column sums).
 All trainable tensors live in one flat f32 buffer per engine; q / k / v weights (and biases) of a BERT layer are adjacent in
 it, so the fused [3H, H] operand and its gradient are plain views.
 """
 import torch
 
-from . import engine, ops
-from .engine import BF16, F32, BertEngine, ViTEngine, split_plan
-from .lib import EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_RESID_F32, KPAD
+from . import ops
+from .engine import BF16, F32, BertEngine, ViTEngine, split_plan, tok0
+from .lib import EPI_RESID_F32
 
 
 class _FTMixin:
@@ -82,6 +84,11 @@ class _FTMixin:
         else:
             ops.gemm(tA, tB, gW, EPI_RESID_F32, resid=gW, K=Mp)
 
+    def _ln_dw(self, x, stats, mode, wname, bname, **grads):
+        """grad(gain), grad(bias) += ...; ``grads``: those of the following layernorm_bwd's g_resid / g_gemm / dt / lora_a / in_dropout
+        that pass through the normalisation (a pre-LN block's g_resid does not)."""
+        ops.ln_param_grad(x, stats, mode, self.tp(wname, grad=True), self.tp(bname, grad=True), **grads)
+
 
 # ============================================================================================================== ViT
 class ViTEngineFT(_FTMixin, ViTEngine):
@@ -131,75 +138,11 @@ class ViTEngineFT(_FTMixin, ViTEngine):
             ws["dyp"] = torch.empty(B * 196, self.H, dtype=BF16, device=self.device)   # patch rows of d x0, bf16
         return ws
 
-    def backward(self, dout):
-        ws = self.ws
-        B, M, H, S, FF = ws["B"], ws["M"], self.H, self.S, self.FF
-        scale = 64 ** -0.5
-        self.flat.bind_grads()
-        x = ws["x"]
-        dx, dxb = ws["dx"], ws["dxb"]
-        tok0 = lambda t, w: t.view(B, S * w)[:, :w]
-        # ---- head (trainable in both regimes) ----
-        ops.cast_f32_bf16(dout, ws["dout_bf"])
-        ops.transpose_bf16(ws["dout_bf"], B, self.out_dim, ws["dout_t"])
-        ops.transpose_bf16(ws["clsn"], B, H, ws["clsn_t"])
-        gw = self.extra(0, grad=True)
-        ops.gemm(ws["dout_t"], ws["clsn_t"], gw, EPI_RESID_F32, resid=gw)
-        ops.colsum(dout, B, self.out_dim, self.extra(1, grad=True))
-        ops.transpose_bf16(self.w_head_bf, self.out_dim, H, self.w_head_t)
-        ops.gemm(ws["dout_bf"], self.w_head_t, ws["dclsn"], EPI_BF16)
-        # ---- final norm on the token-0 rows ----
-        dx.zero_()
-        dxb.zero_()
-        ops.ln_param_grad(tok0(x[-1], H), ws["st_f"], 0, self.tp("norm.w", grad=True), self.tp("norm.b", grad=True),
-                          g_gemm=ws["dclsn"])
-        ops.layernorm_bwd(tok0(x[-1], H), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dclsn"], dx_f32=tok0(dx, H), dx_bf16=tok0(dxb, H))
-        L = len(self.layers)
-        for l in range(L - 1, -1, -1):
-            lay = self.layers[l]
-            n2w, n2b = self.tp(f"{l}.n2.w", grad=True), self.tp(f"{l}.n2.b", grad=True)
-            if l == L - 1:   # only token 0 of the last block carries gradient (see ViTEngine.backward)
-                dxb_c, dx_c = tok0(dxb, H), tok0(dx, H)
-                self._dw(dxb_c, ws["act_c"], B, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
-                ops.gemm(dxb_c, lay.w_fc2_t, ws["dz_c"], EPI_DGELU_BF16, aux=ws["z_c"])
-                self._dw(ws["dz_c"], ws["h2_c"], B, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
-                ops.gemm(ws["dz_c"], lay.w_fc1_t, ws["dh_c"], EPI_BF16)
-                ops.ln_param_grad(tok0(x[2 * l + 1], H), ws["st_c"], 0, n2w, n2b, g_gemm=ws["dh_c"])
-                ops.layernorm_bwd(tok0(x[2 * l + 1], H), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c, g_gemm=ws["dh_c"], dx_f32=dx_c,
-                                  dx_bf16=dxb_c)
-                self._dw(dxb_c, tok0(ws["ctx"][l], H), B, H, H, f"{l}.proj.w", f"{l}.proj.b")
-                ws["dctx"].zero_()
-                ops.gemm(dxb_c, lay.w_proj_t, tok0(ws["dctx"], H), EPI_BF16)
-            else:
-                self._dw(dxb, ws["acts"][l], M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
-                ops.gemm(dxb, lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
-                self._dw(ws["dz"], ws["h2s"][l], M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
-                ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
-                ops.ln_param_grad(x[2 * l + 1], ws["st2"][l], 0, n2w, n2b, g_gemm=ws["dh"])
-                ops.layernorm_bwd(x[2 * l + 1], ws["st2"][l], lay.ln2[0], 0, g_resid=dx, g_gemm=ws["dh"], dx_f32=dx, dx_bf16=dxb)
-                self._dw(dxb, ws["ctx"][l], M, H, H, f"{l}.proj.w", f"{l}.proj.b")
-                ops.gemm(dxb, lay.w_proj_t, ws["dctx"], EPI_BF16)
-            lb = self.lora_b(l)
-            part = lb is not None and engine.ATTN_LORA    # the LoRA regime's path: dt / dB partial sums out of the attention backward
-            ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"], q_rows=1 if l == L - 1 else 0,
-                         lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
-            self._dw(ws["dqkv"], ws["h1"][l], M, 3 * H, H, f"{l}.qkv.w", f"{l}.qkv.b")
-            if lb is not None:
-                gb = self.lora_b(l, grad=True)
-                if part:
-                    ops.lora_grad_heads(ws["h1"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1])
-                else:
-                    ops.lora_grad(ws["dqkv"], ws["h1"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True), gb[0], gb[1])
-            # the chain continues through block 0: patch filters, cls token and position table are trained too
-            ops.gemm(ws["dqkv"], lay.wqkv_t, ws["dh"], EPI_BF16)
-            dt, la = (ws["dt"], self.lora_a(l)) if lb is not None else (None, None)
-            ops.ln_param_grad(x[2 * l], ws["st1"][l], 0, self.tp(f"{l}.n1.w", grad=True), self.tp(f"{l}.n1.b", grad=True),
-                              g_gemm=ws["dh"], dt=dt, lora_a=la)
-            ops.layernorm_bwd(x[2 * l], ws["st1"][l], lay.ln1[0], 0, g_resid=dx, g_gemm=ws["dh"], dt=dt, lora_a=la, dx_f32=dx,
-                              dx_bf16=dxb)
-        # ---- d x0 [B, 197, H]: x0[b, 0] = cls + pos[0], x0[b, 1 + p] = patch_p W^T + b + pos[1 + p] ----
+    def _below_layer0(self, ws):
+        """d x0 [B, 197, H]: x0[b, 0] = cls + pos[0], x0[b, 1 + p] = patch_p W^T + b + pos[1 + p]."""
+        B, S, H, dx = ws["B"], self.S, self.H, ws["dx"]
         ops.colsum(dx.view(B, S * H), B, S * H, self.tp("pos", grad=True).view(-1))      # ordered sum over the batch
-        ops.colsum(tok0(dx, H), B, H, self.tp("cls", grad=True).view(-1))
+        ops.colsum(tok0(dx, B), B, H, self.tp("cls", grad=True).view(-1))
         ops.gather_cast_rows(dx, B * 196, S, 196, 1, ws["dyp"])
         self._dw(ws["dyp"], ws["cols"], B * 196, H, ws["cols"].shape[1], "patch.w", "patch.b")
 
@@ -266,74 +209,14 @@ class BertEngineFT(_FTMixin, BertEngine):
             ws["demb"] = torch.empty(B * S, self.H, dtype=F32, device=self.device)
         return ws
 
-    def backward(self, dout):
-        ws = self.ws
-        B, S, M, H, L, FF = ws["B"], ws["S"], ws["M"], self.H, len(self.layers), self.FF
-        scale = 0.125
-        self.flat.bind_grads()
-        self._begin_dropout(ws, advance=False)
-        gw, gb = self.extra(0, grad=True), self.extra(1, grad=True)
-        ops.transpose_bf16(self.w_head_bf, self.out_dim, self.head_in, self.w_head_t)
-        if self.head == "mlm_softmax_mean":
-            ops.softmax_meanpool_bwd(ws["logits"], ws["sm"], dout, B, S, ws["dlog"])
-            self._decoder_grads(ws, gw, gb)
-            ops.gemm(ws["dlog"], self.w_head_t, ws["dtn"], EPI_BF16)
-            ops.ln_param_grad(ws["tg"], ws["st_t"], 0, self.tp("lnt.w", grad=True), self.tp("lnt.b", grad=True), g_gemm=ws["dtn"])
-            ops.layernorm_bwd(ws["tg"], ws["st_t"], self.ln_t[0], 0, g_gemm=ws["dtn"], dx_bf16=ws["dtg"])
-            ops.dgelu_mul(ws["dtg"], ws["tz"], M, H, ws["dtg"])
-            self._dw(ws["dtg"], ws["yb"][L], M, H, H, "tr.w", "tr.b")
-            ops.gemm(ws["dtg"], self.w_tr_t, ws["dh"], EPI_BF16)
-            g_resid, g_gemm = None, ws["dh"]
-        else:
-            ops.cast_f32_bf16(dout, ws["dout_bf"])
-            ops.transpose_bf16(ws["dout_bf"], B, self.out_dim, ws["dout_t"])
-            ops.transpose_bf16(ws["mp"], B, H, ws["mp_t"])
-            ops.gemm(ws["dout_t"], ws["mp_t"], gw, EPI_RESID_F32, resid=gw)
-            ops.colsum(dout, B, self.out_dim, gb)
-            ops.gemm(ws["dout_bf"], self.w_head_t, ws["dmp"], EPI_F32)
-            ops.meanpool_tokens_bwd(ws["dmp"], B, S, ws["dyl"])
-            g_resid, g_gemm = ws["dyl"], None
-        dt_in, a_in = None, None
-        for l in range(L - 1, -1, -1):
-            lay = self.layers[l]
-            ops.ln_param_grad(ws["s2"][l], ws["stb"][l], 1, self.tp(f"{l}.lnb.w", grad=True), self.tp(f"{l}.lnb.b", grad=True),
-                              g_resid=g_resid, g_gemm=g_gemm, dt=dt_in, lora_a=a_in)
-            ops.layernorm_bwd(ws["s2"][l], ws["stb"][l], lay.ln_b[0], 1, g_resid=g_resid, g_gemm=g_gemm, dt=dt_in, lora_a=a_in,
-                              dx_f32=ws["ds"], dx_bf16=ws["dsb"], dropout=self._drop(ws, self.p_hidden, l, 3))
-            self._dw(ws["dsb"], ws["acts"][l], M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")   # dsb carries fc2's forward dropout mask
-            ops.gemm(ws["dsb"], lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
-            self._dw(ws["dz"], ws["ymbs"][l], M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
-            ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
-            ops.ln_param_grad(ws["s1"][l], ws["sta"][l], 1, self.tp(f"{l}.lna.w", grad=True), self.tp(f"{l}.lna.b", grad=True),
-                              g_resid=ws["ds"], g_gemm=ws["dh"])
-            ops.layernorm_bwd(ws["s1"][l], ws["sta"][l], lay.ln_a[0], 1, g_resid=ws["ds"], g_gemm=ws["dh"], dx_f32=ws["ds1"],
-                              dx_bf16=ws["dsb"], dropout=self._drop(ws, self.p_hidden, l, 2))
-            self._dw(ws["dsb"], ws["ctx"][l], M, H, H, f"{l}.o.w", f"{l}.o.b")
-            ops.gemm(ws["dsb"], lay.w_o_t, ws["dctx"], EPI_BF16)
-            drop_p = self._drop(ws, self.p_attn, l, 1)   # the forward (BertEngine.forward) left its keep decisions in ws["kbits"]
-            lb = self.lora_b(l)
-            kb = ws["kbits"][l] if drop_p is not None and ws["kbits"] is not None else None
-            part = lb is not None and engine.ATTN_LORA and (drop_p is None or kb is not None)
-            ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"], key_bias=ws["key_bias"],
-                         dropout=drop_p, keep_bits=kb, lora=(ws["yb"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
-            self._dw(ws["dqkv"], ws["yb"][l], M, 3 * H, H, f"{l}.q.w", f"{l}.q.b", w_n=3 * H * H)
-            if lb is not None:
-                gbb = self.lora_b(l, grad=True)
-                if part:
-                    ops.lora_grad_heads(ws["yb"][l], M, H, B, ws["dtp"], ws["dbp"], ws["dt"], self.lora_a(l, grad=True), gbb[0], gbb[1])
-                else:
-                    ops.lora_grad(ws["dqkv"], ws["yb"][l], M, H, lb, ws["dt"], self.lora_a(l, grad=True), gbb[0], gbb[1])
-            ops.gemm(ws["dqkv"], lay.wqkv_t, ws["dh"], EPI_BF16)
-            g_resid, g_gemm = ws["ds1"], ws["dh"]
-            dt_in, a_in = (ws["dt"], self.lora_a(l)) if lb is not None else (None, None)
-        # ---- embeddings: LayerNorm (its output was dropped in forward with site (-1, 0)) and the three tables ----
+    def _below_layer0(self, ws, g_resid, g_gemm, dt_in, a_in):
+        """The embedding LayerNorm (its output was dropped in forward with site (-1, 0)) and the three tables."""
         e_drop = self._drop(ws, self.p_hidden, -1, 0)
-        ops.ln_param_grad(ws["emb"], ws["st_e"], 1, self.tp("lne.w", grad=True), self.tp("lne.b", grad=True), g_resid=g_resid,
-                          g_gemm=g_gemm, dt=dt_in, lora_a=a_in, in_dropout=e_drop)
+        self._ln_dw(ws["emb"], ws["st_e"], 1, "lne.w", "lne.b", g_resid=g_resid, g_gemm=g_gemm, dt=dt_in, lora_a=a_in,
+                    in_dropout=e_drop)
         ops.layernorm_bwd(ws["emb"], ws["st_e"], self.ln_e[0], 1, g_resid=g_resid, g_gemm=g_gemm, dt=dt_in, lora_a=a_in,
                           dx_f32=ws["demb"], in_dropout=e_drop)
         ids = ws["ids"].contiguous()
         tt = ws["type_ids"]
         ops.embed_grad(ids, None if tt is None else tt.contiguous(), ws["demb"], self.tp("word", grad=True),
                        self.tp("posw", grad=True), self.tp("typew", grad=True), pad_id=self.pad_id)
-        ops.set_dropout_step(None)
