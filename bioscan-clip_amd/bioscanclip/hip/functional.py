@@ -1,4 +1,5 @@
-"""Autograd nodes for the two small ops outside the encoders: F.normalize and the contrastive loss."""
+"""Autograd nodes for the small ops outside the encoders: F.normalize, the contrastive loss and the supervised fine-tuning
+head (Linear + cross-entropy)."""
 import torch
 
 from . import ops
@@ -81,3 +82,151 @@ def infonce(zs, labels, scale, row0=0, n_local=None):
         raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
     ws = _workspace(zs[0].shape[0], len(zs), zs[0].device)
     return _InfoNCE.apply(labels.to(torch.int64).contiguous(), float(scale), row0, n_local, ws, *[z.to(F32) for z in zs])
+
+
+# ---- supervised fine-tuning head: Linear(768, C) + CrossEntropyLoss (reference util.py:13-25, fine_tuning_epoch.py:27) ----------
+HEAD_D = 768
+
+
+def _pad(n, m):
+    return (n + m - 1) // m * m
+
+
+class _HeadWorkspace:
+    """Scratch of one (B, C) head call: the split-bf16 operands of the three products and the padded logits.  Everything in here is
+    dead once the call that filled it returns (forward) or finishes (backward); what a backward needs from its forward -- dlogits
+    in both forms -- is allocated per call, because two classifiers of one (B, C) have their forwards queued before either backward."""
+
+    def __init__(self, B, C, device):
+        D = HEAD_D
+        self.Cn, self.Ck, self.Bp = _pad(C, 128), _pad(C, 64), _pad(B, 64)   # GEMM N, the dz product's K, the dW product's K
+        bf, f32 = torch.bfloat16, F32
+        self.z3 = torch.empty(B, 3 * D, dtype=bf, device=device)
+        # rows / elements [C, Cn) are never written: the GEMM forms logits for them that every reader masks out
+        self.w3 = torch.zeros(self.Cn, 3 * D, dtype=bf, device=device)
+        self.bias = torch.zeros(self.Cn, dtype=f32, device=device)
+        self.logits = torch.empty(B, self.Cn, dtype=f32, device=device)
+        self.row_loss = torch.empty(B, dtype=f32, device=device)
+        self.wT3 = torch.empty(D * 3 * self.Ck, dtype=bf, device=device)
+        self.zT3 = torch.empty(D * 3 * self.Bp, dtype=bf, device=device)
+        self.dT3 = torch.empty(C * 3 * self.Bp, dtype=bf, device=device)
+        # dW[C, 768] reduces over K = 3 Bp columns -- the hi.hi, lo.hi and hi.lo terms, Bp each: from four 64-wide K-tiles per term up
+        # each term is a K range (workgroup) of its own, unless that would be more than two rounds of workgroups over the chip
+        tiles = -(-C // 256) * (D // 256)
+        self.splits = 3 if self.Bp >= 256 and 3 * tiles <= 512 else 1
+        self.partial = torch.empty(self.splits * C * D, dtype=f32, device=device)
+        self.db = torch.empty(C, dtype=f32, device=device)
+
+
+_HEAD_WS = {}
+_CE_FLAG = {}
+
+
+def _head_workspace(B, C, device):
+    # one workspace per launching stream, as ops._lora_grad_workspace: classifiers may be driven from streams of their own
+    key = (B, C, str(device), torch.cuda.current_stream().cuda_stream)
+    ws = _HEAD_WS.get(key)
+    if ws is None:
+        ws = _HEAD_WS[key] = _HeadWorkspace(B, C, device)
+    return ws
+
+
+def ce_flag(device):
+    """The int32 device word ``linear_cross_entropy`` ORs its out-of-range-target bit into when the caller passes none."""
+    key = str(torch.device(device))
+    if key not in _CE_FLAG:
+        _CE_FLAG[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _CE_FLAG[key]
+
+
+def _head_inputs(z, weight, bias):
+    if not (z.is_cuda and weight.is_cuda and bias.is_cuda):
+        raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
+    if z.dim() != 2 or z.shape[1] != HEAD_D or weight.dim() != 2 or weight.shape[1] != HEAD_D or tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"classifier head: z [B, {HEAD_D}], weight [C, {HEAD_D}], bias [C] expected, got {tuple(z.shape)}, "
+                         f"{tuple(weight.shape)}, {tuple(bias.shape)}")
+    if weight.dtype != F32 or bias.dtype != F32 or not weight.is_contiguous() or not bias.is_contiguous():
+        raise ValueError("classifier head: weight and bias must be contiguous f32 (fp16 / fp8 operand modes are not built for the head)")
+    if z.shape[0] < 1 or weight.shape[0] < 1:
+        raise ValueError("classifier head: B >= 1 and C >= 1")
+
+
+def _head_logits(z, weight, bias, ws, out):
+    """out[:B, :Cn] = z W^T + b on the split-bf16 GEMM (hi.hi + lo.hi + hi.lo: ~2^-16 per product)."""
+    C = weight.shape[0]
+    ops.split3_rows(z, ws.z3)
+    ops.split3_weight(weight, ws.w3[:C])
+    ws.bias[:C].copy_(bias)
+    ops.gemm(ws.z3, ws.w3, out, epilogue=ops.EPI_F32, bias=ws.bias)
+
+
+def linear_logits(z, weight, bias):
+    """``F.linear(z, weight, bias)`` for the classifier head without autograd (evaluation): f32 [B, C], a view into a freshly
+    allocated padded buffer [B, C rounded up to 128] -- the layout ``ops.class_topk`` and ``ops.ce_fwd_bwd`` read."""
+    _head_inputs(z, weight, bias)
+    z = z.detach().to(F32).contiguous()
+    B, C = z.shape[0], weight.shape[0]
+    ws = _head_workspace(B, C, z.device)
+    out = torch.empty(B, ws.Cn, dtype=F32, device=z.device)
+    _head_logits(z, weight.detach(), bias.detach(), ws, out)
+    return out[:, :C]
+
+
+class _LinearCrossEntropy(torch.autograd.Function):
+    """``F.cross_entropy(F.linear(z, W, b), target)``: the forward forms the logits and, in one pass over them, the loss and
+    dlogits; the backward is the three products.  dW and db are accumulated in place into ``.grad`` (``None`` is returned for
+    them), as the encoders' nodes do; dz goes back through autograd."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, target, flag, ws):
+        B, C = z.shape[0], weight.shape[0]
+        _head_logits(z, weight, bias, ws, ws.logits)
+        loss = torch.empty(1, dtype=F32, device=z.device)
+        dl = dl3 = None
+        if any(ctx.needs_input_grad[:3]):
+            dl = torch.empty(B, ws.Cn, dtype=F32, device=z.device)
+            dl3 = torch.empty(B, 3 * ws.Ck, dtype=torch.bfloat16, device=z.device)
+        ops.ce_fwd_bwd(ws.logits, target, C, loss, ws.row_loss, dl, dl3, flag)
+        ctx.save_for_backward(z, weight)
+        ctx.dl, ctx.dl3, ctx.ws, ctx.bias = dl, dl3, ws, bias
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        z, weight = ctx.saved_tensors
+        dl, dl3, ws, bias = ctx.dl, ctx.dl3, ctx.ws, ctx.bias
+        B, C = z.shape[0], weight.shape[0]
+        dz = None
+        # the incoming scalar scales the small side of every product (as _InfoNCE.backward scales its stored gradients)
+        if ctx.needs_input_grad[0]:
+            wT3 = ops.split3_transpose(weight, ws.wT3, 1)                    # W^T as the B operand: [768, 3 Ck], [hi | hi | lo]
+            dz = torch.empty(B, HEAD_D, dtype=F32, device=z.device)
+            ops.gemm(dl3, wT3, dz, epilogue=ops.EPI_F32)
+            dz = dz * g
+        if ctx.needs_input_grad[1]:
+            if weight.grad is None:
+                weight.grad = torch.zeros_like(weight)
+            zT3 = ops.split3_transpose(z * g, ws.zT3, 1)                     # [768, 3 Bp], zeros in the padded rows' columns
+            dT3 = ops.split3_transpose(dl[:, :C], ws.dT3, 0)                 # dlogits^T: [C, 3 Bp], [hi | lo | hi]
+            ops.gemm_splitk_f32(dT3, zT3, weight.grad, ws.splits, ws.partial, K=3 * ws.Bp)
+        if ctx.needs_input_grad[2]:
+            if bias.grad is None:
+                bias.grad = torch.zeros_like(bias)
+            ws.db.zero_()
+            ops.colsum(dl, B, C, ws.db)
+            bias.grad.addcmul_(ws.db, g)
+        return dz, None, None, None, None, None
+
+
+def linear_cross_entropy(z, weight, bias, target, flag=None):
+    """Mean cross-entropy of ``z @ weight.T + bias`` against integer ``target`` [B] as one autograd node (the fused path of
+    ``EncoderWithExtraLayer.loss``).  No host synchronisation: a target outside [0, C) contributes zero loss and zero gradient and
+    sets bit 0 of ``flag`` (int32 [1] on the GPU; default: the per-device word ``ce_flag(device)``), which the caller reads when it
+    chooses to -- the epoch drivers do once per epoch."""
+    _head_inputs(z, weight, bias)
+    if target.dim() != 1 or target.shape[0] != z.shape[0] or target.dtype not in (torch.int32, torch.int64):
+        raise ValueError("linear_cross_entropy: target must be an integer tensor [B]")
+    z = z.to(F32).contiguous()
+    ws = _head_workspace(z.shape[0], weight.shape[0], z.device)
+    flag = ce_flag(z.device) if flag is None else flag
+    return _LinearCrossEntropy.apply(z, weight, bias, target.to(z.device, torch.int32).contiguous(), flag, ws)

@@ -720,6 +720,54 @@ def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=N
     return seen, right
 
 
+def check_ce_flag(word, what="target"):
+    """Raise for the error bit ``ce_fwd_bwd`` ORs into its flag word (``word``: its value on the host)."""
+    if word & 1:
+        raise ValueError(f"ce_fwd_bwd: a {what} index lies outside [0, C)")
+
+
+def ce_fwd_bwd(logits, targets, C, loss_out, row_loss, dlogits=None, dlogits_split3=None, flag=None):
+    """Mean cross-entropy of the class logits ``logits[:B, :C]`` (f32 [B, ldc >= C], a padded buffer) against ``targets`` (int32 [B]) into
+    ``loss_out`` (f32 [1]), and dlogits = (softmax - onehot) / B as f32 [B, >= C] (``dlogits``) and / or as the split-bf16 operand
+    [hi | lo | hi] over C rounded up to 64 columns (``dlogits_split3`` bf16 [B, >= 3 Cp]).  Without ``flag`` the error word is read
+    back here and a target outside [0, C) raises; with a caller's ``flag`` (int32 [1], cleared by the caller) nothing synchronises
+    and the caller runs ``check_ce_flag`` on it."""
+    ldc = _rowmajor(logits, "logits")
+    B = logits.shape[0]
+    dev = logits.device
+    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0, "ce_fwd_bwd: logits f32 [B, >= C], row stride % 4 == 0")
+    _req(targets.dtype == I32 and targets.is_contiguous() and targets.numel() == B and targets.device == dev, "ce_fwd_bwd: targets int32 [B]")
+    _req(loss_out.dtype == F32 and loss_out.numel() >= 1 and loss_out.device == dev, "ce_fwd_bwd: loss_out f32 [1]")
+    _req(row_loss.dtype == F32 and row_loss.is_contiguous() and row_loss.numel() >= B and row_loss.device == dev, "ce_fwd_bwd: row_loss f32 [B]")
+    Cp = (C + 63) // 64 * 64
+    ld_d = ld_d3 = 0
+    if dlogits is not None:
+        ld_d = _rowmajor(dlogits, "dlogits")
+        _req(dlogits.dtype == F32 and dlogits.shape[0] >= B and dlogits.shape[1] >= C and ld_d % 4 == 0, "ce_fwd_bwd: dlogits f32 [B, >= C]")
+    if dlogits_split3 is not None:
+        ld_d3 = _rowmajor(dlogits_split3, "dlogits_split3")
+        _req(dlogits_split3.dtype == BF16 and dlogits_split3.shape[0] >= B and dlogits_split3.shape[1] >= 3 * Cp and ld_d3 % 4 == 0,
+             "ce_fwd_bwd: dlogits_split3 bf16 [B, >= 3 x (C rounded up to 64)]")
+    flag, own = _eval_flag(flag, dev)
+    check(_l.load().bsclip_ce_fwd_bwd(_p(logits), ldc, _p(targets), B, C, _p(loss_out), _p(row_loss), _p(dlogits), ld_d,
+                                      _p(dlogits_split3), ld_d3, _p(flag), _stream()))
+    if own:
+        check_ce_flag(int(flag.item()))
+
+
+def class_topk(logits, C, k):
+    """The k (<= 16, <= C) largest of ``logits[:, :C]`` per row, descending, ties to the lower class index: (scores f32 [B, k],
+    indices int64 [B, k]) on the GPU.  ``logits`` f32 [B, >= C] may be a view into a padded buffer (row stride % 4 == 0)."""
+    ldc = _rowmajor(logits, "logits")
+    B = logits.shape[0]
+    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0, "class_topk: logits f32 [B, >= C], row stride % 4 == 0")
+    _req(1 <= k <= min(16, C), "class_topk: 1 <= k <= 16, k <= C")
+    scores = torch.empty(B, k, dtype=F32, device=logits.device)
+    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
+    check(_l.load().bsclip_class_topk(_p(logits), ldc, B, C, k, _p(scores), _p(idx), _stream()))
+    return scores, idx
+
+
 _LG_WS = {}
 
 

@@ -1,6 +1,44 @@
-"""Checkpoint helpers with the reference's names (bioscanclip/util/util.py:72-84).  The rest of the reference's util.py
-(result tables, plotting colours, faiss helper) is control plane and not rebuilt."""
+"""Checkpoint helpers with the reference's names (bioscanclip/util/util.py:72-84) and ``EncoderWithExtraLayer`` (:13-25), the
+species classifier of supervised fine-tuning.  The rest of the reference's util.py (result tables, plotting colours, faiss
+helper) is control plane and not rebuilt."""
 import torch
+import torch.nn as nn
+
+
+class EncoderWithExtraLayer(nn.Module):
+    """An encoder of a trained model with a new ``nn.Linear(768, C)`` on its output (reference util.py:13-25): same constructor,
+    same ``get_feature`` / ``forward`` signatures, same ``state_dict`` keys (``encoder.*``, ``new_linear_layer.weight`` / ``.bias``).
+
+    ``forward(x)`` returns the logits [B, C] from the HIP head (``hip.functional.linear_logits``); it carries no autograd graph,
+    so it serves evaluation.  Training goes through ``loss(x, target)``, the fast path: logits, cross-entropy and dlogits in one
+    fused call and the three backward products on the HIP GEMMs (``hip.functional.linear_cross_entropy``).  There is no torch
+    compute path: calling ``forward`` where a gradient would be recorded raises instead of silently training through ``nn.Linear``."""
+
+    def __init__(self, encoder, new_linear_layer):
+        super().__init__()
+        if not isinstance(new_linear_layer, nn.Linear) or new_linear_layer.bias is None:
+            raise NotImplementedError("EncoderWithExtraLayer: new_linear_layer must be an nn.Linear with a bias (the MLP + Softmax head of "
+                                      "SimpleCLIPWithClassificationHead is not built)")
+        self.encoder = encoder
+        self.new_linear_layer = new_linear_layer
+
+    def get_feature(self, x):
+        return self.encoder(x)
+
+    def forward(self, x):
+        from bioscanclip.hip import functional as HF
+        lin = self.new_linear_layer
+        if torch.is_grad_enabled() and (lin.weight.requires_grad or any(p.requires_grad for p in self.encoder.parameters())):
+            raise RuntimeError("EncoderWithExtraLayer.forward returns logits without an autograd graph: call it under torch.no_grad() "
+                               "(evaluation) and train through .loss(x, target), the fused HIP path")
+        return HF.linear_logits(self.encoder(x), lin.weight, lin.bias)
+
+    def loss(self, x, target, flag=None):
+        """Mean cross-entropy of the classifier on batch ``x`` against integer ``target`` [B]: the fused fast path (one autograd
+        node for the head).  ``flag``: see ``hip.functional.linear_cross_entropy``."""
+        from bioscanclip.hip import functional as HF
+        lin = self.new_linear_layer
+        return HF.linear_cross_entropy(self.encoder(x), lin.weight, lin.bias, target, flag=flag)
 
 
 def remove_extra_pre_fix(state_dict):

@@ -261,6 +261,27 @@ extern "C" int bsclip_topk_ip_indexed(const float* queries, int Q, const float* 
     return topk_search(queries, Q, reinterpret_cast<const bf16_t*>(index), K, D, k, scores_out, idx_out, workspace, stream);
 }
 
+// ---- top-k over class logits (supervised fine-tuning: evaluate_epoch's argsort(output, descending)[:, :max(k)]) ---------------
+// The selection kernel of the retrieval search on a logits matrix the caller owns: its 16-byte chunk loads need 16-byte aligned
+// rows (ldc % 4 == 0) and ldc >= C rounded up to 4, which ldc >= C and ldc % 4 == 0 give; columns >= C are masked.
+
+extern "C" int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* scores_out, int64_t* idx_out,
+                                 void* stream) {
+    BSCLIP_REQUIRE(logits && scores_out && idx_out, "bsclip_class_topk: null pointer");
+    BSCLIP_REQUIRE(B >= 1 && C >= 1, "bsclip_class_topk: B=%d C=%d (both >= 1)", B, C);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "bsclip_class_topk: k=%d (1..16, <= C=%d)", k, C);
+    BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "bsclip_class_topk: ldc=%d (>= C=%d, a multiple of 4)", ldc, C);
+    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)scores_out) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
+                   "bsclip_class_topk: logits must be 16-byte, scores_out 4-byte, idx_out 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k <= 8)
+        hipLaunchKernelGGL((topk_rows_kernel<8>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
+    else
+        hipLaunchKernelGGL((topk_rows_kernel<16>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
 // ---- scoring on integer label ids (make_prediction's label lookup + top_k_micro_accuracy / top_k_macro_accuracy counts) -------
 
 namespace {

@@ -413,6 +413,29 @@ int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int32_t* query_
                                   const int32_t* level_offsets, const int32_t* k_list, int nk, int32_t* seen, int32_t* right,
                                   int32_t* flag, void* stream);
 
+/* ---- supervised fine-tuning: species classifier on an encoder (util.EncoderWithExtraLayer) ----------------
+ * The head `new_linear_layer` (bioscanclip/util/util.py:13-25) is logits [B, C] = z W^T + b for any C >= 1.  It runs on
+ * bsclip_gemm_bf16 with split-bf16 operands (bsclip_split3_rows x bsclip_split3_weight, N = C padded to 128), so the logits
+ * live in a padded buffer [B, ldc]; both entry points read columns [0, C) only: a padded column is absent, not a logit of 0.
+ * ce_fwd_bwd: `criterion(output, target)` with nn.CrossEntropyLoss() (bioscanclip/epoch/fine_tuning_epoch.py:27,93) and its
+ *   autograd.  logits f32 [B, ldc] (ldc >= C, ldc % 4 == 0, 16-byte aligned), targets int32 [B].  Per row, in f32: the maximum
+ *   is subtracted first (logits of magnitude 1e4 are fine), row_loss[r] = log sum_c exp(x_c - max) + (max - x_target);
+ *   loss_out[0] = sum_r row_loss[r] / B, summed in a fixed order (no float atomics: eager and graph replay agree bit for bit).
+ *   dlogits = (softmax - onehot) / B goes out in the forms the backward products read, each nullable (both NULL: loss only):
+ *     dlogits        f32 [B, ld_d] (ld_d >= C, % 4, 16-byte aligned): columns [0, C) are written, the rest is left alone --
+ *                    bsclip_colsum makes db of it, bsclip_split3_transpose the operand of dW += dlogits^T z
+ *     dlogits_split3 bf16 [B, ld_d3 >= 3 Cp], Cp = C rounded up to 64, 8-byte aligned: [hi | lo | hi], Cp columns each, zeros
+ *                    in columns [C, Cp) -- the A operand of dz = dlogits W against bsclip_split3_transpose(W, order 1, Rp = Cp)
+ *   A target outside [0, C) is never used as an index: it ORs bit 0 into *flag (one int32 device word the caller clears, as for
+ *   bsclip_retrieval_hit_ranks) and its row gets loss 0 and a zero gradient; the divisor stays B.  row_loss f32 [B] is scratch
+ *   the caller owns (the per-row losses stay readable in it).
+ * class_topk: `torch.argsort(output, dim=1, descending=True)[:, :max(k_values)]` (fine_tuning_epoch.py:60): the k (<= 16,
+ *   <= C) largest of each row's C logits in descending order, scores_out f32 [B, k], idx_out int64 [B, k].  Ties resolve to the
+ *   lower class index.  Same layout requirements for logits as above. */
+int bsclip_ce_fwd_bwd(const float* logits, int ldc, const int32_t* targets, int B, int C, float* loss_out, float* row_loss,
+                      float* dlogits, int ld_d, void* dlogits_split3, int ld_d3, int32_t* flag, void* stream);
+int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* scores_out, int64_t* idx_out, void* stream);
+
 /* ---- RCCL collectives of the global-batch step ---------------------------------------------------
  * One process per GPU.  bsclip_comm_unique_id on rank 0 -> the caller ships the bsclip_comm_unique_id_bytes() bytes to the
  * other ranks (any channel) -> bsclip_comm_init on every rank (ncclCommInitRank).  The collectives run on `comm_stream`;
