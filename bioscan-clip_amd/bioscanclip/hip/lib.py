@@ -5,7 +5,7 @@ The library is built in-tree by ``__graft_entry__.build()`` / ``make -C bioscan-
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_void_p
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BSCLIP_LIB: another build of the same ABI (A/B experiments: `make -C bioscan-clip_amd/csrc exp`); never a non-HIP path
@@ -92,6 +92,9 @@ SIGNATURES = {
     "bsclip_topk_ip_indexed": (I, [P, I, P, I, I, I, P, P, P, P]),
     "bsclip_retrieval_hit_ranks": (I, [P, I, I, P, I, P, I, P, P, P]),
     "bsclip_retrieval_class_counts": (I, [P, P, I, I, P, P, I, P, P, P, P]),
+    "bsclip_retrieval_match_bits": (I, [P, I, I, P, I, P, I, P, I, I, P, P, P]),
+    "bsclip_retrieval_merge_hit_ranks": (I, [P, I, I, P, P, I, c_double, P, P]),
+    "bsclip_retrieval_threshold_sweep": (I, [P, I, I, P, P, I, I, I, P, I, P, P]),
     "bsclip_ce_fwd_bwd": (I, [P, I, P, I, I, P, P, P, I, P, I, P, P]),
     "bsclip_class_topk": (I, [P, I, I, I, I, P, P, P]),
     "bsclip_comm_unique_id_bytes": (I, []),

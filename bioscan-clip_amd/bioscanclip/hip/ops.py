@@ -669,7 +669,7 @@ def check_retrieval_flag(word):
     if word & 1:
         raise ValueError("retrieval_hit_ranks: an idx entry lies outside [0, K)")
     if word & 2:
-        raise ValueError("retrieval_class_counts: a query label lies outside its level's class range")
+        raise ValueError("retrieval_class_counts / retrieval_match_bits: a label lies outside its level's class range or the member table")
 
 
 def retrieval_hit_ranks(idx, key_labels, query_labels, flag=None):
@@ -718,6 +718,72 @@ def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=N
     if own:
         check_retrieval_flag(int(flag.item()))
     return seen, right
+
+
+def _masks(name, sim, A, B):
+    _req(sim.dim() == 2 and sim.dtype == F32 and sim.is_contiguous() and sim.is_cuda, f"{name}: sim f32 contiguous GPU [Q,k]")
+    Q, k = sim.shape
+    _req(A.dtype == I32 and B.dtype == I32 and A.is_contiguous() and B.is_contiguous() and A.dim() in (1, 2) and A.shape == B.shape
+         and A.shape[0] == Q and A.device == sim.device and B.device == sim.device,
+         f"{name}: A, B int32 contiguous [Q,L] (or [Q]) on sim's GPU")
+    L = A.shape[1] if A.dim() == 2 else 1
+    _req(Q >= 1 and 1 <= k <= 16 and 1 <= L <= 8, f"{name}: Q >= 1, 1 <= k <= 16, 1 <= L <= 8")
+    return Q, k, L
+
+
+def retrieval_match_bits(idx, key_labels, query_labels=None, member=None, level=0, flag=None):
+    """bits int32 [Q,L]: bit r set exactly when key_labels[idx[q,r], l] == query_labels[q,l].  With ``member`` (int32 0/1 [C]) the
+    member mask int32 [Q] of column ``level`` instead: bit r set exactly when member[key_labels[idx[q,r], level]] != 0.  ``flag`` as
+    for ``retrieval_hit_ranks``: an idx outside [0, K) or a label outside the member table sets its bit and is not read."""
+    _req(idx.dim() == 2 and idx.dtype == torch.int64 and idx.is_contiguous() and idx.is_cuda, "retrieval_match_bits: idx int64 GPU [Q,k]")
+    Q, k = idx.shape
+    dev = idx.device
+    _req(key_labels.dim() == 2 and key_labels.dtype == I32 and key_labels.is_contiguous() and key_labels.device == dev,
+         "retrieval_match_bits: key_labels int32 contiguous [K,L] on idx's GPU")
+    K, L = key_labels.shape
+    _req(Q >= 1 and K >= 1 and 1 <= k <= 16 and 1 <= L <= 8, "retrieval_match_bits: Q, K >= 1, 1 <= k <= 16, 1 <= L <= 8")
+    C = 0
+    if member is None:
+        _req(query_labels is not None and query_labels.dtype == I32 and query_labels.is_contiguous() and query_labels.device == dev
+             and tuple(query_labels.shape) == (Q, L), "retrieval_match_bits: query_labels int32 contiguous [Q,L] on idx's GPU")
+        bits = torch.empty(Q, L, dtype=I32, device=dev)
+    else:
+        _req(member.dim() == 1 and member.dtype == I32 and member.is_contiguous() and member.device == dev and member.numel() >= 1,
+             "retrieval_match_bits: member int32 contiguous [C] on idx's GPU")
+        _req(0 <= int(level) < L, "retrieval_match_bits: 0 <= level < L")
+        C, query_labels = member.numel(), None
+        bits = torch.empty(Q, dtype=I32, device=dev)
+    flag, own = _eval_flag(flag, dev)
+    check(_l.load().bsclip_retrieval_match_bits(_p(idx), Q, k, _p(key_labels), K, _p(query_labels), L, _p(member), C, int(level),
+                                                _p(bits), _p(flag), _stream()))
+    if own:
+        check_retrieval_flag(int(flag.item()))
+    return bits
+
+
+def retrieval_merge_hit_ranks(sim, A, B, threshold):
+    """hit_rank int32 (the shape of A): the lowest r < k with bit r of (A & s) | (B & ~s) set, or k, where bit r of s is
+    ``float64(sim[q,r]) > threshold`` (strict; a NaN similarity selects B)."""
+    Q, k, L = _masks("retrieval_merge_hit_ranks", sim, A, B)
+    hit_rank = torch.empty_like(A)
+    check(_l.load().bsclip_retrieval_merge_hit_ranks(_p(sim), Q, k, _p(A), _p(B), L, float(threshold), _p(hit_rank), _stream()))
+    return hit_rank
+
+
+def retrieval_threshold_sweep(sim, A, B, level, k_prime, thresholds, out=None):
+    """counts int32 [T]: per threshold (``thresholds`` float64 GPU [T]) the number of queries whose merged hit rank at ``level`` is
+    below ``k_prime``.  ``out``: a zeroed int32 [T] buffer the counts are added to (default: a fresh one)."""
+    Q, k, L = _masks("retrieval_threshold_sweep", sim, A, B)
+    _req(thresholds.dim() == 1 and thresholds.dtype == torch.float64 and thresholds.is_contiguous() and thresholds.device == sim.device
+         and thresholds.numel() >= 1, "retrieval_threshold_sweep: thresholds float64 contiguous [T] on sim's GPU")
+    T = thresholds.numel()
+    _req(0 <= int(level) < L and int(k_prime) >= 1, "retrieval_threshold_sweep: 0 <= level < L, k_prime >= 1")
+    if out is None:
+        out = torch.zeros(T, dtype=I32, device=sim.device)
+    _req(out.dtype == I32 and out.is_contiguous() and out.numel() == T and out.device == sim.device, "retrieval_threshold_sweep: out int32 [T]")
+    check(_l.load().bsclip_retrieval_threshold_sweep(_p(sim), Q, k, _p(A), _p(B), L, int(level), int(k_prime), _p(thresholds), T,
+                                                     _p(out), _stream()))
+    return out
 
 
 def check_ce_flag(word, what="target"):

@@ -355,6 +355,97 @@ __global__ __launch_bounds__(256) void class_counts_kernel(const int* __restrict
     }
 }
 
+
+// ---- method-one evaluation (reference scripts/method_one_eval.py): label matches as bit masks, the merge at a threshold, the sweep --
+
+constexpr int EVAL_SWEEP_CHUNK = 64;  // thresholds per block of the sweep (blockIdx.y)
+
+// The lane layout of hit_ranks_kernel, but the ballot itself is the output: bit r of bits[q, l] is set exactly when the level-l
+// label of key idx[q, r] equals the query's.  With a member table the only column read is `level` and bit r of bits[q] says
+// whether that label is listed (member[label] != 0); a label outside [0, C) is flagged and never used as an index.
+__global__ __launch_bounds__(256) void match_bits_kernel(const int64_t* __restrict__ idx, int Q, int k,
+                                                          const int* __restrict__ key_labels, int K,
+                                                          const int* __restrict__ query_labels, int L,
+                                                          const int* __restrict__ member, int C, int level,
+                                                          int* __restrict__ bits, int* __restrict__ flag) {
+    const int lane = threadIdx.x & 63, sub = lane >> 4, r = lane & 15;
+    const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool inq = q < Q && r < k;
+    const int64_t id = inq ? idx[(size_t)q * k + r] : 0;
+    const bool ok = inq && id >= 0 && id < K;
+    if (inq && !ok) atomicOr(flag, EVAL_FLAG_BAD_IDX);
+    if (member) {  // kernel-uniform
+        const int lab = ok ? key_labels[(size_t)id * L + level] : 0;
+        const bool inr = ok && lab >= 0 && lab < C;
+        if (ok && !inr) atomicOr(flag, EVAL_FLAG_BAD_LABEL);
+        const unsigned long long b = __ballot(inr && member[lab] != 0);
+        if (r == 0 && q < Q) bits[q] = (int)((unsigned)(b >> (sub * 16)) & 0xffffu);
+        return;
+    }
+    int kl[EVAL_MAX_LEVELS];
+#pragma unroll
+    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) kl[l] = (ok && l < L) ? key_labels[(size_t)id * L + l] : 0;
+#pragma unroll
+    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) {
+        if (l >= L) break;  // wave-uniform
+        const int ql = q < Q ? query_labels[(size_t)q * L + l] : 0;
+        const unsigned long long b = __ballot(ok && kl[l] == ql);
+        if (r == l && q < Q) bits[(size_t)q * L + l] = (int)((unsigned)(b >> (sub * 16)) & 0xffffu);
+    }
+}
+
+// bit r set exactly when slot r takes the seen-key prediction: (double)sim[q, r] > t, strict, false for a NaN
+__device__ __forceinline__ unsigned select_bits(const float* __restrict__ sim_row, int n, double t) {
+    unsigned s = 0;
+    for (int r = 0; r < n; ++r) s |= ((double)sim_row[r] > t ? 1u : 0u) << r;
+    return s;
+}
+
+// One lane per query: the selection mask of its k slots, then per level the lowest set bit of (A & s) | (B & ~s), or k.
+__global__ __launch_bounds__(256) void merge_hit_ranks_kernel(const float* __restrict__ sim, int Q, int k, const int* __restrict__ A,
+                                                               const int* __restrict__ B, int L, double t,
+                                                               int* __restrict__ hit_rank) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    const unsigned s = select_bits(sim + (size_t)q * k, k, t);
+    const unsigned low = (1u << k) - 1u;  // k <= 16
+    for (int l = 0; l < L; ++l) {
+        const unsigned a = (unsigned)A[(size_t)q * L + l], b = (unsigned)B[(size_t)q * L + l];
+        const unsigned m = ((a & s) | (b & ~s)) & low;
+        hit_rank[(size_t)q * L + l] = m ? __ffs(m) - 1 : k;
+    }
+}
+
+// Brute force over (query, threshold): blockIdx.x takes 256 queries, one per lane, blockIdx.y EVAL_SWEEP_CHUNK thresholds.  A lane
+// keeps its first kk = min(k', k) similarities as doubles and its two masks cut to kk bits; per threshold its count (0 or 1) is
+// summed over the wave with a ballot and lane 0 adds it to counts[j].  Integer atomics: the sums do not depend on their order.
+// `every` (k' > k): hit_rank <= k < k' holds for each query, whatever its masks.
+__global__ __launch_bounds__(256) void threshold_sweep_kernel(const float* __restrict__ sim, int Q, int k, const int* __restrict__ A,
+                                                               const int* __restrict__ B, int L, int level, int kk, bool every,
+                                                               const double* __restrict__ thr, int T, int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const unsigned low = (1u << kk) - 1u;  // kk <= 16
+    double s[16];
+    unsigned a = 0, b = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = (q < Q && r < kk) ? (double)sim[(size_t)q * k + r] : 0.0;
+    if (q < Q) {
+        a = (unsigned)A[(size_t)q * L + level] & low;
+        b = (unsigned)B[(size_t)q * L + level] & low;
+    }
+    const int j0 = blockIdx.y * EVAL_SWEEP_CHUNK;
+    const int j1 = j0 + EVAL_SWEEP_CHUNK < T ? j0 + EVAL_SWEEP_CHUNK : T;
+    for (int j = j0; j < j1; ++j) {  // block-uniform
+        const double t = thr[j];
+        unsigned sel = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sel |= (s[r] > t ? 1u : 0u) << r;  // slots >= kk hold 0.0 and are cut by a, b
+        const unsigned long long hit = __ballot(q < Q && (every || ((a & sel) | (b & ~sel)) != 0u));
+        if (lane == 0 && hit) atomicAdd(counts + j, __popcll(hit));
+    }
+}
+
 }  // namespace
 
 extern "C" int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K,
@@ -402,6 +493,58 @@ extern "C" int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int3
     }
     hipLaunchKernelGGL(class_counts_kernel, dim3(ceil_div(Q, 256), L), dim3(256), 0, s, hit_rank, query_labels, Q, L, cfg, nk,
                        seen, right, flag);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_retrieval_match_bits(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K,
+                                           const int32_t* query_labels, int L, const int32_t* member, int C, int level,
+                                           int32_t* bits, int32_t* flag, void* stream) {
+    BSCLIP_REQUIRE(idx && key_labels && bits && flag && (member || query_labels), "bsclip_retrieval_match_bits: null pointer");
+    BSCLIP_REQUIRE(Q > 0 && K > 0, "bsclip_retrieval_match_bits: Q=%d K=%d", Q, K);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_match_bits: k=%d (1..16)", k);
+    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_match_bits: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    if (member) {
+        BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_match_bits: level=%d (0 <= level < L=%d)", level, L);
+        BSCLIP_REQUIRE(C > 0, "bsclip_retrieval_match_bits: C=%d member entries", C);
+    }
+    BSCLIP_REQUIRE((((uintptr_t)idx) & 7) == 0 && ((((uintptr_t)key_labels) | ((uintptr_t)query_labels) | ((uintptr_t)member) |
+                                                    ((uintptr_t)bits) | ((uintptr_t)flag)) & 3) == 0,
+                   "bsclip_retrieval_match_bits: idx must be 8-B aligned, the int32 buffers 4-B aligned");
+    hipLaunchKernelGGL(match_bits_kernel, dim3(ceil_div(Q, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), idx, Q, k,
+                       key_labels, K, query_labels, L, member, C, level, bits, flag);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_retrieval_merge_hit_ranks(const float* sim, int Q, int k, const int32_t* A, const int32_t* B, int L,
+                                                double threshold, int32_t* hit_rank, void* stream) {
+    BSCLIP_REQUIRE(sim && A && B && hit_rank, "bsclip_retrieval_merge_hit_ranks: null pointer");
+    BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_merge_hit_ranks: Q=%d", Q);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_merge_hit_ranks: k=%d (1..16)", k);
+    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_merge_hit_ranks: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)hit_rank)) & 3) == 0,
+                   "bsclip_retrieval_merge_hit_ranks: sim and the int32 buffers must be 4-B aligned");
+    hipLaunchKernelGGL(merge_hit_ranks_kernel, dim3(ceil_div(Q, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), sim, Q, k, A,
+                       B, L, threshold, hit_rank);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_retrieval_threshold_sweep(const float* sim, int Q, int k, const int32_t* A, const int32_t* B, int L, int level,
+                                                int k_prime, const double* thresholds, int T, int32_t* counts, void* stream) {
+    BSCLIP_REQUIRE(sim && A && B && thresholds && counts, "bsclip_retrieval_threshold_sweep: null pointer");
+    BSCLIP_REQUIRE(Q > 0 && T > 0, "bsclip_retrieval_threshold_sweep: Q=%d T=%d", Q, T);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_threshold_sweep: k=%d (1..16)", k);
+    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_threshold_sweep: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_threshold_sweep: level=%d (0 <= level < L=%d)", level, L);
+    BSCLIP_REQUIRE(k_prime >= 1, "bsclip_retrieval_threshold_sweep: k_prime=%d (>= 1)", k_prime);
+    BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)counts)) & 3) == 0 &&
+                       (((uintptr_t)thresholds) & 7) == 0,
+                   "bsclip_retrieval_threshold_sweep: thresholds must be 8-B aligned, sim and the int32 buffers 4-B aligned");
+    const int kk = k_prime < k ? k_prime : k;  // the contract is hit_rank < k_prime: above k it holds for every query
+    hipLaunchKernelGGL(threshold_sweep_kernel, dim3(ceil_div(Q, 256), ceil_div(T, EVAL_SWEEP_CHUNK)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), sim, Q, k, A, B, L, level, kk, k_prime > k, thresholds, T, counts);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -1,0 +1,338 @@
+"""Method-one evaluation (reference scripts/method_one_eval.py): the seen / unseen protocol that ends in a harmonic mean.
+
+An image query is searched against the seen keys, image to image.  For each rank slot that prediction is kept only when its
+similarity is above a threshold; otherwise the slot takes the prediction of a search against the unseen keys, image to DNA.  The
+threshold is the one of ``np.linspace(0, 1, 1000)`` that maximises the harmonic mean of the seen and unseen top-1 species micro
+accuracy; the accuracy tables are then formed from the merged lists.
+
+Mirrored entry points (same names, argument meaning and return shapes as the reference; its function bodies are the specification
+-- the reference script itself does not import, it asks ``bioscanclip.util.dataset`` for a loader that does not exist):
+    inference_with_original_image_encoder_and_dna_encoder   :19-56
+    decide_prediction_with_threshold                        :59-84
+    get_final_pred_and_acc                                  :87-102
+    make_final_pred                                         :105-118
+    harmonic_mean                                           :121-128
+    search_threshold_with_harmonic_mean                     :131-157
+    get_all_unique_species_from_dataloader                  :160-167
+    method_1_inference_and_eval_for_seen_and_unseen         :170-239
+    print_acc_for_google_doc                                :242-262
+    check_for_acc_about_correct_predict_seen_or_unseen      :264-278
+    main                                                    :282-359
+
+``hip_eval=host`` (default) is the string-list arithmetic of the reference with the searches on the HIP top-k (``make_prediction``).
+``hip_eval=gpu`` keeps everything after the features on the GPU (``bioscanclip/hip/method_one.py``): both key indices are built once,
+label matches are bit masks, the 1 000 thresholds are one sweep launch per split, the tables come from integer class counts.  Its
+output dictionaries equal the host path's with ``==``; ``final_pred_labels`` holds strings only with ``with_predictions=True``
+(otherwise ``None``, and ``merged`` carries the GPU handle the membership check reads).
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from bioscanclip.epoch.inference_epoch import get_feature_and_label  # noqa: E402
+from bioscanclip.hip.method_one import harmonic_mean as _harmonic_mean  # noqa: E402
+from inference_and_eval import LEVELS, make_prediction, top_k_macro_accuracy, top_k_micro_accuracy  # noqa: E402
+
+K_LIST = None
+HIP_EVAL_MODES = ("host", "gpu")
+MAX_K = 5   # the search depth of both searches (:50, :54)
+
+
+def eval_mode(args):
+    """``hip_eval=host`` (default) or ``gpu``; anything else is refused (``inference_and_eval.select_eval``)."""
+    mode = str(getattr(args, "hip_eval", "host"))
+    if mode not in HIP_EVAL_MODES:
+        raise ValueError(f"hip_eval must be one of {HIP_EVAL_MODES}, not {mode!r}")
+    return mode
+
+
+def _k_list(args):
+    """``args.inference_and_eval_setting.k_list``; a configuration without the setting gets 1, 3, 5 (``inference_and_eval.main``)."""
+    ies = getattr(args, "inference_and_eval_setting", None)
+    return list(getattr(ies, "k_list", [1, 3, 5])) if ies is not None else [1, 3, 5]
+
+
+def _key_features(original_model, key_dataloaders, device, key_type):
+    feats, labels = [], []
+    for loader in key_dataloaders:
+        _, f, lab = get_feature_and_label(loader, original_model, device, type_of_feature=key_type, multi_gpu=False)
+        feats.append(f)
+        labels = labels + lab
+    return np.concatenate(feats, axis=0), labels
+
+
+def inference_with_original_image_encoder_and_dna_encoder(original_model, seen_query_dataloader, unseen_query_dataloader,
+                                                          key_dataloaders, device, key_type='dna'):
+    _, seen_q, seen_gt = get_feature_and_label(seen_query_dataloader, original_model, device, type_of_feature="image", multi_gpu=False)
+    _, unseen_q, unseen_gt = get_feature_and_label(unseen_query_dataloader, original_model, device, type_of_feature="image",
+                                                   multi_gpu=False)
+    keys, key_labels = _key_features(original_model, key_dataloaders, device, key_type)
+    seen_pred, seen_sim = make_prediction(seen_q, keys, key_labels, with_similarity=True, max_k=MAX_K)
+    unseen_pred, unseen_sim = make_prediction(unseen_q, keys, key_labels, with_similarity=True, max_k=MAX_K)
+    return seen_pred, seen_sim, seen_gt, unseen_pred, unseen_sim, unseen_gt
+
+
+def decide_prediction_with_threshold(args, pred_labels_from_image_classifier, confidence_score_or_similarity,
+                                     pred_labels_from_search, threshold):
+    final_pred_labels = []
+    for first, scores, second in zip(pred_labels_from_image_classifier, confidence_score_or_similarity, pred_labels_from_search):
+        merged = {}
+        for kth, score in enumerate(scores):
+            source = first if score > threshold else second          # strict; a NaN takes the second list
+            for level in source:
+                merged.setdefault(level, []).append(source[level][kth])
+        final_pred_labels.append(merged)
+    return final_pred_labels
+
+
+def get_final_pred_and_acc(args, pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
+                           pred_labels_from_search_with_unseen_keys, gt_labels, best_threshold=None):
+    final_pred_labels = decide_prediction_with_threshold(args, pred_labels_from_search_with_seen_keys,
+                                                         similarity_from_search_with_seen_keys,
+                                                         pred_labels_from_search_with_unseen_keys, best_threshold)
+    k_list = _k_list(args)
+    macro_acc, per_class_acc = top_k_macro_accuracy(final_pred_labels, gt_labels, k_list=k_list)
+    return {"final_pred_labels": final_pred_labels, "gt_labels": gt_labels, "best_threshold": best_threshold,
+            "micro_acc": top_k_micro_accuracy(final_pred_labels, gt_labels, k_list=k_list), "macro_acc": macro_acc,
+            "per_class_acc": per_class_acc}
+
+
+def make_final_pred(args, pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
+                    pred_labels_from_search_with_unseen_keys, gt_labels, threshold):
+    n = [len(pred_labels_from_search_with_seen_keys), len(similarity_from_search_with_seen_keys),
+         len(pred_labels_from_search_with_unseen_keys)]
+    if n[0] != n[1] != n[2]:   # the reference's chained comparison (:107-108), kept as it is
+        print(f"pred_labels_from_search_with_seen_keys: {n[0]}")
+        print(f"similarity_from_search_with_seen_keys: {n[1]}")
+        print(f"pred_labels_from_search_with_unseen_keys: {n[2]}")
+        sys.exit()
+    return decide_prediction_with_threshold(args, pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
+                                            pred_labels_from_search_with_unseen_keys, threshold), gt_labels
+
+
+def harmonic_mean(l):
+    return _harmonic_mean(l)
+
+
+def search_threshold_with_harmonic_mean(args, all_split_data, num_intervals=1000):
+    """Host path: every merged list is rebuilt for every threshold, as the reference does (no progress bar)."""
+    best_threshold, max_score = None, float('-inf')
+    k_list = _k_list(args)
+    for threshold in np.linspace(0, 1, num_intervals):
+        acc_list = []
+        for split in all_split_data:
+            final_pred_labels, gt_labels = make_final_pred(args, split['pred_labels_from_search_with_seen_keys'],
+                                                           split['pred_similarity_from_search_with_seen_keys'],
+                                                           split['pred_labels_from_search_with_unseen_keys'], split['gt_label'],
+                                                           threshold=threshold)
+            acc_list.append(top_k_micro_accuracy(final_pred_labels, gt_labels, k_list=k_list)[1]['species'])
+        score = harmonic_mean(acc_list)
+        if score > max_score:
+            max_score, best_threshold = score, threshold
+    return best_threshold
+
+
+def get_all_unique_species_from_dataloader(dataloader):
+    names = set()
+    for batch in dataloader:
+        names.update(batch[6]['species'])
+    return list(names)
+
+
+class MergedOnGpu:
+    """What the GPU path returns in place of the merged string lists: the split's GPU state, the threshold, and what is needed to
+    name things (``vocab``) or to build the strings after all (``strings()``)."""
+
+    def __init__(self, split, threshold, vocab, seen_key_labels, unseen_key_labels):
+        self.split, self.threshold, self.vocab = split, threshold, vocab
+        self.seen_key_labels, self.unseen_key_labels = seen_key_labels, unseen_key_labels
+
+    def strings(self):
+        from bioscanclip.hip.method_one import merged_predictions
+        return merged_predictions(self.split, self.threshold, self.seen_key_labels, self.unseen_key_labels)
+
+    def member_share(self, species_list, ks=(1, 3, 5)):
+        from bioscanclip.hip.method_one import member_share
+        listed = set(species_list)
+        table = np.asarray([int(name in listed) for name in self.vocab["species"]], dtype=np.int32)
+        return member_share(self.split, self.threshold, table, ks=ks, level="species")
+
+
+def _method_1_gpu(args, original_model, seen_query_dataloader, unseen_query_dataloader, seen_keys_dataloader,
+                  val_unseen_keys_dataloader, test_unseen_keys_dataloader, device, searched_threshold, with_predictions, num_intervals):
+    """The GPU path: features as on the host path, then both key indices built once, every split's two searches and its masks."""
+    seen_keys, seen_key_labels = _key_features(original_model, [seen_keys_dataloader], device, "image")
+    print()
+    unseen_keys, unseen_key_labels = _key_features(original_model, [val_unseen_keys_dataloader, test_unseen_keys_dataloader], device,
+                                                   "dna")
+    queries = [get_feature_and_label(loader, original_model, device, type_of_feature="image", multi_gpu=False)[1:]
+               for loader in (seen_query_dataloader, unseen_query_dataloader)]
+    return score_features_on_gpu(args, seen_keys, seen_key_labels, unseen_keys, unseen_key_labels, queries, searched_threshold,
+                                 with_predictions, num_intervals)
+
+
+def score_features_on_gpu(args, seen_keys, seen_key_labels, unseen_keys, unseen_key_labels, queries, searched_threshold=None,
+                          with_predictions=False, num_intervals=1000):
+    """The GPU path from features on: ``queries`` is ``[(image features, gt_labels)]``, one pair per split (seen queries, unseen
+    queries); the keys are the seen keys' image features and the unseen keys' DNA features with their label lists."""
+    from bioscanclip.hip.method_one import MethodOneSplit
+    from bioscanclip.hip.retrieval import Labels, RetrievalIndex, encode_labels
+    arrays, vocab = encode_labels(seen_key_labels, unseen_key_labels, *[gt for _, gt in queries], levels=LEVELS)
+    seen_index, unseen_index = RetrievalIndex(seen_keys), RetrievalIndex(unseen_keys)    # built once, shared by the splits
+    seen_ids, unseen_ids = Labels(arrays[0]), Labels(arrays[1])
+    splits = [MethodOneSplit.from_queries(seen_index, seen_ids, unseen_index, unseen_ids, feats, ids, max_k=MAX_K, levels=LEVELS)
+              for (feats, _), ids in zip(queries, arrays[2:])]
+    return score_splits_on_gpu(args, splits, [gt for _, gt in queries], vocab, seen_key_labels, unseen_key_labels, searched_threshold,
+                               with_predictions, num_intervals)
+
+
+def score_splits_on_gpu(args, splits, gt_labels, vocab, seen_key_labels, unseen_key_labels, searched_threshold=None,
+                        with_predictions=False, num_intervals=1000):
+    """Threshold search (unless given) and one output dictionary per ``MethodOneSplit``."""
+    from bioscanclip.hip.method_one import linspace_thresholds, merged_accuracy, pick_threshold, sweep
+    k_list = _k_list(args)
+    print("Searching best threshold.")
+    if searched_threshold is None:
+        if 1 not in k_list:
+            raise KeyError(1)     # the host path reads micro_acc[1] in its threshold search
+        thresholds = linspace_thresholds(num_intervals)
+        counts, totals = sweep(splits, thresholds, level="species", k=1)
+        best_threshold = pick_threshold(counts, totals, thresholds)
+    else:
+        best_threshold = searched_threshold
+    outputs = []
+    for split, gt in zip(splits, gt_labels):
+        acc, per_class = merged_accuracy(split, best_threshold, k_list, vocab)
+        merged = MergedOnGpu(split, best_threshold, vocab, seen_key_labels, unseen_key_labels)
+        outputs.append({"final_pred_labels": merged.strings() if with_predictions else None, "gt_labels": gt,
+                        "best_threshold": best_threshold, "micro_acc": acc["micro_acc"], "macro_acc": acc["macro_acc"],
+                        "per_class_acc": per_class, "merged": merged})
+    return tuple(outputs)
+
+
+def method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_query_dataloader, unseen_query_dataloader,
+                                                    seen_keys_dataloader, val_unseen_keys_dataloader, test_unseen_keys_dataloader,
+                                                    device, searched_threshold=None, with_predictions=False, num_intervals=1000):
+    """``(seen_output_dict, unseen_output_dict)``.  ``with_predictions`` and ``num_intervals`` are additions: the first matters on
+    the GPU path only (the host path always holds its string lists), the second is the grid size of the threshold search."""
+    if eval_mode(args) == "gpu":
+        return _method_1_gpu(args, original_model, seen_query_dataloader, unseen_query_dataloader, seen_keys_dataloader,
+                             val_unseen_keys_dataloader, test_unseen_keys_dataloader, device, searched_threshold, with_predictions,
+                             num_intervals)
+    (seen_pred_seen_keys, seen_sim, seen_gt, unseen_pred_seen_keys, unseen_sim,
+     unseen_gt) = inference_with_original_image_encoder_and_dna_encoder(original_model, seen_query_dataloader, unseen_query_dataloader,
+                                                                        [seen_keys_dataloader], device=device, key_type='image')
+    print()
+    seen_pred_unseen_keys, _, _, unseen_pred_unseen_keys, _, _ = inference_with_original_image_encoder_and_dna_encoder(
+        original_model, seen_query_dataloader, unseen_query_dataloader, [val_unseen_keys_dataloader, test_unseen_keys_dataloader],
+        device=device, key_type='dna')
+    return score_predictions_on_host(args, (seen_pred_seen_keys, seen_sim.tolist(), seen_pred_unseen_keys, seen_gt),
+                          (unseen_pred_seen_keys, unseen_sim.tolist(), unseen_pred_unseen_keys, unseen_gt), searched_threshold,
+                          num_intervals)
+
+
+def score_predictions_on_host(args, seen, unseen, searched_threshold=None, num_intervals=1000):
+    """The host path from predictions on: each of ``seen`` / ``unseen`` is (seen-key predictions, similarities as lists,
+    unseen-key predictions, ground truth)."""
+    data = [{'pred_labels_from_search_with_seen_keys': s[0], 'pred_similarity_from_search_with_seen_keys': s[1],
+             'pred_labels_from_search_with_unseen_keys': s[2], 'gt_label': s[3]} for s in (seen, unseen)]
+    print("Searching best threshold.")
+    if searched_threshold is None:
+        best_threshold = search_threshold_with_harmonic_mean(args, data, num_intervals=num_intervals)
+    else:
+        best_threshold = searched_threshold
+    return tuple(get_final_pred_and_acc(args, s[0], s[1], s[2], s[3], best_threshold=best_threshold) for s in (seen, unseen))
+
+
+def print_acc_for_google_doc(seen_output_dict, unseen_output_dict, K_LIST=None):
+    if K_LIST is None:
+        K_LIST = [1, 3, 5]
+    outputs = (seen_output_dict, unseen_output_dict)
+    for type_of_acc in ['micro_acc', 'macro_acc']:
+        for k in K_LIST:
+            values = [out[type_of_acc][k][level] for out in outputs for level in LEVELS]
+            means = [harmonic_mean([out[type_of_acc][k][level] for out in outputs]) for level in LEVELS]
+            print("".join(" " + str(round(v, 4)) for v in values + means))
+
+
+def check_for_acc_about_correct_predict_seen_or_unseen(final_pred_list, species_list):
+    """Prints, for k in 1, 3, 5, the share of records whose top-k species hold a name of ``species_list``.  ``final_pred_list`` is
+    the list of merged predictions, or the GPU path's ``merged`` handle (the same numbers from member masks)."""
+    if isinstance(final_pred_list, MergedOnGpu):
+        shares = final_pred_list.member_share(species_list)
+    else:
+        shares = {}
+        for k in [1, 3, 5]:
+            correct = sum(any(name in species_list for name in record['species'][:k]) for record in final_pred_list)
+            shares[k] = correct * 1.0 / len(final_pred_list)
+    for k in [1, 3, 5]:
+        print(f"for k = {k}: {shares[k]}")
+    return shares
+
+
+def _predictions_of(output_dict):
+    return output_dict["final_pred_labels"] if output_dict["final_pred_labels"] is not None else output_dict["merged"]
+
+
+def main(argv=None):
+    """Reference entry (:282-359): config -> ``load_clip_model`` -> checkpoint (unless ``model_config.load_ckpt`` is false) ->
+    threshold search and tables on the val splits -> the same threshold on the test splits.  The HDF5 splits are not available:
+    the seven splits (seen / val-unseen / test-unseen keys, seen and unseen val queries, seen and unseen test queries) come from
+    ``SyntheticEvalLoader`` with distinct seeds.  The reference's last membership check passes the test-unseen species list twice
+    (:358-359); here the unseen queries are checked against val + test unseen species in both places.  ``hip_eval=gpu`` (default
+    host) scores on the GPU.  Returns ``{"val": (seen, unseen), "test": (seen, unseen)}`` output dictionaries."""
+    from bioscanclip.model.simple_clip import load_clip_model
+    from bioscanclip.util.config import load_config
+    from bioscanclip.util.synthetic import SyntheticEvalLoader
+    from bioscanclip.util.util import load_checked, remove_extra_pre_fix
+    here = os.path.dirname(os.path.abspath(__file__))
+    args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
+    eval_mode(args)
+    mc = args.model_config
+    if getattr(mc, "for_open_clip", False):
+        raise NotImplementedError("the open_clip branch is not part of the HIP-accelerated path")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("method-one evaluation runs on one GPU")
+    if not torch.cuda.is_available():
+        raise RuntimeError("method_one_eval needs a ROCm GPU: the encoders and the top-k search run in libbsclip_hip.so")
+    global K_LIST
+    K_LIST = _k_list(args)
+    device = torch.device("cuda", 0)
+    print("Construct dataloader...")
+    bs, n = 40, int(getattr(args, "synthetic_eval_batches", 2))    # the reference evaluates at batch 40 (:295)
+    mk = lambda seed: SyntheticEvalLoader(bs, n, with_text=False, seed=seed)
+    seen_keys, val_unseen_keys, test_unseen_keys = mk(5301), mk(5302), mk(5303)
+    seen_val, unseen_val, seen_test, unseen_test = mk(5304), mk(5305), mk(5306), mk(5307)
+    original_model = load_clip_model(args, device)
+    if not (hasattr(mc, "load_ckpt") and mc.load_ckpt is False):
+        load_checked(original_model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
+    original_model.eval()
+
+    val = method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_val, unseen_val, seen_keys, val_unseen_keys,
+                                                          test_unseen_keys, device)
+    print_acc_for_google_doc(*val, K_LIST=K_LIST)
+    seen_species = get_all_unique_species_from_dataloader(seen_keys)
+    unseen_species = (get_all_unique_species_from_dataloader(val_unseen_keys)
+                      + get_all_unique_species_from_dataloader(test_unseen_keys))
+    print("For seen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(val[0]), seen_species)
+    print("For unseen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(val[1]), unseen_species)
+
+    test = method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_test, unseen_test, seen_keys, val_unseen_keys,
+                                                           test_unseen_keys, device, searched_threshold=val[0]['best_threshold'])
+    print_acc_for_google_doc(*test, K_LIST=K_LIST)
+    print("For seen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(test[0]), seen_species)
+    print("For unseen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(test[1]), unseen_species)
+    return {"val": val, "test": test}
+
+
+if __name__ == '__main__':
+    main()

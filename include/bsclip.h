@@ -412,6 +412,32 @@ int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, const int32_t* 
 int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int32_t* query_labels, int Q, int L,
                                   const int32_t* level_offsets, const int32_t* k_list, int nk, int32_t* seen, int32_t* right,
                                   int32_t* flag, void* stream);
+/* Method-one evaluation (scripts/method_one_eval.py): an image query is searched against the seen keys and against the unseen
+ * keys; rank slot r keeps the seen-key prediction when its similarity is above a threshold and takes the unseen-key one otherwise.
+ * On label ids the two prediction lists of a query are two bit masks per level, and the merge is (A & s) | (B & ~s).
+ *   match_bits: the label lookup of make_prediction and the `gt[level] in pred[level][:k]` of top_k_micro_accuracy, kept per
+ *     rank.  idx int64 [Q, k] (k <= 16), key_labels int32 [K, L], query_labels int32 [Q, L], L <= 8 -> bits int32 [Q, L]: bit r
+ *     is set exactly when key_labels[idx[q, r], l] == query_labels[q, l]; bits >= k are zero (ctz(bits), or k for 0, is the
+ *     hit_rank of bsclip_retrieval_hit_ranks).  With member != NULL (int32 0/1 [C]) it is the `single_pred in species_list` of
+ *     check_for_acc_about_correct_predict_seen_or_unseen (:264-278): bits int32 [Q], bit r set exactly when
+ *     member[key_labels[idx[q, r], level]] != 0; query_labels is not read and may be NULL.  flag as above: bit 0 for an idx
+ *     entry outside [0, K), bit 1 for a label outside [0, C); neither is dereferenced, its bit stays zero.
+ *   merge_hit_ranks: decide_prediction_with_threshold (:59-84) followed by the hit test.  sim f32 [Q, k], A / B int32 [Q, L] the
+ *     masks of the seen-key / unseen-key search.  s has bit r set exactly when (double)sim[q, r] > threshold -- strict, in
+ *     float64 as Python compares `similarity.tolist()` with np.linspace values, so a NaN takes the unseen-key prediction; no order
+ *     is assumed within a row.  hit_rank int32 [Q, L] = the lowest set bit below k of (A & s) | (B & ~s), or k: the contract of
+ *     bsclip_retrieval_hit_ranks, so bsclip_retrieval_class_counts applies unchanged.
+ *   threshold_sweep: the loop of search_threshold_with_harmonic_mean (:131-157) without the lists.  thresholds double [T] (DEVICE
+ *     memory, any order); counts int32 [T] (zeroed by the caller, added to): counts[j] += the number of queries whose merged
+ *     hit_rank at level `level` and threshold thresholds[j] is below k_prime (above k that is every query: clamp k_prime to k for
+ *     the meaning of `pred[:k_prime]`, as for class_counts).  Brute force
+ *     over (query, threshold); integer atomics only, so every run gives the same counts. */
+int bsclip_retrieval_match_bits(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K, const int32_t* query_labels,
+                                int L, const int32_t* member, int C, int level, int32_t* bits, int32_t* flag, void* stream);
+int bsclip_retrieval_merge_hit_ranks(const float* sim, int Q, int k, const int32_t* A, const int32_t* B, int L, double threshold,
+                                     int32_t* hit_rank, void* stream);
+int bsclip_retrieval_threshold_sweep(const float* sim, int Q, int k, const int32_t* A, const int32_t* B, int L, int level,
+                                     int k_prime, const double* thresholds, int T, int32_t* counts, void* stream);
 
 /* ---- supervised fine-tuning: species classifier on an encoder (util.EncoderWithExtraLayer) ----------------
  * The head `new_linear_layer` (bioscanclip/util/util.py:13-25) is logits [B, C] = z W^T + b for any C >= 1.  It runs on
