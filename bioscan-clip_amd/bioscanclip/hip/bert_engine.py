@@ -2,7 +2,7 @@
 (language_encoder.py:87-89)."""
 import torch
 
-from .engine import BertEngine, run_encoder, wants_fp8, wants_fp16, wants_full_ft
+from .engine import BertEngine, run_encoder
 
 
 def _need_gpu(t, who):
@@ -13,12 +13,12 @@ def _need_gpu(t, who):
 def barcode_bert_forward(module, ids):
     _need_gpu(ids, "LoRA_barcode_bert.forward")
     m = module.lora_barcode_bert
-    def build():
+    def build(mode, reuse_flat):
         heads = (m.cls.predictions.transform, m.cls.predictions.decoder)
-        if wants_full_ft(module):
+        if mode.full_ft:
             from .engine_ft import BertEngineFT
-            return BertEngineFT(m.bert, "mlm_softmax_mean", heads, ids.device)
-        return BertEngine(m.bert, "mlm_softmax_mean", heads, ids.device, fp8=wants_fp8(module), fp16=wants_fp16(module))
+            return BertEngineFT(m.bert, "mlm_softmax_mean", heads, ids.device, mode, reuse_flat)
+        return BertEngine(m.bert, "mlm_softmax_mean", heads, ids.device, mode, reuse_flat)
     # the reference passes input_ids only: token_type 0, no attention mask
     return run_encoder(module, build, (ids.to(torch.int64), None, None))
 
@@ -26,11 +26,11 @@ def barcode_bert_forward(module, ids):
 def bert_text_forward(module, x):
     ids = x["input_ids"]
     _need_gpu(ids, "LoRA_bert.forward")
-    def build():
-        if wants_full_ft(module):
+    def build(mode, reuse_flat):
+        if mode.full_ft:
             from .engine_ft import BertEngineFT
-            return BertEngineFT(module.lora_bert, "mean_proj", (module.proj,), ids.device)
-        return BertEngine(module.lora_bert, "mean_proj", (module.proj,), ids.device, fp16=wants_fp16(module))
+            return BertEngineFT(module.lora_bert, "mean_proj", (module.proj,), ids.device, mode, reuse_flat)
+        return BertEngine(module.lora_bert, "mean_proj", (module.proj,), ids.device, mode, reuse_flat)
     tt = x.get("token_type_ids")
     am = x.get("attention_mask")
     return run_encoder(module, build, (ids.to(torch.int64), None if tt is None else tt.to(torch.int64),

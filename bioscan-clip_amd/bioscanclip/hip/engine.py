@@ -14,6 +14,7 @@ Reference call shapes: SURVEY.md 2.3 (K1-K15), 3.2; semantics App. A.1-A.3.
 import itertools
 import os
 import zlib
+from collections import namedtuple
 
 import torch
 
@@ -24,6 +25,10 @@ from .lib import (EPI_BF16, EPI_DGELU_BF16, EPI_F32, EPI_GELU_BF16, EPI_GELU_FP8
 BF16 = torch.bfloat16
 F16 = torch.float16
 F32 = torch.float32
+# The six switches below (set_parity_mode assigns three of them) are the REQUEST: how the next engine should run.  No engine reads
+# them: it is built for one EngineMode -- wanted_mode(module): these switches and the module's hip_* attributes -- and keeps it as
+# ``engine.mode``.  _engine_for compares request and engine at every forward and rebuilds the engine when they differ; the flat
+# parameter / gradient buffer (FlatParams) of the old engine goes to the new one.
 # Residual-GRADIENT stream dtype of the LoRA-regime backward (the gradient that flows down the skip connections, read and
 # written by every LayerNorm backward): "bf16" halves its bytes (LN backward is HBM-bound: 16 -> 10-12 bytes per element);
 # the forward and the parameter gradients' f32 accumulation are unchanged.  "f32" restores round 2's behaviour.  Full
@@ -65,20 +70,29 @@ if os.environ.get("BSCLIP_PARITY", "0") in ("1", "2"):
     EXACT_FORWARD = os.environ.get("BSCLIP_PARITY") == "2"
 
 
+# Everything that shapes an engine: the six switches above, then the module's own requests (set_precision, set_operand_format, hip_full_ft)
+EngineMode = namedtuple("EngineMode", "grad_stream_bf16 resid_stream_bf16 patch_split exact attn_keep_bits attn_lora fp8 fp16 full_ft")
+
+
+def wanted_mode(module):
+    """The mode an engine of encoder ``module`` should have now."""
+    return EngineMode(GRAD_STREAM_BF16, RESID_STREAM_BF16, PATCH_SPLIT, EXACT_FORWARD, ATTN_KEEP_BITS, ATTN_LORA,
+                      wants_fp8(module), wants_fp16(module), wants_full_ft(module))
+
+
 def set_parity_mode(on, model=None):
-    """Switch at run time: 0 / False = default, 1 / True = f32 streams, 2 = the exact mode (f32 streams + the exact forward and
-    backward, csrc/exact.hip).  Engines built
-    afterwards pick it up; pass ``model`` to have its engines rebuilt at the next forward.  Returns the previous
+    """Change the request at run time: 0 / False = default, 1 / True = f32 streams, 2 = the exact mode (f32 streams + the exact
+    forward and backward, csrc/exact.hip).  An encoder whose engine was built for another mode gets a new engine at its next forward,
+    with or without ``model``; the flat parameter / gradient buffer carries over.  ``model``: drop its engines now.  Returns the previous
     (grad_stream_bf16, resid_stream_bf16) pair (restore with the module attributes; EXACT_FORWARD is reset by passing 0 / 1)."""
     global GRAD_STREAM_BF16, RESID_STREAM_BF16, EXACT_FORWARD
     prev = (GRAD_STREAM_BF16, RESID_STREAM_BF16)
     level = int(on)
     GRAD_STREAM_BF16 = RESID_STREAM_BF16 = level == 0
     EXACT_FORWARD = level == 2
-    if model is not None:
-        for m in model.modules():
-            if getattr(m, "_engine", None) is not None:
-                m._engine = None
+    for m in model.modules() if model is not None else ():
+        if getattr(m, "_engine", None) is not None:
+            _park_engine(m)
     return prev
 
 
@@ -116,16 +130,14 @@ def _anomaly_check(engine, phase, out=None):
             if count_nonfinite(t):
                 raise RuntimeError(f"{who} forward: non-finite values first appear in {name} (BSCLIP_DETECT_ANOMALY)")
         raise RuntimeError(f"{who} forward: non-finite values in the encoder output (BSCLIP_DETECT_ANOMALY)")
-    if getattr(engine, "fp16", False) and hasattr(engine, "backward_probes"):
-        # the fp16 backward's scaled gradient stream: an overflow there is the finding, whether or not it reached .grad
-        for name, t in engine.backward_probes():
-            if count_nonfinite(t):
-                raise RuntimeError(f"{who} backward: non-finite values in {name} (fp16 gradient scale 2^{engine.FP16_GRAD_SCALE_LOG2}; "
+    # the fp16 backward's scaled gradient stream: an overflow there is the finding, whether or not it reached .grad
+    for name, t in engine.backward_probes():
+        if count_nonfinite(t):
+            raise RuntimeError(f"{who} backward: non-finite values in {name} (fp16 gradient scale 2^{engine.FP16_GRAD_SCALE_LOG2}; "
                                    "BSCLIP_DETECT_ANOMALY)")
     if count_nonfinite(engine.flat.grad) == 0:
         return
-    owner = getattr(engine, "_owner", None)
-    names = {id(p): n for n, p in owner.named_parameters()} if owner is not None else {}
+    names = {id(p): n for n, p in engine._owner.named_parameters()} if engine._owner is not None else {}
     bad = [names.get(id(p), f"trainable tensor #{i}") for i, p in enumerate(engine.flat.params)
            if p.grad is not None and count_nonfinite(p.grad)]
     raise RuntimeError(f"{who} backward: non-finite gradient values in {', '.join(bad[:6])}"
@@ -227,14 +239,30 @@ def _pack_linear(lin, dev, h16=BF16, transposed=True):
 
 
 class _Layer:
-    pass
+    def __init__(self):   # one block's packed weights; the exact mode's split copies are made by its first forward / backward
+        self.qkv32 = self.wqkv3 = self.w3 = self.w3t = self.wqkvT3 = None
 
 
 class EncoderEngineBase:
-    """Shared pieces of the ViT and BERT engines: LoRA bookkeeping and the flat trainable buffer."""
+    """Shared pieces of the ViT and BERT engines: the mode, LoRA bookkeeping and the flat trainable buffer."""
 
-    def _setup_lora(self, qv_modules, H, dev, extra_params):
-        """qv_modules: per layer either None (no LoRA) or (A_q, A_v, B_q, B_v) nn.Linear modules."""
+    def __init__(self, mode, device):
+        self.mode, self.device = mode, device
+        self.full_ft = mode.full_ft
+        self.fp8 = mode.fp8 and not mode.full_ft     # full fine-tuning has no fp8 path
+        # fp16 operands: every frozen weight, the head weight's per-forward cast and the workspace's 16-bit buffers are IEEE fp16, the
+        # kernels get BSCLIP_OPERANDS_FP16.  The ViT trains on them; the BERT engines are inference-only.
+        self.fp16, self.h16 = mode.fp16, F16 if mode.fp16 else BF16
+        self.ws = None
+        # run_encoder: the owning module, its train / eval state, a count of forwards (_EncoderFn.backward checks that the saved
+        # activations are still its own); _engine_for: what the packed frozen weights were made from
+        self._owner, self.training, self._fwd_generation, self._frozen_sig = None, False, 0, None
+        self._waug_table = None        # refresh_lora_weights: device addresses of the K-augmentation columns, made at the first call
+        self._step_word = None         # BERT dropout: the device step counter, made by the first training-mode forward
+        self.w_tr3 = self.w_tr3t = None   # exact mode, MLM head: the transform weight's split and transposed split
+
+    def _setup_lora(self, qv_modules, H, dev, extra_params, reuse_flat):
+        """qv_modules: per layer either None (no LoRA) or (A_q, A_v, B_q, B_v) nn.Linear modules.  reuse_flat: the replaced engine's flat buffer, or None."""
         params = []
         self._lora_index = []
         for mods in qv_modules:
@@ -248,15 +276,12 @@ class EncoderEngineBase:
         self._trunk_index = len(params)
         params += list(self._trunk_trainables())   # full fine-tuning (hip/engine_ft.py): every trunk tensor, in its order
         ops.init_tables()
-        prev = _REUSE_FLAT[0] if _REUSE_FLAT else None
-        if (prev is not None and len(prev.params) == len(params) and all(p is q for p, q in zip(prev.params, params))
-                and prev.data.device.type == torch.device(dev).type and torch.device(dev).index in (None, prev.data.device.index)):
-            self.flat = prev   # an engine rebuilt for another operand format / frozen weights keeps the trained values and .grad
+        if (reuse_flat is not None and len(reuse_flat.params) == len(params) and all(p is q for p, q in zip(reuse_flat.params, params))
+                and reuse_flat.data.device.type == torch.device(dev).type and torch.device(dev).index in (None, reuse_flat.data.device.index)):
+            self.flat = reuse_flat   # an engine rebuilt for another mode / frozen weights keeps the trained values and .grad
         else:
             self.flat = FlatParams(params, dev)
         self._zero_a = torch.zeros(8, H, dtype=F32, device=dev)
-
-    full_ft = False
 
     def _trunk_trainables(self):
         return []
@@ -279,7 +304,7 @@ class EncoderEngineBase:
     def refresh_lora_weights(self):
         """LoRA-B into the K-augmentation columns of every layer's QKV weight: one launch over a table of device addresses (the
         weights and the flat parameter buffer live as long as the engine)."""
-        if getattr(self, "_waug_table", None) is None:
+        if self._waug_table is None:
             rows = [(lay.waug.data_ptr(), self.lora_b(l)[0].data_ptr(), self.lora_b(l)[1].data_ptr())
                     for l, lay in enumerate(self.layers) if self.lora_b(l) is not None]
             lds = {_lay.waug.stride(0) for _lay in self.layers}
@@ -321,16 +346,44 @@ class EncoderEngineBase:
     def _below_layer0(self, ws, *grads):
         """The embeddings' gradients, once the chain has passed layer 0."""
 
-    fp8 = False
-    fp16 = False
-    h16 = BF16
+    def _extend_workspace(self, ws):
+        """What a subclass adds to a workspace that ``_workspace`` has just built (hip/engine_ft.py); nothing here."""
 
-    def _set_format(self, fp16):
-        """fp16 operands (set_operand_format): every frozen weight the forward (and, for the ViT, the backward) reads, the head
-        weight's per-forward cast and the workspace's 16-bit buffers are IEEE fp16; the kernels get BSCLIP_OPERANDS_FP16.  The ViT
-        trains on them; the BERT engines are inference-only."""
-        self.fp16 = bool(fp16)
-        self.h16 = F16 if self.fp16 else BF16
+    def _keep_workspace(self, ws):
+        self._extend_workspace(ws)
+        self.ws = ws
+        return ws
+
+    def backward_probes(self):
+        """(name, tensor) of the fp16 backward's gradient buffers (BSCLIP_DETECT_ANOMALY); none unless the engine has that backward."""
+        return ()
+
+    # Static gradient scale of the fp16 backward (DESIGN.md 4, part 3a; profiles/r08_fp16_vit_training.jsonl): dL/dz of the head is
+    # multiplied by 2^s where it becomes the fp16 dout, so the whole gradient stream lives 2^s up, clear of fp16's subnormals; each
+    # trainable gradient is brought back by 2^-s (exact) before it is added into .grad.  s is the largest that leaves the largest
+    # scaled |gradient| of any site >= 2^4 under 65 504 at unit-sized cotangents (tests/test_20's: 1627 at s = 13, so 3254 at s = 14);
+    # a B = 256 InfoNCE step's cotangents are ~2^8 smaller (largest 6.9 at s = 13), and a share of its smallest values is subnormal.
+    FP16_GRAD_SCALE_LOG2 = 14
+
+    def _head_backward(self, ws, dout, pooled, pooled_t, dx, dx_epi):
+        """Backward of the trainable linear head out = pooled W^T + b over the B pooled rows: dW += dout^T pooled, db += colsum(dout),
+        dx = dout W through ``dx_epi``.  fp16: dout enters 2^s up, dW leaves the scale in ``gw_head``; db is summed from the f32 dout."""
+        B, N, K = ws["B"], self.out_dim, self.head_in
+        gw = self.extra(0, grad=True)
+        if self.fp16:
+            ops.cast_f32_f16_scaled(dout, ws["dout_bf"], self.FP16_GRAD_SCALE_LOG2)
+        else:
+            ops.cast_f32_bf16(dout, ws["dout_bf"])
+        ops.transpose_bf16(ws["dout_bf"], B, N, ws["dout_t"])
+        ops.transpose_bf16(pooled, B, K, pooled_t)
+        if self.fp16:
+            ops.gemm(ws["dout_t"], pooled_t, ws["gw_head"], EPI_F32)
+            ops.add_scaled_f32(ws["gw_head"], gw, -self.FP16_GRAD_SCALE_LOG2)
+        else:
+            ops.gemm(ws["dout_t"], pooled_t, gw, EPI_RESID_F32, resid=gw)
+        ops.colsum(dout, B, N, self.extra(1, grad=True))
+        ops.transpose_bf16(self.w_head_bf, N, K, self.w_head_t)
+        ops.gemm(ws["dout_bf"], self.w_head_t, dx, dx_epi)
 
     def _no_fp16_backward(self):
         if self.fp16:
@@ -339,7 +392,7 @@ class EncoderEngineBase:
 
     # ------------------------------------------------------------------------------ exact mode (BSCLIP_PARITY=2)
     def exact(self):
-        return EXACT_FORWARD and not self.fp8 and not self.full_ft
+        return self.mode.exact and not self.fp8 and not self.full_ft
 
     def _ex_weight(self, w_f32, lora=None):
         """[hi | hi | lo] rows of a frozen f32 weight (LoRA folded in f32 when given: refreshed by the caller every step)."""
@@ -376,10 +429,17 @@ class EncoderEngineBase:
         b = ops.split3_transpose(x, ws["t3b"], 1, R=M)
         ops.gemm(a, b, gw, EPI_RESID_F32, resid=gw)
 
+    def _ex_forward_weights(self):
+        """Split weights of the frozen Linears (once) and the f32 QKV master whose LoRA-folded split is refilled every step."""
+        for lay in self.layers:
+            if lay.w3 is None:
+                lay.qkv32, lay.wqkv3 = self._ex_weight(lay.src[0], lora=True)
+                lay.w3 = [self._ex_weight(w)[1] for w in lay.src[1:]]   # ViT: proj, fc1, fc2; BERT: attention output, intermediate, output
+
     def _ex_backward_weights(self):
         """Transposed split weights of the frozen Linears (once) and the buffer of the LoRA-folded QKV transpose (refilled every step)."""
         for lay in self.layers:
-            if not hasattr(lay, "w3t"):
+            if lay.w3t is None:
                 lay.w3t = [self._ex_weight_t(w) for w in lay.src[1:]]
                 lay.wqkvT3 = torch.empty(self.H * 9 * self.H, dtype=BF16, device=self.device)
 
@@ -398,19 +458,17 @@ class EncoderEngineBase:
 class ViTEngine(EncoderEngineBase):
     """LoRA ViT-B/16 forward/backward (reference image_encoder.py:15-109 over timm vit_base_patch16_224)."""
 
-    def __init__(self, module, device, fp8=False, fp16=False):
+    def __init__(self, module, device, mode, reuse_flat=None):
+        super().__init__(mode, device)
         vit = module.lora_vit
-        self.fp8 = bool(fp8)
-        self._set_format(fp16)
-        h16 = self.h16
-        self.device = dev = device
+        h16, dev = self.h16, device
         self.H = H = vit.blocks[0].norm1.weight.numel()
         self.heads = vit.blocks[0].attn.num_heads
         self.S = vit.pos_embed.shape[1]
         assert H == 768 and self.S == 197 and vit.patch_embed.proj.weight.shape[-1] == 16, \
             "HIP ViT engine is built for vit_base_patch16_224"
         self.w_patch = vit.patch_embed.proj.weight.detach().reshape(H, -1).to(dev, F32).to(h16).contiguous()
-        # split-bf16 patch embedding (PATCH_SPLIT): the weight as [hi | hi | lo] against im2col rows [hi | lo | hi] (fp16 parts in fp16 mode)
+        # split-bf16 patch embedding (mode.patch_split): the weight as [hi | hi | lo] against im2col rows [hi | lo | hi] (fp16 parts in fp16 mode)
         w32 = vit.patch_embed.proj.weight.detach().reshape(H, -1).to(dev, F32)
         w_hi = w32.to(h16)
         self.w_patch3 = torch.cat([w_hi, w_hi, (w32 - w_hi.to(F32)).to(h16)], dim=1).contiguous()
@@ -440,12 +498,11 @@ class ViTEngine(EncoderEngineBase):
             self.layers.append(lay)
         self.ln_f = (_f32(vit.norm.weight, dev), _f32(vit.norm.bias, dev))
         self.FF = self.layers[0].w_fc1.shape[0]
-        self.out_dim = vit.head.weight.shape[0]
+        self.out_dim, self.head_in = vit.head.weight.shape
         assert self.out_dim % 128 == 0, "head width must be a multiple of 128 for the HIP GEMM"
-        self._setup_lora(qv, H, dev, [vit.head.weight, vit.head.bias])
+        self._setup_lora(qv, H, dev, [vit.head.weight, vit.head.bias], reuse_flat)
         self.w_head_bf = torch.empty(self.out_dim, H, dtype=h16, device=dev)     # the head weight in the operand format, cast every forward
         self.w_head_t = torch.empty(H, self.out_dim, dtype=h16, device=dev)
-        self.ws = None
 
     # ------------------------------------------------------------------------------------------ workspace
     def _workspace(self, B):
@@ -456,10 +513,11 @@ class ViTEngine(EncoderEngineBase):
         h16 = self.h16     # the 16-bit operand buffers (and the 16-bit residual stream) are fp16 in an fp16 engine
         z = lambda *s, dt=h16: torch.empty(*s, dtype=dt, device=dev)
         ws = {"B": B, "M": M, "gen": next(_WS_GEN)}
-        ws["cols"] = z(B * 196, 3 * H if (PATCH_SPLIT and not self.full_ft) else H)
-        rb = ws["resid_bf16"] = RESID_STREAM_BF16 and not self.full_ft and not self.fp8
+        mode = self.mode
+        ws["cols"] = z(B * 196, 3 * H if (mode.patch_split and not self.full_ft) else H)
+        rb = ws["resid_bf16"] = mode.resid_stream_bf16 and not self.full_ft and not self.fp8
         if self.exact():
-            assert not rb and not GRAD_STREAM_BF16, "the exact forward runs on the f32 streams"
+            assert not rb and not mode.grad_stream_bf16, "the exact forward runs on the f32 streams"
             # per layer, all f32: LN1 output, q | k | v, attention output, fc1 pre-activation -- what the exact backward reads
             ws["y32s"], ws["ctx32s"] = [z(M, H, dt=F32) for _ in range(L)], [z(M, H, dt=F32) for _ in range(L)]
             ws["qkv32s"] = [z(M, 3 * H, dt=F32) for _ in range(L)]
@@ -494,7 +552,7 @@ class ViTEngine(EncoderEngineBase):
         ws["h2_c"], ws["act_c"], ws["z_c"], ws["st_c"] = z(B, H), z(B, FF), z(B, FF, dt=torch.uint8), z(B, 2, dt=F32)   # last-block token-0 path
         # backward temporaries (16-bit ones in the operand format: an fp16 engine's gradient stream and dX operands are fp16, in
         # units of the tower's static gradient scale 2^FP16_GRAD_SCALE_LOG2)
-        ws["grad_bf16"] = GRAD_STREAM_BF16 and not self.full_ft
+        ws["grad_bf16"] = mode.grad_stream_bf16 and not self.full_ft
         assert ws["grad_bf16"] or not self.fp16, "the fp16 backward runs on the 16-bit gradient stream"
         ws["dx"] = None if ws["grad_bf16"] else torch.zeros(M, H, dtype=F32, device=dev)
         ws["dxb"] = torch.zeros(M, H, dtype=h16, device=dev)
@@ -503,7 +561,7 @@ class ViTEngine(EncoderEngineBase):
         ws["dctx"] = z(M, H)
         ws["dqkv"] = z(M, 3 * H)
         ws["dt"] = z(M, 8, dt=F32)
-        ws["dtp"], ws["dbp"] = z(self.heads, 2, M, 4, dt=F32), z(B * self.heads, 2, 4, 64, dt=F32)   # LoRA partial sums (ATTN_LORA)
+        ws["dtp"], ws["dbp"] = z(self.heads, 2, M, 4, dt=F32), z(B * self.heads, 2, 4, 64, dt=F32)   # LoRA partial sums (mode.attn_lora)
         Bp = _pad64(B)
         ws["dout_bf"] = torch.zeros(B, self.out_dim, dtype=h16, device=dev)
         ws["dout_t"] = torch.zeros(self.out_dim, Bp, dtype=h16, device=dev)
@@ -512,15 +570,14 @@ class ViTEngine(EncoderEngineBase):
             ws["gw_head"] = torch.empty(self.out_dim, H, dtype=F32, device=dev)
         ws["dclsn"] = z(B, H)
         ws["dz_c"], ws["dh_c"] = z(B, FF), z(B, H)
-        self.ws = ws
-        return ws
+        return self._keep_workspace(ws)
 
     def backward_probes(self):
         """(name, tensor) of the backward's 16-bit gradient buffers (BSCLIP_DETECT_ANOMALY on an fp16 engine: the scaled gradient
         stream is where an fp16 overflow would show first).  What the last backward left in them: the shared temporaries hold
         block 0's values (the head's for dout)."""
         ws = self.ws
-        for name in ("dout_bf", "dxb", "dz", "dh", "dctx", "dqkv"):
+        for name in ("dout_bf", "dxb", "dz", "dh", "dctx", "dqkv") if self.fp16 else ():
             yield f"the fp16 backward's {name}", ws[name]
 
     def anomaly_probes(self):
@@ -547,10 +604,7 @@ class ViTEngine(EncoderEngineBase):
         B, H, S, M, L, FF = image.shape[0], self.H, self.S, ws["M"], len(self.layers), self.FF
         scale = 64 ** -0.5
         x, a3 = ws["x"], ws["a3"]
-        for lay in self.layers:
-            if not hasattr(lay, "w3"):
-                lay.qkv32, lay.wqkv3 = self._ex_weight(lay.src[0], lora=True)
-                lay.w3 = [self._ex_weight(w)[1] for w in lay.src[1:]]   # proj, fc1, fc2
+        self._ex_forward_weights()
         ops.im2col_patch16(image, ws["cols"])
         ops.gemm(ws["cols"], self.w_patch3, x[0], EPI_PATCH_F32, bias=self.b_patch, resid=self.pos)
         ops.vit_cls_rows(x[0], self.cls, self.pos, B, S, H)
@@ -638,12 +692,6 @@ class ViTEngine(EncoderEngineBase):
         return out
 
     # ------------------------------------------------------------------------------------------- backward
-    # Static gradient scale of the fp16 backward (part 3a; profiles/r08_fp16_vit_training.jsonl): dL/dz of the head is
-    # multiplied by 2^s where it becomes the fp16 dout, so the whole gradient stream lives 2^s up, clear of fp16's subnormals; each
-    # trainable gradient is brought back by 2^-s (exact) before it is added into .grad.  s is the largest that leaves the largest
-    # scaled |gradient| of any site >= 2^4 under 65 504 at unit-sized cotangents (tests/test_20's: 1627 at s = 13, so 3254 at s = 14);
-    # a B = 256 InfoNCE step's cotangents are ~2^8 smaller (largest 6.9 at s = 13), and a share of its smallest values is subnormal.
-    FP16_GRAD_SCALE_LOG2 = 14
     # measurement hook (tools/fp16_grad_scale.py, tests): a callable (site, tensor) called after each backward site writes its 16-bit
     # gradient -- it may read the tensor back (host sync), so only eager runs set it.  None: no calls.
     grad_probe = None
@@ -661,24 +709,9 @@ class ViTEngine(EncoderEngineBase):
         dx, dxb = ws["dx"], ws["dxb"]
         f16, ft = self.fp16, self.full_ft
         gs = self.FP16_GRAD_SCALE_LOG2 if f16 else None
-        # head: dW = dout^T clsn, db = colsum(dout), dclsn = dout W  (fp16: dout enters 2^s up; db is summed from the f32 dout)
-        if f16:
-            ops.cast_f32_f16_scaled(dout, ws["dout_bf"], gs)
-        else:
-            ops.cast_f32_bf16(dout, ws["dout_bf"])
+        self._head_backward(ws, dout, ws["clsn"], ws["clsn_t"], ws["dclsn"], EPI_BF16)
         probe = self.grad_probe or (lambda site, t: None)
-        probe("dout", ws["dout_bf"])
-        ops.transpose_bf16(ws["dout_bf"], B, self.out_dim, ws["dout_t"])
-        ops.transpose_bf16(ws["clsn"], B, H, ws["clsn_t"])
-        gw = self.extra(0, grad=True)
-        if f16:
-            ops.gemm(ws["dout_t"], ws["clsn_t"], ws["gw_head"], EPI_F32)
-            ops.add_scaled_f32(ws["gw_head"], gw, -gs)
-        else:
-            ops.gemm(ws["dout_t"], ws["clsn_t"], gw, EPI_RESID_F32, resid=gw)
-        ops.colsum(dout, B, self.out_dim, self.extra(1, grad=True))
-        ops.transpose_bf16(self.w_head_bf, self.out_dim, H, self.w_head_t)
-        ops.gemm(ws["dout_bf"], self.w_head_t, ws["dclsn"], EPI_BF16)
+        probe("dout", ws["dout_bf"])     # the head's scaled dout: still in its buffer
         # final norm on token-0 rows only: every other row of the residual gradient is zero
         # bf16 gradient stream (no dropout in the ViT): the bf16 operand buffer IS the residual gradient, read and rewritten
         # in place by each LayerNorm backward (same lane, same elements); the f32 copy does not exist
@@ -729,7 +762,7 @@ class ViTEngine(EncoderEngineBase):
             probe("dattn_out", ws["dctx"])
             lb = self.lora_b(l)
             # dt / dB partial sums out of the attention backward (the fp16 backward has this form only)
-            part = lb is not None and (ATTN_LORA or f16) and not self.fp8
+            part = lb is not None and (self.mode.attn_lora or f16) and not self.fp8
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
                          q_rows=1 if l == L - 1 else 0, lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
             probe("dqkv", ws["dqkv"])
@@ -802,11 +835,9 @@ class BertEngine(EncoderEngineBase):
       'mean_proj'        : mean over tokens -> proj Linear (text)
     """
 
-    def __init__(self, bert, head, head_modules, device, fp8=False, fp16=False):
-        self.fp8 = bool(fp8)
-        self._set_format(fp16)
-        h16 = self.h16
-        self.device = dev = device
+    def __init__(self, bert, head, head_modules, device, mode, reuse_flat=None):
+        super().__init__(mode, device)
+        h16, dev = self.h16, device
         cfg = getattr(bert, "config", None)
         emb = bert.embeddings
         self.H = H = emb.word_embeddings.weight.shape[1]
@@ -860,10 +891,9 @@ class BertEngine(EncoderEngineBase):
             trainable = [proj.weight, proj.bias]
             self.out_dim, self.head_in = proj.weight.shape
         assert self.out_dim % 128 == 0 and self.head_in % 128 == 0
-        self._setup_lora(qv, H, dev, trainable)
+        self._setup_lora(qv, H, dev, trainable, reuse_flat)
         self.w_head_bf = torch.empty(self.out_dim, self.head_in, dtype=h16, device=dev)   # the head weight in the operand format
         self.w_head_t = None if self.fp16 else torch.empty(self.head_in, self.out_dim, dtype=BF16, device=dev)
-        self.ws = None
 
     def _workspace(self, B, S):
         if self.ws is not None and self.ws["B"] == B and self.ws["S"] == S:
@@ -875,7 +905,8 @@ class BertEngine(EncoderEngineBase):
         ws = {"B": B, "S": S, "M": M, "gen": next(_WS_GEN)}
         ws["emb"] = z(M, H, dt=F32)
         ws["yb"] = [z(M, H + KPAD) for _ in range(L + 1)]   # LN outputs feeding each layer's QKV GEMM (+ LoRA t)
-        rb = ws["resid_bf16"] = RESID_STREAM_BF16 and not self.full_ft and not self.fp8
+        mode = self.mode
+        rb = ws["resid_bf16"] = mode.resid_stream_bf16 and not self.full_ft and not self.fp8
         sdt = h16 if rb else F32
         ws["y"] = z(M, H, dt=F32)                           # f32 copy of the current layer input (residual; bf16 stream: head input only)
         ws["ym"] = None if rb else z(M, H, dt=F32)
@@ -884,9 +915,9 @@ class BertEngine(EncoderEngineBase):
         ws["ctx"] = [z(M, H) for _ in range(L)]
         ws["lse"] = [z(B, self.heads, S, dt=F32) for _ in range(L)]
         # attention-probs dropout: the forward leaves its keep decisions (1 bit per probability, 32 B per query row) for the backward,
-        # which otherwise re-hashes every element (BSCLIP_ATTN_KEEP_BITS=0: the re-hashing form, same masks); 64 B per query row
+        # which otherwise re-hashes every element (mode.attn_keep_bits off: the re-hashing form, same masks); 64 B per query row
         ws["kbits"] = ([torch.zeros(B * self.heads * S * ops.KEEP_WORDS, dtype=torch.int32, device=dev) for _ in range(L)]
-                       if self.p_attn > 0.0 and ATTN_KEEP_BITS and not self.exact() and not self.fp16 else None)
+                       if self.p_attn > 0.0 and mode.attn_keep_bits and not self.exact() and not self.fp16 else None)
         ws["s1"] = [z(M, H, dt=sdt) for _ in range(L)]      # pre-LN sums (LN backward inputs)
         ws["s2"] = [z(M, H, dt=sdt) for _ in range(L)]
         ws["sta"] = [z(M, 2, dt=F32) for _ in range(L)]
@@ -902,7 +933,7 @@ class BertEngine(EncoderEngineBase):
             ws["t"] = [z(M, KPAD) for _ in range(L)]
             ws["ymb8"], ws["act8"] = z(M, H, dt=ops.FP8), z(M, FF, dt=ops.FP8)
         if self.exact():
-            assert not rb and not GRAD_STREAM_BF16, "the exact forward runs on the f32 streams"
+            assert not rb and not mode.grad_stream_bf16, "the exact forward runs on the f32 streams"
             # per layer, all f32: the layer input (ys[l]; ys[L] = the last hidden state), q | k | v, attention output, intermediate
             # pre-activation -- what the exact backward reads
             ws["ys"] = [ws["y"]] + [z(M, H, dt=F32) for _ in range(L)]
@@ -926,11 +957,10 @@ class BertEngine(EncoderEngineBase):
                 ws["st_t"], ws["logits"], ws["sm"] = z(M, 2, dt=F32), z(M, self.out_dim, dt=F32), z(M, 2, dt=F32)
             else:
                 ws["mp"], ws["mp32"] = z(B, H), z(B, H, dt=F32)
-            self.ws = ws
-            return ws
+            return self._keep_workspace(ws)
         # backward temporaries
-        ws["grad_bf16"] = GRAD_STREAM_BF16 and not self.full_ft
-        gdt = BF16 if ws["grad_bf16"] else F32       # residual-gradient stream (see GRAD_STREAM_BF16)
+        ws["grad_bf16"] = mode.grad_stream_bf16 and not self.full_ft
+        gdt = BF16 if ws["grad_bf16"] else F32       # residual-gradient stream (mode.grad_stream_bf16)
         ws["ds"] = z(M, H, dt=gdt)
         ws["dsb"] = z(M, H)
         ws["ds1"] = z(M, H, dt=gdt)
@@ -939,7 +969,7 @@ class BertEngine(EncoderEngineBase):
         ws["dctx"] = z(M, H)
         ws["dqkv"] = z(M, 3 * H)
         ws["dt"] = z(M, 8, dt=F32)
-        ws["dtp"], ws["dbp"] = z(self.heads, 2, M, 4, dt=F32), z(B * self.heads, 2, 4, 64, dt=F32)   # LoRA partial sums (ATTN_LORA)
+        ws["dtp"], ws["dbp"] = z(self.heads, 2, M, 4, dt=F32), z(B * self.heads, 2, 4, 64, dt=F32)   # LoRA partial sums (mode.attn_lora)
         if self.head == "mlm_softmax_mean":
             ws["head_splits"], Mp = split_plan(M, self.out_dim, H)
             if ws["head_splits"] > 1:
@@ -963,8 +993,7 @@ class BertEngine(EncoderEngineBase):
             ws["mp_t"] = torch.zeros(H, Bp, dtype=BF16, device=dev)
             ws["dmp"] = z(B, H, dt=F32)
             ws["dyl"] = z(M, H, dt=F32)
-        self.ws = ws
-        return ws
+        return self._keep_workspace(ws)
 
     def _decoder_grads(self, ws, gw, gb):
         """dW_dec += dlogits^T tn (reduced over all B*S tokens: split-K, the [768, 768] output alone is 9 tiles) and db_dec += column
@@ -990,7 +1019,7 @@ class BertEngine(EncoderEngineBase):
         if not (ws["train"] and (self.p_hidden > 0.0 or self.p_attn > 0.0)):
             ops.set_dropout_step(None)
             return
-        if getattr(self, "_step_word", None) is None:
+        if self._step_word is None:
             self._step_word = torch.zeros(1, dtype=torch.int32, device=self.device)
         if advance:
             ops.counter_add(self._step_word, 1)
@@ -1014,10 +1043,7 @@ class BertEngine(EncoderEngineBase):
         the default path; what ``_backward_exact`` reads stays resident in f32."""
         B, S, M, H, L, FF = ws["B"], ws["S"], ws["M"], self.H, len(self.layers), self.FF
         a3, ys = ws["a3"], ws["ys"]
-        for lay in self.layers:
-            if not hasattr(lay, "w3"):
-                lay.qkv32, lay.wqkv3 = self._ex_weight(lay.src[0], lora=True)
-                lay.w3 = [self._ex_weight(w)[1] for w in lay.src[1:]]   # attention output, intermediate, output
+        self._ex_forward_weights()
         for l, lay in enumerate(self.layers):
             has = self._lora_index[l] is not None
             qkv32, ctx32, z32 = ws["qkv32s"][l], ws["ctx32s"][l], ws["z32s"][l]
@@ -1036,7 +1062,7 @@ class BertEngine(EncoderEngineBase):
         out = torch.empty(B, self.out_dim, dtype=F32, device=self.device)
         ops.split3_weight(self.extra(0), ws["whead3"])
         if self.head == "mlm_softmax_mean":
-            if not hasattr(self, "w_tr3"):
+            if self.w_tr3 is None:
                 self.w_tr3 = self._ex_weight(self.src_tr)[1]
             self._ex_gemm(ys[L], self.w_tr3, ws["tz32"], EPI_F32, a3, bias=self.b_tr)
             ops.gelu_split3(ws["tz32"], None, g32=ws["t32"])                                # the GELU feeds a LayerNorm: f32 out
@@ -1062,7 +1088,7 @@ class BertEngine(EncoderEngineBase):
         dout = dout.contiguous()
         wt_head = ops.split3_transpose(self.extra(0), ws["wheadT3"], 1)
         if self.head == "mlm_softmax_mean":
-            if not hasattr(self, "w_tr3t"):
+            if self.w_tr3t is None:
                 self.w_tr3t = self._ex_weight_t(self.src_tr)
             ops.softmax_meanpool_bwd_f32(ws["logits"], ws["sm"], dout, B, S, ws["dlog32"])
             self._ex_dw(ws["dlog32"], ws["tn32"], gw, ws)
@@ -1111,7 +1137,7 @@ class BertEngine(EncoderEngineBase):
         scale = 0.125
         # HF BERT dropout (hidden 0.1 / attention-probs 0.1) is active in train mode (reference train_epoch.py:20);
         # masks are functions of (seed, element index), regenerated in backward from the seeds kept here
-        ws["train"] = bool(getattr(self, "training", False))
+        ws["train"] = bool(self.training)
         # the rank is mixed in: ranks seeded alike (bench.py, train_cl.py) must not draw the same masks for their shards
         # ... and the engine (its head kind): the DNA and text towers share layer / site numbers and step values
         ws["drop_base"] = (torch.initial_seed() * 0x2545F491 + _rank() * 0x632BE5AB + zlib.crc32(self.head.encode())) & 0xFFFFFFFF
@@ -1200,11 +1226,10 @@ class BertEngine(EncoderEngineBase):
         ft = self.full_ft
         self.flat.bind_grads()
         self._begin_dropout(ws, advance=False)   # backward runs on autograd's thread: the pointer is per thread
-        gw, gb = self.extra(0, grad=True), self.extra(1, grad=True)
-        ops.transpose_bf16(self.w_head_bf, self.out_dim, self.head_in, self.w_head_t)
         if self.head == "mlm_softmax_mean":
+            ops.transpose_bf16(self.w_head_bf, self.out_dim, self.head_in, self.w_head_t)
             ops.softmax_meanpool_bwd(ws["logits"], ws["sm"], dout, B, S, ws["dlog"])
-            self._decoder_grads(ws, gw, gb)
+            self._decoder_grads(ws, self.extra(0, grad=True), self.extra(1, grad=True))
             ops.gemm(ws["dlog"], self.w_head_t, ws["dtn"], EPI_BF16)                   # d tn
             self._ln_dw(ws["tg"], ws["st_t"], 0, "lnt.w", "lnt.b", g_gemm=ws["dtn"])
             ops.layernorm_bwd(ws["tg"], ws["st_t"], self.ln_t[0], 0, g_gemm=ws["dtn"], dx_bf16=ws["dtg"])
@@ -1213,12 +1238,7 @@ class BertEngine(EncoderEngineBase):
             ops.gemm(ws["dtg"], self.w_tr_t, ws["dh"], EPI_BF16)                       # d (last hidden state)
             g_resid, g_gemm = None, ws["dh"]
         else:
-            ops.cast_f32_bf16(dout, ws["dout_bf"])
-            ops.transpose_bf16(ws["dout_bf"], B, self.out_dim, ws["dout_t"])
-            ops.transpose_bf16(ws["mp"], B, H, ws["mp_t"])
-            ops.gemm(ws["dout_t"], ws["mp_t"], gw, EPI_RESID_F32, resid=gw)            # dW_proj += dout^T mean
-            ops.colsum(dout, B, self.out_dim, gb)
-            ops.gemm(ws["dout_bf"], self.w_head_t, ws["dmp"], EPI_F32)
+            self._head_backward(ws, dout, ws["mp"], ws["mp_t"], ws["dmp"], EPI_F32)   # dW_proj += dout^T mean, ...
             ops.meanpool_tokens_bwd(ws["dmp"], B, S, ws["dyl"])
             g_resid, g_gemm = ws["dyl"], None
         dt_in, a_in = None, None
@@ -1246,7 +1266,7 @@ class BertEngine(EncoderEngineBase):
             drop_p = self._drop(ws, self.p_attn, l, 1)   # the forward left its keep decisions in ws["kbits"]
             lb = self.lora_b(l)
             kb = ws["kbits"][l] if drop_p is not None and ws["kbits"] is not None else None
-            part = lb is not None and ATTN_LORA and not self.fp8 and (drop_p is None or kb is not None)
+            part = lb is not None and self.mode.attn_lora and not self.fp8 and (drop_p is None or kb is not None)
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
                          key_bias=ws["key_bias"], dropout=drop_p, keep_bits=kb,
                          lora=(ws["yb"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
@@ -1340,7 +1360,7 @@ def set_precision(model, precision):
     for m in model.modules():
         if hasattr(m, "lora_vit") or hasattr(m, "lora_barcode_bert"):
             m.hip_precision = precision
-            m._engine = None
+            _park_engine(m)
 
 
 OPERAND_FORMATS = ("bf16", "fp16")
@@ -1363,7 +1383,7 @@ def set_operand_format(model, fmt, towers=None):
     the true gradient.  The DNA and text towers' fp16 engines are inference-only -- eval() and torch.no_grad() -- until their fp16
     backward (dropout forms) exists.  ``towers``: a subset of ("image", "dna", "language"), default None = every tower; the others
     keep their format (a mixed step: image on fp16, DNA and text on bf16).  Engines are rebuilt on the next forward; their flat
-    trainable buffers (LoRA, heads, the optimizer's moments keyed on them) carry over."""
+    trainable buffers (LoRA, heads, the optimizer's moments keyed on them) carry over, as after every change of mode."""
     if fmt not in OPERAND_FORMATS:
         raise ValueError(f"operand format must be 'bf16' or 'fp16', not {fmt!r}")
     if towers is None:
@@ -1377,9 +1397,7 @@ def set_operand_format(model, fmt, towers=None):
     for m in model.modules():
         if any(hasattr(m, a) for a in marks):
             m.hip_operands = fmt
-            if getattr(m, "_engine", None) is not None:
-                m._engine_prev = m._engine   # its flat buffer goes to the rebuilt engine (_engine_for)
-            m._engine = None
+            _park_engine(m)
 
 
 def _check_fp16(module):
@@ -1408,29 +1426,25 @@ def wants_full_ft(module):
     return bool(getattr(module, "hip_full_ft", False))
 
 
-_REUSE_FLAT = []   # the flat buffer of the engine being replaced (_engine_for -> _setup_lora): reused when it holds the same tensors
+def _park_engine(m):
+    """Drop module ``m``'s engine now; its flat buffer goes to the engine that the next forward builds (_engine_for)."""
+    if getattr(m, "_engine", None) is not None:
+        m._engine_prev = m._engine
+    m._engine = None
 
 
 def _engine_for(module, build):
-    eng = getattr(module, "_engine", None)
-    if eng is not None and (eng.fp8 != wants_fp8(module) or eng.full_ft != wants_full_ft(module)
-                            or getattr(eng, "fp16", False) != wants_fp16(module)):
-        eng = None
-    if eng is not None and eng.flat.valid() and _frozen_signature(module, eng) != eng._frozen_sig:
-        eng = None  # frozen weights were overwritten (checkpoint loaded after the first forward): repack
-    if eng is None or not eng.flat.valid():
+    """The module's engine, rebuilt (``build(mode, reuse_flat)``) when it was made for another mode than the one wanted now, when its
+    parameters left the flat buffer (``.to()``) or when the frozen weights it packed were overwritten (a checkpoint loaded later)."""
+    eng, mode = getattr(module, "_engine", None), wanted_mode(module)
+    if eng is None or eng.mode != mode or not eng.flat.valid() or _frozen_signature(module, eng) != eng._frozen_sig:
         if not torch.cuda.is_available():
             raise RuntimeError("bioscanclip needs a ROCm GPU: all arithmetic runs in libbsclip_hip.so "
                                "(there is no CPU/torch fallback)")
-        old = getattr(module, "_engine", None) or getattr(module, "_engine_prev", None)
-        _REUSE_FLAT[:] = [old.flat] if old is not None and old.flat.valid() else []
-        try:
-            eng = build()
-        finally:
-            _REUSE_FLAT.clear()
-        module._engine_prev = None
+        old = eng or getattr(module, "_engine_prev", None)
+        eng = build(mode, old.flat if old is not None and old.flat.valid() else None)
         eng._frozen_sig = _frozen_signature(module, eng)
-        module._engine = eng
+        module._engine, module._engine_prev = eng, None
     return eng
 
 
@@ -1438,11 +1452,10 @@ def run_encoder(module, build, fwd_args):
     if wants_fp16(module):
         _check_fp16(module)
     eng = _engine_for(module, build)
-    eng.training = module.training
-    eng._owner = module
+    eng.training, eng._owner = module.training, module
     # the engine keeps ONE set of saved activations (its workspace): any later forward of the same encoder, with or without
     # autograd, overwrites them -- _EncoderFn.backward checks that it still owns them
-    eng._fwd_generation = getattr(eng, "_fwd_generation", 0) + 1
+    eng._fwd_generation += 1
     if torch.is_grad_enabled() and any(p.requires_grad for p in eng.flat.params):
         return _EncoderFn.apply(eng, fwd_args, *eng.flat.params)
     out = eng.forward(*fwd_args)

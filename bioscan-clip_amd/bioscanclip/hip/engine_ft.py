@@ -24,7 +24,6 @@ from .lib import EPI_RESID_F32
 
 
 class _FTMixin:
-    full_ft = True
     _partial = None
 
     # ------------------------------------------------------------------------------------------------ flat-buffer access
@@ -92,10 +91,11 @@ class _FTMixin:
 
 # ============================================================================================================== ViT
 class ViTEngineFT(_FTMixin, ViTEngine):
-    def __init__(self, module, device):
+    def __init__(self, module, device, mode, reuse_flat=None):
+        assert mode.full_ft
         self._module = module
         self._tbufs = {}
-        super().__init__(module, device, fp8=False)
+        super().__init__(module, device, mode, reuse_flat)
         vit = module.lora_vit
         H = self.H
         # live f32 views (the parameters were re-homed into the flat buffer by the base constructor)
@@ -131,12 +131,8 @@ class ViTEngineFT(_FTMixin, ViTEngine):
         named += [("norm.w", vit.norm.weight), ("norm.b", vit.norm.bias)]
         return self._register(named)
 
-    def _workspace(self, B):
-        fresh = self.ws is None or self.ws["B"] != B
-        ws = super()._workspace(B)
-        if fresh:
-            ws["dyp"] = torch.empty(B * 196, self.H, dtype=BF16, device=self.device)   # patch rows of d x0, bf16
-        return ws
+    def _extend_workspace(self, ws):
+        ws["dyp"] = torch.empty(ws["B"] * 196, self.H, dtype=BF16, device=self.device)   # patch rows of d x0, bf16
 
     def _below_layer0(self, ws):
         """d x0 [B, 197, H]: x0[b, 0] = cls + pos[0], x0[b, 1 + p] = patch_p W^T + b + pos[1 + p]."""
@@ -149,12 +145,13 @@ class ViTEngineFT(_FTMixin, ViTEngine):
 
 # ============================================================================================================= BERT
 class BertEngineFT(_FTMixin, BertEngine):
-    def __init__(self, module_bert, head, head_modules, device):
+    def __init__(self, module_bert, head, head_modules, device, mode, reuse_flat=None):
+        assert mode.full_ft
         self._module = module_bert
         self._head_modules = head_modules
         self._head_kind = head
         self._tbufs = {}
-        super().__init__(module_bert, head, head_modules, device, fp8=False)
+        super().__init__(module_bert, head, head_modules, device, mode, reuse_flat)
         bert, H = module_bert, self.H
         emb = bert.embeddings
         self.word, self.posw = emb.word_embeddings.weight.data, emb.position_embeddings.weight.data
@@ -202,12 +199,8 @@ class BertEngineFT(_FTMixin, BertEngine):
             named += [("tr.w", tr.dense.weight), ("tr.b", tr.dense.bias), ("lnt.w", tr.LayerNorm.weight), ("lnt.b", tr.LayerNorm.bias)]
         return self._register(named)
 
-    def _workspace(self, B, S):
-        fresh = self.ws is None or self.ws["B"] != B or self.ws["S"] != S
-        ws = super()._workspace(B, S)
-        if fresh:
-            ws["demb"] = torch.empty(B * S, self.H, dtype=F32, device=self.device)
-        return ws
+    def _extend_workspace(self, ws):
+        ws["demb"] = torch.empty(ws["M"], self.H, dtype=F32, device=self.device)
 
     def _below_layer0(self, ws, g_resid, g_gemm, dt_in, a_in):
         """The embedding LayerNorm (its output was dropped in forward with site (-1, 0)) and the three tables."""

@@ -40,6 +40,40 @@ def _rowmajor(t, name):
     return t.stride(0)
 
 
+def _f32_shaped(t, shape, name):
+    # as above: nothing is formatted unless the check fails
+    if t is None or t.dtype != F32 or not t.is_contiguous() or t.shape != shape:
+        raise ValueError(f"{name} must be contiguous f32 {list(shape)}")
+
+
+def _lora_grads_ok(M, H, dt, dA, dBq, dBv):
+    _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
+    _f32_shaped(dA, (8, H), "dA")
+    _f32_shaped(dBq, (H, 4), "dBq")
+    _f32_shaped(dBv, (H, 4), "dBv")
+
+
+def _key_bias_ok(key_bias, B, S):
+    if key_bias is not None and not (key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S):
+        raise ValueError("key_bias f32 [B,S]")
+
+
+def _drop(dropout):   # a dropout site's (p, seed), or None for none, as the kernels take it
+    return (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+
+
+_STREAM_WS = {}
+
+
+def _stream_ws(tag, device, floats):
+    """f32 scratch of >= ``floats`` elements for kernel family ``tag``: one per device and launching stream (the towers run concurrently)."""
+    key = (tag, str(device), torch.cuda.current_stream().cuda_stream)
+    ws = _STREAM_WS.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _STREAM_WS[key] = torch.empty(floats, dtype=F32, device=device)
+    return ws
+
+
 def gemm(a, b, out, epilogue=EPI_BF16, bias=None, resid=None, aux=None, M=None, K=None, dropout=None):
     """out = epilogue(a[:M, :K] @ b[:, :K].T).  a [M, >=K], b [N, >=K] (row strides may exceed K), both bf16 or both fp16; with
     fp16 operands every 16-bit output / residual of the epilogue is fp16 too (BSCLIP_OPERANDS_FP16)."""
@@ -74,7 +108,7 @@ def gemm(a, b, out, epilogue=EPI_BF16, bias=None, resid=None, aux=None, M=None, 
         args.ld_aux = _rowmajor(aux, "aux")
     if dropout is not None:  # (p, seed): C = dropout(acc + bias) + resid
         _req(epilogue in (EPI_RESID_F32, EPI_RESID_BF16), "gemm: dropout is only defined for EPI_RESID_F32 / _BF16")
-        args.dropout_p, args.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF
+        args.dropout_p, args.dropout_seed = _drop(dropout)
     fmt = OPERANDS_FP16 if h16 == F16 else 0
     check(_l.load().bsclip_gemm_bf16(_p(a), lda, _p(b), ldb, _p(out), ldc, M, N, K, epilogue | fmt, ctypes.byref(args),
                                      _stream()))
@@ -110,7 +144,7 @@ def gemm_fp8(a8, b8, out, alpha, bias, epilogue=EPI_BF16, resid=None, aux=None, 
         args.aux, args.ld_aux = aux.data_ptr(), _rowmajor(aux, "aux")
     if dropout is not None:
         _req(epilogue == EPI_RESID_F32, "gemm_fp8: dropout is only defined for EPI_RESID_F32")
-        args.dropout_p, args.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF
+        args.dropout_p, args.dropout_seed = _drop(dropout)
     f8 = Fp8Args()
     f8.form = FP8_FORM if form is None else form
     f8.alpha = alpha.data_ptr()
@@ -136,7 +170,8 @@ def quantize_rows_fp8(w):
 
 def lora_baug_set(b_aug, H, bq, bv, alpha):
     _req(b_aug.dtype == BF16 and b_aug.shape[0] >= 3 * H and b_aug.shape[1] >= 64, "b_aug bf16 [3H, >=64]")
-    _req(all(t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (H, 4) for t in (bq, bv)), "bq/bv f32 [H,4]")
+    _f32_shaped(bq, (H, 4), "bq")
+    _f32_shaped(bv, (H, 4), "bv")
     _req(alpha.dtype == F32 and alpha.is_contiguous() and alpha.numel() >= 3 * H, "alpha f32 [3H]")
     check(_l.load().bsclip_lora_baug_set(_p(b_aug), _rowmajor(b_aug, "b_aug"), H, _p(bq), _p(bv), _p(alpha), _stream()))
 
@@ -187,14 +222,14 @@ def layernorm_fwd(x, gamma, beta, eps, y_bf16=None, y_f32=None, lora_a=None, sta
         _req(y_f32.dtype == F32 and y_f32.is_contiguous() and y_f32.shape[0] >= M and y_f32.shape[1] == H,
              "layernorm_fwd: y_f32 must be contiguous f32 [M, H]")
     if lora_a is not None:
-        _req(lora_a.dtype == F32 and lora_a.is_contiguous() and tuple(lora_a.shape) == (8, H), "lora_a must be f32 [8,H]")
+        _f32_shaped(lora_a, (8, H), "lora_a")
     if stats is not None:
         _req(stats.dtype == F32 and stats.is_contiguous() and stats.numel() >= 2 * M, "stats must be f32 [M,2]")
     ld_y3 = 0
     if y_split3 is not None:
         ld_y3 = _rowmajor(y_split3, "y_split3")
         _req(y_split3.dtype == BF16 and y_split3.shape[0] >= M and y_split3.shape[1] >= 3 * H, "layernorm_fwd: y_split3 bf16 [M, >= 3H]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    dp, ds = _drop(dropout)
     fmt = OPERANDS_FP16 if h16 == F16 else 0
     check(_l.load().bsclip_layernorm_fwd(_p(x), ld_x, int(x.dtype != F32) | fmt, M, H, _p(gamma), _p(beta), float(eps),
                                          _p(y_bf16), ld_y, _p(y_f32), _p(y_split3), ld_y3, _p(lora_a), _p(stats), dp, ds, _stream()))
@@ -213,12 +248,12 @@ def layernorm_fwd_fp8(x, gamma, beta, eps, y_fp8, t_aug=None, y_f32=None, lora_a
     if t_aug is not None:
         ld_t = _rowmajor(t_aug, "t_aug")
         _req(t_aug.dtype == BF16 and t_aug.shape[0] >= M and t_aug.shape[1] >= KPAD, "t_aug bf16 [M, >=64]")
-        _req(lora_a.dtype == F32 and lora_a.is_contiguous() and tuple(lora_a.shape) == (8, H), "lora_a must be f32 [8,H]")
+        _f32_shaped(lora_a, (8, H), "lora_a")
     if y_f32 is not None:
         _req(y_f32.dtype == F32 and y_f32.is_contiguous() and y_f32.shape[0] >= M and y_f32.shape[1] == H, "y_f32 f32 [M,H]")
     if stats is not None:
         _req(stats.dtype == F32 and stats.is_contiguous() and stats.numel() >= 2 * M, "stats must be f32 [M,2]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    dp, ds = _drop(dropout)
     check(_l.load().bsclip_layernorm_fwd_fp8(_p(x), ld_x, int(x.dtype == BF16), M, H, _p(gamma), _p(beta), float(eps),
                                              _p(y_fp8), _rowmajor(y_fp8, "y_fp8"), _p(t_aug), ld_t, _p(y_f32), _p(lora_a),
                                              _p(stats), dp, ds, _stream()))
@@ -254,8 +289,7 @@ def layernorm_bwd(x, stats, gamma, mode, g_resid=None, g_gemm=None, dt=None, lor
         _req(g_gemm.dtype in (BF16, F32, F16) and g_gemm.shape[0] >= M and g_gemm.shape[1] >= H, "g_gemm must be bf16 / f32 [M,>=H]")
     if dt is not None:
         _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt must be f32 [M,8]")
-        _req(lora_a is not None and tuple(lora_a.shape) == (8, H) and lora_a.dtype == F32 and lora_a.is_contiguous(),
-             "lora_a must be f32 [8,H]")
+        _f32_shaped(lora_a, (8, H), "lora_a")
     if dx_f32 is not None:
         ld_dx = _rowmajor(dx_f32, "dx_f32")
         _req(dx_f32.dtype in (F32, BF16, F16) and dx_f32.shape[0] >= M and dx_f32.shape[1] >= H, "dx_f32 must be f32 / bf16 [M,>=H]")
@@ -269,10 +303,7 @@ def layernorm_bwd(x, stats, gamma, mode, g_resid=None, g_gemm=None, dt=None, lor
     check(_l.load().bsclip_layernorm_bwd(_p(x), ld_x, (1 | OPERANDS_FP16) if f16 else int(x.dtype == BF16), _p(stats), _p(gamma), M, H, _p(g_resid),
                                          ld_gr, _p(g_gemm), ld_g, _p(dt), _p(lora_a) if dt is not None else None,
                                          int(mode), _p(dx_f32), ld_dx, _p(dx_bf16), ld_dxb,
-                                         0.0 if dropout is None else float(dropout[0]),
-                                         0 if dropout is None else int(dropout[1]) & 0xFFFFFFFF,
-                                         0.0 if in_dropout is None else float(in_dropout[0]),
-                                         0 if in_dropout is None else int(in_dropout[1]) & 0xFFFFFFFF,
+                                         *_drop(dropout), *_drop(in_dropout),
                                          (1 if g_resid is not None and g_resid.dtype in b16 else 0)
                                          | (2 if dx_f32 is not None and dx_f32.dtype in b16 else 0)
                                          | (4 if g_gemm is not None and g_gemm.dtype == F32 else 0)
@@ -298,9 +329,8 @@ def attn_fwd(qkv, B, S, heads, scale, ctx, lse, key_bias=None, dropout=None, q_r
     _req(qkv.dtype == h16 and ctx.dtype == h16 and lse.dtype == F32, "attn_fwd dtypes")
     _req(qkv.shape[0] >= B * S and qkv.shape[1] >= 3 * heads * 64, "attn_fwd: qkv too small")
     _req(ctx.shape[0] >= B * S and ctx.shape[1] >= heads * 64 and lse.numel() >= B * heads * S, "attn_fwd: outputs too small")
-    if key_bias is not None:
-        _req(key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S, "key_bias f32 [B,S]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    _key_bias_ok(key_bias, B, S)
+    dp, ds = _drop(dropout)
     fmt = OPERANDS_FP16 if h16 == F16 else 0
     check(_l.load().bsclip_attn_fwd(_p(qkv), ld_qkv, B, S, heads, _p(key_bias), float(scale), _p(ctx), ld_ctx, _p(lse),
                                     int(q_rows) | fmt, _p(keep_bits), dp, ds, _stream()))
@@ -321,14 +351,13 @@ def attn_bwd(qkv, dctx, lse, B, S, heads, scale, dqkv, key_bias=None, dropout=No
     _req(min(qkv.shape[0], dctx.shape[0], dqkv.shape[0]) >= B * S, "attn_bwd: rows")
     _req(qkv.shape[1] >= 3 * heads * 64 and dqkv.shape[1] >= 3 * heads * 64 and dctx.shape[1] >= heads * 64
          and lse.numel() >= B * heads * S, "attn_bwd: cols")
-    if key_bias is not None:
-        _req(key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S, "key_bias f32 [B,S]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    _key_bias_ok(key_bias, B, S)
+    dp, ds = _drop(dropout)
     if lora is not None:
         t_aug, lora_b, dtp, dbp = lora
         ld_t = _rowmajor(t_aug, "t_aug")
         _req(t_aug.dtype == h16 and t_aug.shape[0] >= B * S and t_aug.shape[1] >= 8, "attn_bwd: t_aug 16-bit [>= B S, >= 8] (qkv's format)")
-        _req(lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, heads * 64, 4), "attn_bwd: lora_b f32 [2,H,4]")
+        _f32_shaped(lora_b, (2, heads * 64, 4), "attn_bwd: lora_b")
         _req(dtp.dtype == F32 and dtp.is_contiguous() and dtp.numel() >= heads * B * S * 8
              and dbp.dtype == F32 and dbp.is_contiguous() and dbp.numel() >= B * heads * 512, "attn_bwd: dt_partial / db_partial sizes")
         _req(dp == 0.0 or keep_bits is not None, "attn_bwd: the LoRA partials under dropout need the forward's keep_bits")
@@ -358,8 +387,9 @@ def split3_weight(w, dst, lora_a=None, lora_b=None):
     H = 0
     if lora_a is not None:
         H = K
-        _req(lora_a.dtype == F32 and lora_a.is_contiguous() and tuple(lora_a.shape) == (8, K) and N == 3 * K, "lora_a f32 [8, H], N = 3H")
-        _req(lora_b is not None and lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, K, 4), "lora_b f32 [2,H,4]")
+        _req(N == 3 * K, "split3_weight: the LoRA fold needs w [3H, H]")
+        _f32_shaped(lora_a, (8, K), "lora_a")
+        _f32_shaped(lora_b, (2, K, 4), "lora_b")
     check(_l.load().bsclip_split3_weight(_p(w), K, N, K, _p(lora_a), _p(lora_b if lora_a is not None else None), H, _p(dst), 3 * K,
                                          _stream()))
     return dst
@@ -400,9 +430,8 @@ def attn_fwd_f32(qkv, B, S, heads, scale, ctx, lse, key_bias=None, dropout=None,
     _req(qkv.dtype == F32 and ctx.dtype == F32 and lse.dtype == F32, "attn_fwd_f32 dtypes")
     _req(qkv.shape[0] >= B * S and qkv.shape[1] >= 3 * heads * 64 and ctx.shape[0] >= B * S and ctx.shape[1] >= heads * 64
          and lse.numel() >= B * heads * S, "attn_fwd_f32 shapes")
-    if key_bias is not None:
-        _req(key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S, "key_bias f32 [B,S]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    _key_bias_ok(key_bias, B, S)
+    dp, ds = _drop(dropout)
     check(_l.load().bsclip_attn_fwd_f32(_p(qkv), ld_qkv, B, S, heads, _p(key_bias), float(scale), _p(ctx), ld_ctx, _p(lse),
                                         _p(ctx_split3), ld_c3, dp, ds, _stream()))
 
@@ -435,9 +464,9 @@ def split3_transpose(src, dst_flat, order, R=None, lora_a=None, lora_b=None):
     H = 0
     if lora_a is not None:
         H = C
-        _req(src.is_contiguous() and R == 3 * C and lora_a.dtype == F32 and lora_a.is_contiguous() and tuple(lora_a.shape) == (8, C)
-             and lora_b is not None and lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, C, 4),
-             "split3_transpose: LoRA fold needs src [3H, H], lora_a [8, H], lora_b [2, H, 4]")
+        _req(src.is_contiguous() and R == 3 * C, "split3_transpose: the LoRA fold needs src [3H, H]")
+        _f32_shaped(lora_a, (8, C), "lora_a")
+        _f32_shaped(lora_b, (2, C, 4), "lora_b")
     dst = dst_flat.view(-1)[:C * 3 * Rp].view(C, 3 * Rp)
     check(_l.load().bsclip_split3_transpose(_p(src), _rowmajor(src, "src"), R, C, Rp, int(order), _p(lora_a),
                                             _p(lora_b if lora_a is not None else None), H, _p(dst), 3 * Rp, _stream()))
@@ -452,19 +481,15 @@ def softmax_meanpool_bwd_f32(logits, stats, d_pooled, B, S, dlogits):
                                                     _rowmajor(dlogits, "dlogits"), _stream()))
 
 
-_LG32_WS = {}
-
-
 def lora_grad_f32(dqkv, y, M, H, lora_a, lora_b, dA, dB):
     """dA [8, H] += ..., dB [2, H, 4] += ... from f32 dqkv [M, >= 3H] and the f32 LayerNorm output y [M, >= H]."""
     _req(dqkv.dtype == F32 and y.dtype == F32 and dqkv.shape[0] >= M and dqkv.shape[1] >= 3 * H and y.shape[0] >= M and y.shape[1] >= H,
          "lora_grad_f32 shapes")
-    _req(all(t.dtype == F32 and t.is_contiguous() for t in (lora_a, lora_b, dA, dB)) and tuple(lora_a.shape) == (8, H)
-         and tuple(lora_b.shape) == (2, H, 4) and tuple(dA.shape) == (8, H) and tuple(dB.shape) == (2, H, 4), "lora_grad_f32: parameters")
-    key = (M, H, str(dqkv.device), torch.cuda.current_stream().cuda_stream)   # one workspace per launching stream (towers run concurrently)
-    ws = _LG32_WS.get(key)
-    if ws is None:
-        ws = _LG32_WS[key] = torch.empty(_l.load().bsclip_lora_grad_f32_workspace_floats(M, H), dtype=F32, device=dqkv.device)
+    _f32_shaped(lora_a, (8, H), "lora_a")
+    _f32_shaped(lora_b, (2, H, 4), "lora_b")
+    _f32_shaped(dA, (8, H), "dA")
+    _f32_shaped(dB, (2, H, 4), "dB")
+    ws = _stream_ws(("lora_grad_f32", M, H), dqkv.device, _l.load().bsclip_lora_grad_f32_workspace_floats(M, H))
     check(_l.load().bsclip_lora_grad_f32(_p(dqkv), _rowmajor(dqkv, "dqkv"), _p(y), _rowmajor(y, "y"), M, H, _p(lora_a), _p(lora_b),
                                          _p(dA), _p(dB), _p(ws), _stream()))
 
@@ -485,9 +510,8 @@ def attn_bwd_f32(qkv, dctx, ctx, lse, B, S, heads, scale, dqkv, key_bias=None, d
     _req(qkv.shape[0] >= B * S and qkv.shape[1] >= 3 * heads * 64 and dqkv.shape[0] >= B * S and dqkv.shape[1] >= 3 * heads * 64
          and ctx.shape[0] >= B * S and ctx.shape[1] >= heads * 64 and dctx.shape[0] >= B * S and dctx.shape[1] >= heads * 64
          and lse.numel() >= B * heads * S, "attn_bwd_f32 shapes")
-    if key_bias is not None:
-        _req(key_bias.dtype == F32 and key_bias.is_contiguous() and key_bias.numel() >= B * S, "key_bias f32 [B,S]")
-    dp, ds = (0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+    _key_bias_ok(key_bias, B, S)
+    dp, ds = _drop(dropout)
     check(_l.load().bsclip_attn_bwd_f32(_p(qkv), _rowmajor(qkv, "qkv"), _p(dctx), _rowmajor(dctx, "dctx"), _p(ctx), _rowmajor(ctx, "ctx"),
                                         _p(lse), B, S, heads, _p(key_bias), float(scale), _p(dqkv), _rowmajor(dqkv, "dqkv"),
                                         _p(dqkv_split3), ld_d3, dp, ds, _stream()))
@@ -834,26 +858,15 @@ def class_topk(logits, C, k):
     return scores, idx
 
 
-_LG_WS = {}
-
-
 def _lora_grad_workspace(H, device):
-    # one workspace per launching stream: the towers run concurrently on their own streams (SimpleCLIP.forward)
-    key = (H, str(device), torch.cuda.current_stream().cuda_stream)
-    ws = _LG_WS.get(key)
-    if ws is None:
-        ws = torch.empty(_l.load().bsclip_lora_grad_workspace_floats(H), dtype=F32, device=device)
-        _LG_WS[key] = ws
-    return ws
+    return _stream_ws(("lora_grad", H), device, _l.load().bsclip_lora_grad_workspace_floats(H))
 
 
 def lora_grad(dqkv, h_aug, M, H, lora_b, dt, dA, dBq, dBv):
     _req(dqkv.dtype == BF16 and h_aug.dtype == BF16, "lora_grad: bf16 inputs")
     _req(dqkv.shape[0] >= M and dqkv.shape[1] >= 3 * H and h_aug.shape[0] >= M and h_aug.shape[1] >= H + 8, "lora_grad shapes")
-    _req(lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, H, 4), "lora_b f32 [2,H,4]")
-    _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
-    _req(dA.dtype == F32 and dA.is_contiguous() and tuple(dA.shape) == (8, H), "dA f32 [8,H]")
-    _req(all(t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (H, 4) for t in (dBq, dBv)), "dB f32 [H,4]")
+    _f32_shaped(lora_b, (2, H, 4), "lora_b")
+    _lora_grads_ok(M, H, dt, dA, dBq, dBv)
     check(_l.load().bsclip_lora_grad(_p(dqkv), _rowmajor(dqkv, "dqkv"), _p(h_aug), _rowmajor(h_aug, "h_aug"), M, H,
                                      _p(lora_b), _p(dt), _p(dA), _p(dBq), _p(dBv),
                                      _p(_lora_grad_workspace(H, dqkv.device)), _stream()))
@@ -870,9 +883,7 @@ def lora_grad_heads(h_aug, M, H, B, dt_partial, db_partial, dt, dA, dBq, dBv, gr
     _req(h_aug.dtype in (BF16, F16) and h_aug.shape[0] >= M and h_aug.shape[1] >= H and M % B == 0, "lora_grad_heads: h_aug bf16 [M, >= H]")
     _req(dt_partial.dtype == F32 and dt_partial.is_contiguous() and dt_partial.numel() >= heads * M * 8
          and db_partial.dtype == F32 and db_partial.is_contiguous() and db_partial.numel() >= B * heads * 512, "lora_grad_heads: partials")
-    _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
-    _req(dA.dtype == F32 and dA.is_contiguous() and tuple(dA.shape) == (8, H), "dA f32 [8,H]")
-    _req(all(t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (H, 4) for t in (dBq, dBv)), "dB f32 [H,4]")
+    _lora_grads_ok(M, H, dt, dA, dBq, dBv)
     if h_aug.dtype == F16:
         check(_l.load().bsclip_lora_grad_heads_f16(_p(h_aug), _rowmajor(h_aug, "h_aug"), M, H, B, _p(dt_partial), _p(db_partial), _p(dt),
                                                    _p(dA), _p(dBq), _p(dBv), _p(_lora_grad_workspace(H, h_aug.device)),
@@ -886,10 +897,8 @@ def lora_grad_fp8(dqkv, y_fp8, t_aug, M, H, lora_b, dt, dA, dBq, dBv):
     _req(dqkv.dtype == BF16 and y_fp8.dtype == FP8 and t_aug.dtype == BF16, "lora_grad_fp8: dtypes")
     _req(dqkv.shape[0] >= M and dqkv.shape[1] >= 3 * H and y_fp8.shape[0] >= M and y_fp8.shape[1] >= H
          and t_aug.shape[0] >= M and t_aug.shape[1] >= 8, "lora_grad_fp8 shapes")
-    _req(lora_b.dtype == F32 and lora_b.is_contiguous() and tuple(lora_b.shape) == (2, H, 4), "lora_b f32 [2,H,4]")
-    _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
-    _req(dA.dtype == F32 and dA.is_contiguous() and tuple(dA.shape) == (8, H), "dA f32 [8,H]")
-    _req(all(t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == (H, 4) for t in (dBq, dBv)), "dB f32 [H,4]")
+    _f32_shaped(lora_b, (2, H, 4), "lora_b")
+    _lora_grads_ok(M, H, dt, dA, dBq, dBv)
     check(_l.load().bsclip_lora_grad_fp8(_p(dqkv), _rowmajor(dqkv, "dqkv"), _p(y_fp8), _rowmajor(y_fp8, "y_fp8"), _p(t_aug),
                                          _rowmajor(t_aug, "t_aug"), M, H, _p(lora_b), _p(dt), _p(dA), _p(dBq), _p(dBv),
                                          _p(_lora_grad_workspace(H, dqkv.device)), _stream()))
@@ -908,20 +917,13 @@ def transpose_bf16(src, R, C, dst):
     check(_l.load().bsclip_transpose_bf16(_p(src), _rowmajor(src, "src"), R, C, _p(dst), _rowmajor(dst, "dst"), _stream()))
 
 
-_TC_WS = {}
-
-
 def transpose_colsum_bf16(src, R, C, dst, colsum_out):
     """dst[C, R] = src[R, C]^T and colsum_out[c] += sum_r src[r, c] in one pass over src (weight-gradient operand + bias gradient)."""
     _req(src.dtype == BF16 and dst.dtype == BF16, "transpose_colsum_bf16 dtypes")
     _req(src.shape[0] >= R and src.shape[1] >= C and dst.shape[0] >= C and dst.shape[1] >= R, "transpose_colsum_bf16 shapes")
     _req(colsum_out.dtype == F32 and colsum_out.is_contiguous() and colsum_out.numel() >= C, "transpose_colsum_bf16: colsum f32 [C]")
     lib = _l.load()
-    need = lib.bsclip_transpose_colsum_workspace_floats(R, C)
-    key = (str(src.device), torch.cuda.current_stream().cuda_stream)
-    ws = _TC_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _TC_WS[key] = torch.empty(need, dtype=F32, device=src.device)
+    ws = _stream_ws("transpose_colsum", src.device, lib.bsclip_transpose_colsum_workspace_floats(R, C))
     check(lib.bsclip_transpose_colsum_bf16(_p(src), _rowmajor(src, "src"), R, C, _p(dst), _rowmajor(dst, "dst"), _p(colsum_out),
                                            _p(ws), _stream()))
 
@@ -1030,9 +1032,6 @@ def augment_images(src, records, B, mid_capacity, mid, out_size, out):
 
 
 # ------------------------------------------------------------------------------------------- full fine-tuning (8f-4)
-_PG_WS = {}
-
-
 def ln_param_grad(x, stats, mode, d_gamma, d_beta, g_resid=None, g_gemm=None, dt=None, lora_a=None, M=None, in_dropout=None):
     """d_gamma / d_beta += LayerNorm parameter gradients, dy assembled as layernorm_bwd does."""
     ld_x = _rowmajor(x, "x")
@@ -1049,13 +1048,10 @@ def ln_param_grad(x, stats, mode, d_gamma, d_beta, g_resid=None, g_gemm=None, dt
         ld_g = _rowmajor(g_gemm, "g_gemm")
         _req(g_gemm.dtype == BF16 and g_gemm.shape[0] >= M and g_gemm.shape[1] >= H, "g_gemm bf16 [M,>=H]")
     if dt is not None:
-        _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M and lora_a is not None
-             and tuple(lora_a.shape) == (8, H) and lora_a.dtype == F32 and lora_a.is_contiguous(), "dt f32 [M,8], lora_a f32 [8,H]")
-    key = (H, str(x.device), torch.cuda.current_stream().cuda_stream)
-    ws = _PG_WS.get(key)
-    if ws is None:
-        ws = _PG_WS[key] = torch.empty(_l.load().bsclip_ln_param_grad_workspace_floats(H), dtype=F32, device=x.device)
-    dp, ds = (0.0, 0) if in_dropout is None else (float(in_dropout[0]), int(in_dropout[1]) & 0xFFFFFFFF)
+        _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
+        _f32_shaped(lora_a, (8, H), "lora_a")
+    ws = _stream_ws(("ln_param_grad", H), x.device, _l.load().bsclip_ln_param_grad_workspace_floats(H))
+    dp, ds = _drop(in_dropout)
     check(_l.load().bsclip_ln_param_grad(_p(x), ld_x, int(x.dtype == BF16), _p(stats), M, H, _p(g_resid), ld_gr, _p(g_gemm), ld_g,
                                          _p(dt), _p(lora_a) if dt is not None else None, int(mode), dp, ds, _p(d_gamma),
                                          _p(d_beta), _p(ws), _stream()))
@@ -1069,10 +1065,7 @@ def embed_grad(ids, type_ids, d_emb, d_word, d_pos, d_type, pad_id=0):
     _req(d_emb.dtype == F32 and d_emb.is_contiguous() and d_emb.shape[0] >= B * S and d_emb.shape[1] == H, "d_emb f32 [B*S,H]")
     _req(all(t.dtype == F32 and t.is_contiguous() and t.shape[1] == H for t in (d_word, d_pos, d_type)) and d_pos.shape[0] >= S
          and d_type.shape[0] >= 2, "embed_grad: gradient tables f32 [*,H]")
-    key = ("embed", H, str(d_emb.device), torch.cuda.current_stream().cuda_stream)
-    ws = _PG_WS.get(key)
-    if ws is None:
-        ws = _PG_WS[key] = torch.empty(_l.load().bsclip_embed_grad_workspace_floats(H), dtype=F32, device=d_emb.device)
+    ws = _stream_ws(("embed_grad", H), d_emb.device, _l.load().bsclip_embed_grad_workspace_floats(H))
     check(_l.load().bsclip_embed_grad(_p(ids), _p(type_ids), B, S, H, d_word.shape[0], int(pad_id), _p(d_emb), _p(d_word),
                                       _p(d_pos), _p(d_type), _p(ws), _stream()))
 

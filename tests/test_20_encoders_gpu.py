@@ -290,6 +290,124 @@ def test_exact_forward_meets_north_star_tolerance(which, monkeypatch):
     assert e <= EXACT_FACTOR * m_e and worst <= EXACT_FACTOR * m_g, (which, e, worst, EXACT_MEASURED[which])
 
 
+# ---- engines carry the mode they were built for (hip/engine.py EngineMode): a changed request reaches a live engine at its next forward
+_MODE_REF = {}   # (which, parity level) -> (output, flat gradient) of a model built fresh in that mode: shared by the tests below
+
+
+def _small_encoder(which):
+    """The depth-2 ViT / BarcodeBERT of the tests above on their seeded weights, batch 2, in train mode, with a cotangent."""
+    from bioscanclip.model import arch
+    with skip_param_init():
+        if which == "vit":
+            from bioscanclip.model.image_encoder import LoRA_ViT_timm
+            m = LoRA_ViT_timm(arch.VisionTransformerParams(depth=2), r=4, num_classes=768)
+            _load(m, "image_encoder.", 13)
+            x = synth.synth_batch(2, seed=23)[0]
+        else:
+            from bioscanclip.model.dna_encoder import LoRA_barcode_bert
+            m = LoRA_barcode_bert(arch.BertForMaskedLMParams(arch.barcode_bert_config(num_hidden_layers=2, **NODROP)), r=4, num_classes=768)
+            _load(m, "dna_encoder.", 11)
+            x = synth.synth_batch(2, seed=21)[1]
+    return m.to("cuda").train(), x.cuda(), synth.synth_tensor(f"{which}.cot.2", (2, 768), seed=5).cuda()
+
+
+def _step(m, x, w):
+    """One forward + backward from zeroed gradients: (output, flat gradient buffer), both copied."""
+    m.zero_grad(set_to_none=False)     # the parameters' .grad are views of the flat buffer, whichever engine holds it
+    y = m(x)
+    (y * w).sum().backward()
+    torch.cuda.synchronize()
+    return y.detach().clone(), m._engine.flat.grad.clone()
+
+
+class _parity_mode:
+    """``with _parity_mode(n):`` -- engine.set_parity_mode(n) WITHOUT a model; the three globals are put back on the way out."""
+
+    def __init__(self, level):
+        self.level = level
+
+    def __enter__(self):
+        from bioscanclip.hip import engine
+        self.keep = (engine.GRAD_STREAM_BF16, engine.RESID_STREAM_BF16, engine.EXACT_FORWARD)
+        engine.set_parity_mode(self.level)
+
+    def __exit__(self, *exc):
+        from bioscanclip.hip import engine
+        engine.GRAD_STREAM_BF16, engine.RESID_STREAM_BF16, engine.EXACT_FORWARD = self.keep
+
+
+def _fresh_in_mode(which, level):
+    if (which, level) not in _MODE_REF:
+        with _parity_mode(level):
+            _MODE_REF[which, level] = _step(*_small_encoder(which))
+    return _MODE_REF[which, level]
+
+
+def _same(got, want):
+    return torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
+@pytest.mark.parametrize("which", ["vit", "dna"])
+def test_live_engine_follows_the_exact_mode_globals(which, monkeypatch):
+    """The three exact-mode globals change under a live engine, the model is not touched: the next forward runs on a NEW engine built
+    for the exact mode, on the SAME flat parameter / gradient buffer, and gives bitwise what a model built fresh in that mode gives;
+    the globals flipped back, the default-mode results come back bitwise.  (Before the engines carried their mode, the old engine
+    answered exact() from the new global with the old workspace: a KeyError for the exact mode's first buffer, 'a3'.)"""
+    from bioscanclip.hip import engine
+    m, x, w = _small_encoder(which)
+    first = _step(m, x, w)
+    eng0, flat = m._engine, m._engine.flat
+    assert not eng0.exact()
+    monkeypatch.setattr(engine, "RESID_STREAM_BF16", False)
+    monkeypatch.setattr(engine, "GRAD_STREAM_BF16", False)
+    monkeypatch.setattr(engine, "EXACT_FORWARD", True)
+    exact = _step(m, x, w)
+    eng1 = m._engine
+    assert eng1.exact()
+    assert eng1 is not eng0
+    assert eng1.flat is flat
+    monkeypatch.undo()
+    assert _same(exact, _fresh_in_mode(which, 2))
+    again = _step(m, x, w)
+    assert not m._engine.exact() and m._engine is not eng1 and m._engine.flat is flat
+    assert _same(again, first)
+
+
+@pytest.mark.parametrize("which", ["vit", "dna"])
+def test_set_parity_mode_without_a_model_reaches_a_live_engine(which):
+    """set_parity_mode(1) called without ``model`` (as bench.py calls it): the live engine is replaced by one on the f32 streams."""
+    m, x, w = _small_encoder(which)
+    first = _step(m, x, w)
+    eng0, flat = m._engine, m._engine.flat
+    assert eng0.ws["resid_bf16"] is True and eng0.ws["grad_bf16"] is True
+    with _parity_mode(1):
+        f32 = _step(m, x, w)
+        eng1 = m._engine
+        assert eng1.ws["resid_bf16"] is False and eng1.ws["grad_bf16"] is False
+        assert not eng1.exact() and eng1 is not eng0 and eng1.flat is flat
+    assert _same(f32, _fresh_in_mode(which, 1))
+    again = _step(m, x, w)
+    assert m._engine.ws["resid_bf16"] is True and m._engine.ws["grad_bf16"] is True and m._engine.flat is flat
+    assert _same(again, first)
+
+
+@pytest.mark.parametrize("which", ["vit", "dna"])
+def test_set_precision_keeps_the_flat_buffer(which):
+    """set_precision carries the flat parameter / gradient buffer over to the rebuilt engine, as set_operand_format does."""
+    from bioscanclip.hip import engine
+    m, x, w = _small_encoder(which)
+    first = _step(m, x, w)
+    flat = m._engine.flat
+    engine.set_precision(m, "fp8")
+    assert m._engine is None
+    _step(m, x, w)
+    assert m._engine.fp8 and m._engine.flat is flat
+    engine.set_precision(m, "bf16")
+    again = _step(m, x, w)
+    assert not m._engine.fp8 and m._engine.flat is flat
+    assert _same(again, first)
+
+
 def _build_clip(*a, **k):
     from helpers import skip_param_init
     with skip_param_init():   # every tensor is loaded from oracle.synth right after construction

@@ -28,12 +28,12 @@ if os.environ.get("GUARD", "0") == "1":   # the f32 LoRA-gradient workspaces bet
     SENT = 12345.678
 
     def guarded(dqkv, y, M, H, lora_a, lora_b, dA, dB):
-        key = (M, H, str(dqkv.device), torch.cuda.current_stream().cuda_stream)
-        if key not in ops._LG32_WS:
+        key = (("lora_grad_f32", M, H), str(dqkv.device), torch.cuda.current_stream().cuda_stream)   # ops._stream_ws
+        if key not in ops._STREAM_WS:
             n = ops._l.load().bsclip_lora_grad_f32_workspace_floats(M, H)
             G = 1 << 18
             big = torch.full((n + 2 * G,), SENT, device=dqkv.device)
-            ops._LG32_WS[key] = big[G:G + n]
+            ops._STREAM_WS[key] = big[G:G + n]
             GUARDS[key] = (big, G, n)
         return _orig(dqkv, y, M, H, lora_a, lora_b, dA, dB)
     ops.lora_grad_f32 = guarded
@@ -46,14 +46,14 @@ if os.environ.get("GUARD", "0") == "2":
     _orig2 = ops.lora_grad_f32
 
     def perlayer(dqkv, y, M, H, lora_a, lora_b, dA, dB):
-        key = (M, H, str(dqkv.device), torch.cuda.current_stream().cuda_stream)
+        key = (("lora_grad_f32", M, H), str(dqkv.device), torch.cuda.current_stream().cuda_stream)   # ops._stream_ws
         L = 2 if H == 512 else 3
         i = CALLS.get(key, 0)
         CALLS[key] = (i + 1) % L
         if (key, i) not in PERLAYER:
             n = ops._l.load().bsclip_lora_grad_f32_workspace_floats(M, H)
             PERLAYER[(key, i)] = torch.zeros(n, device=dqkv.device)
-        ops._LG32_WS[key] = PERLAYER[(key, i)]
+        ops._STREAM_WS[key] = PERLAYER[(key, i)]
         return _orig2(dqkv, y, M, H, lora_a, lora_b, dA, dB)
     ops.lora_grad_f32 = perlayer
     engine.ops.lora_grad_f32 = perlayer

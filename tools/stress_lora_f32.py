@@ -32,8 +32,8 @@ sa, sb, sc = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
 torch.cuda.synchronize()
 dA0, dB0 = run(sa)
 torch.cuda.synchronize()
-wkey = [k for k in ops._LG32_WS if k[0] == M and k[1] == H][0]
-ws0 = ops._LG32_WS[wkey].clone()
+wkey = [k for k in ops._STREAM_WS if k[0] == ("lora_grad_f32", M, H)][0]
+ws0 = ops._STREAM_WS[wkey].clone()
 # load generators
 Ml = 3152
 a3 = torch.randn(Ml, 3 * 768, device="cuda").bfloat16()
@@ -84,7 +84,7 @@ for it in range(N):
     load(sc, 3)
     dA, dB = run(sa)
     torch.cuda.synchronize()
-    ws = ops._LG32_WS[wkey]
+    ws = ops._STREAM_WS[wkey]
     if not (torch.equal(dA, dA0) and torch.equal(dB, dB0) and torch.equal(ws, ws0)):
         bad += 1
         d = (ws - ws0)
