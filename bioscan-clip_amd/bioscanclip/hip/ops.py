@@ -858,6 +858,20 @@ def class_topk(logits, C, k):
     return scores, idx
 
 
+def class_softmax_topk(logits, C, k):
+    """``F.softmax(logits[:, :C], -1)`` then ``torch.topk(..., k, sorted=True)`` in one kernel: (confidences f32 [B, k], class indices
+    int64 [B, k]) on the GPU, ordered by logit descending, ties to the lower class index.  ``logits`` as for ``class_topk``."""
+    ldc = _rowmajor(logits, "logits")
+    B = logits.shape[0]
+    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0,
+         "class_softmax_topk: logits f32 [B, >= C], row stride % 4 == 0")
+    _req(1 <= k <= min(16, C), "class_softmax_topk: 1 <= k <= 16, k <= C")
+    conf = torch.empty(B, k, dtype=F32, device=logits.device)
+    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
+    check(_l.load().bsclip_class_softmax_topk(_p(logits), ldc, B, C, k, _p(conf), _p(idx), _stream()))
+    return conf, idx
+
+
 def _lora_grad_workspace(H, device):
     return _stream_ws(("lora_grad", H), device, _l.load().bsclip_lora_grad_workspace_floats(H))
 

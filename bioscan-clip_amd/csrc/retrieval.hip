@@ -78,7 +78,20 @@ __device__ __forceinline__ void topk_insert(float (&v)[MAXK], int (&ix)[MAXK], f
 // Pass 2: re-scan (the slab is L2 / Infinity-Cache resident) and compact the few elements >= T into LDS.  Pass 3: exact
 // top-k of the candidates -- per-lane sorted lists in registers, then k rounds of a wavefront arg-max.  A row with more
 // than TOPK_CAND candidates (many equal scores) falls back to inserting every element, which is exact for any input.
-template <int MAXK>
+//
+// SOFTMAX (bsclip_class_softmax_topk): out_s receives the softmax confidences of the k winners instead of their scores.  Pass 1
+// also keeps ce_rows_kernel's per-lane running (max, sum exp) -- the lane maximum is that running maximum -- merged across the wave
+// into M and S; the winners' logits are in registers at the pop loop, so conf = expf(x - M) / S needs no further pass over the row.
+// Selection stays on the logits (softmax is monotone: distinct logits that round to equal confidences keep their order).  A NaN
+// logit is selected as +inf (torch.topk ranks a NaN first), so every index stays inside [0, K); it makes S, and with it every
+// confidence of its row, a NaN.
+template <bool SOFTMAX>
+__device__ __forceinline__ float topk_key(float x) {
+    if constexpr (SOFTMAX) return x != x ? INFINITY : x;
+    return x;
+}
+
+template <int MAXK, bool SOFTMAX = false>
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ scores, int ld, int nrows, int K, int k,
                                                          float* __restrict__ out_s, int64_t* __restrict__ out_i,
                                                          int out_ld) {
@@ -91,6 +104,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     const int K4 = (K + 3) & ~3;  // ld is a multiple of 128, so the last 16-B chunk is readable; columns >= K are masked
 
     float m = -INFINITY;
+    [[maybe_unused]] float ssum = 0.f, M = 0.f, S = 0.f;
     for (int c0 = lane * 4; c0 < K4; c0 += 1024) {
         f32x4 x[4];
 #pragma unroll
@@ -98,11 +112,34 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             const int c = c0 + u * 256;
             x[u] = c < K4 ? *reinterpret_cast<const f32x4*>(row + c) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         }
+        if constexpr (SOFTMAX) {
+            float gm = -INFINITY;
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c0 + u * 256 + e < K) m = fmaxf(m, x[u][e]);
+                for (int e = 0; e < 4; ++e)
+                    if (c0 + u * 256 + e < K) gm = fmaxf(gm, topk_key<true>(x[u][e]));
+            if (gm > m) {  // the running maximum moves: rescale what has been summed (exp(-inf) = 0 on the first trip)
+                ssum *= expf(m - gm);
+                m = gm;
+            }
+            if (m > -INFINITY) {  // a share of -inf logits only adds nothing (and -inf - -inf is no exponent)
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ssum += (c0 + u * 256 + e < K) ? expf(x[u][e] - m) : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c0 + u * 256 + e < K) m = fmaxf(m, x[u][e]);
+        }
+    }
+    if constexpr (SOFTMAX) {
+        M = wave_max(m);
+        S = wave_sum(m == -INFINITY ? 0.f : ssum * expf(m - M));  // fixed shuffle tree: the same bits on every call
     }
     // T = k-th largest lane maximum (rank by value, ties by lane)
     int rank = 0;
@@ -121,7 +158,10 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         if (c0 < K4) x = *reinterpret_cast<const f32x4*>(row + c0);
         bool hit = false;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) hit |= (c0 + e < K) && x[e] >= T;
+        for (int e = 0; e < 4; ++e) {
+            x[e] = topk_key<SOFTMAX>(x[e]);
+            hit |= (c0 + e < K) && x[e] >= T;
+        }
         if (__ballot(hit) == 0ull) continue;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -146,7 +186,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         __builtin_amdgcn_wave_barrier();
         for (int c = lane; c < count; c += 64) topk_insert<MAXK>(v, ix, cand_v[w][c], cand_i[w][c]);
     } else {
-        for (int c = lane; c < K; c += 64) topk_insert<MAXK>(v, ix, row[c], c);
+        for (int c = lane; c < K; c += 64) topk_insert<MAXK>(v, ix, topk_key<SOFTMAX>(row[c]), c);
     }
     for (int o = 0; o < k; ++o) {
         float bv = v[0];
@@ -160,7 +200,10 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             bi = take ? oi : bi;
         }
         if (lane == 0) {
-            out_s[(size_t)r * out_ld + o] = bv;
+            if constexpr (SOFTMAX)
+                out_s[(size_t)r * out_ld + o] = expf(bv - M) / S;
+            else
+                out_s[(size_t)r * out_ld + o] = bv;
             out_i[(size_t)r * out_ld + o] = bi;
         }
         if (ix[0] == bi) {  // the winning lane pops its head
@@ -278,6 +321,28 @@ extern "C" int bsclip_class_topk(const float* logits, int ldc, int B, int C, int
         hipLaunchKernelGGL((topk_rows_kernel<8>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
     else
         hipLaunchKernelGGL((topk_rows_kernel<16>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// ---- softmax confidences of the k highest class logits (method two: reference scripts/method_two_fine_tuning_and_eval.py:57-62,
+// `F.softmax(output, dim=-1)` then `torch.topk(..., k=5, dim=1, largest=True, sorted=True)`) -------------------------------------
+// The selection kernel above with SOFTMAX set: the same layout contract as bsclip_class_topk.  Order: by logit descending, ties to the
+// lower class index.
+
+extern "C" int bsclip_class_softmax_topk(const float* logits, int ldc, int B, int C, int k, float* conf_out, int64_t* idx_out,
+                                         void* stream) {
+    BSCLIP_REQUIRE(logits && conf_out && idx_out, "bsclip_class_softmax_topk: null pointer");
+    BSCLIP_REQUIRE(B >= 1 && C >= 1, "bsclip_class_softmax_topk: B=%d C=%d (both >= 1)", B, C);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "bsclip_class_softmax_topk: k=%d (1..16, <= C=%d)", k, C);
+    BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "bsclip_class_softmax_topk: ldc=%d (>= C=%d, a multiple of 4)", ldc, C);
+    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)conf_out) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
+                   "bsclip_class_softmax_topk: logits must be 16-byte, conf_out 4-byte, idx_out 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k <= 8)
+        hipLaunchKernelGGL((topk_rows_kernel<8, true>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, conf_out, idx_out, k);
+    else
+        hipLaunchKernelGGL((topk_rows_kernel<16, true>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, conf_out, idx_out, k);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

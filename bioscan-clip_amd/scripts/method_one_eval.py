@@ -192,15 +192,16 @@ def score_features_on_gpu(args, seen_keys, seen_key_labels, unseen_keys, unseen_
 
 
 def score_splits_on_gpu(args, splits, gt_labels, vocab, seen_key_labels, unseen_key_labels, searched_threshold=None,
-                        with_predictions=False, num_intervals=1000):
-    """Threshold search (unless given) and one output dictionary per ``MethodOneSplit``."""
+                        with_predictions=False, num_intervals=1000, grid=None):
+    """Threshold search (unless given) and one output dictionary per ``MethodOneSplit``.  ``grid``: the function that makes the
+    thresholds of ``num_intervals`` (default: method one's ``linspace_thresholds``; method two passes its own)."""
     from bioscanclip.hip.method_one import linspace_thresholds, merged_accuracy, pick_threshold, sweep
     k_list = _k_list(args)
     print("Searching best threshold.")
     if searched_threshold is None:
         if 1 not in k_list:
             raise KeyError(1)     # the host path reads micro_acc[1] in its threshold search
-        thresholds = linspace_thresholds(num_intervals)
+        thresholds = (grid or linspace_thresholds)(num_intervals)
         counts, totals = sweep(splits, thresholds, level="species", k=1)
         best_threshold = pick_threshold(counts, totals, thresholds)
     else:

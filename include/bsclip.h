@@ -462,6 +462,22 @@ int bsclip_ce_fwd_bwd(const float* logits, int ldc, const int32_t* targets, int 
                       float* dlogits, int ld_d, void* dlogits_split3, int ld_d3, int32_t* flag, void* stream);
 int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* scores_out, int64_t* idx_out, void* stream);
 
+/* ---- method two: classifier confidences (reference scripts/method_two_fine_tuning_and_eval.py) --------------------------
+ * class_softmax_topk: `F.softmax(output, dim=-1)` followed by `torch.topk(..., k=5, dim=1, largest=True, sorted=True)`
+ *   (method_two_fine_tuning_and_eval.py:57-62) in one pass over the logits plus the selection's re-scan: the k (<= 16, <= C)
+ *   highest softmax confidences of each row, conf_out f32 [B, k], and their class indices, idx_out int64 [B, k].  logits as for
+ *   bsclip_class_topk: f32 [B, ldc], ldc >= C, ldc % 4 == 0, 16-byte aligned; columns >= C are absent, not logits of 0.
+ *   conf = expf(x - M) / S in f32 with M the row maximum and S = sum_c expf(x_c - M) (logits of magnitude 1e4 are fine; a logit
+ *   of -inf has confidence 0); S is summed in a fixed order (no float atomics: a repeated call gives the same bits).
+ *   Tie rule: the order is by LOGIT descending, ties to the lower class index -- softmax is monotone, so this is torch.topk's
+ *   order wherever that is defined, also where distinct logits round to equal confidences.  A row that holds a NaN logit gets
+ *   NaN confidences; its indices stay inside [0, C) (a NaN ranks first, as in torch.topk).
+ *   The confidences feed the method-one merge kernels (bsclip_retrieval_match_bits on a class table [C, L] built from
+ *   idx_to_all_labels, bsclip_retrieval_threshold_sweep, bsclip_retrieval_merge_hit_ranks): decide_prediction_with_threshold
+ *   (:88-114) compares them strictly against the threshold, search_threshold_with_harmonic_mean (:177-204) sweeps
+ *   np.linspace(0, 1, num_intervals + 1). */
+int bsclip_class_softmax_topk(const float* logits, int ldc, int B, int C, int k, float* conf_out, int64_t* idx_out, void* stream);
+
 /* ---- RCCL collectives of the global-batch step ---------------------------------------------------
  * One process per GPU.  bsclip_comm_unique_id on rank 0 -> the caller ships the bsclip_comm_unique_id_bytes() bytes to the
  * other ranks (any channel) -> bsclip_comm_init on every rank (ncclCommInitRank).  The collectives run on `comm_stream`;
