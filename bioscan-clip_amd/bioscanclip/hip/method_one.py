@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .retrieval import LEVELS, Labels, assemble_accuracy
+from .retrieval import LEVELS, Labels, score_hit_ranks, to_gpu
 
 
 class MethodOneSplit:
@@ -32,8 +32,7 @@ class MethodOneSplit:
 
     def __init__(self, sim, idx_seen, seen_key_labels, idx_unseen, unseen_key_labels, query_labels, levels=None):
         dev = sim.device
-        as_labels = lambda x: x if isinstance(x, Labels) else Labels(x, dev)
-        self.seen_keys, self.unseen_keys, self.labels = as_labels(seen_key_labels), as_labels(unseen_key_labels), as_labels(query_labels)
+        self.seen_keys, self.unseen_keys, self.labels = (Labels.of(x, dev) for x in (seen_key_labels, unseen_key_labels, query_labels))
         if sim.shape[0] != self.labels.ids.shape[0] or idx_seen.shape != sim.shape or idx_unseen.shape != sim.shape:
             raise ValueError("sim, idx_seen and idx_unseen must be [Q, k] for the Q query labels")
         self.sim, self.idx_seen, self.idx_unseen = sim, idx_seen, idx_unseen
@@ -48,11 +47,8 @@ class MethodOneSplit:
     def from_queries(cls, seen_index, seen_key_labels, unseen_index, unseen_key_labels, queries, query_labels, max_k=5, levels=None):
         """Search the image ``queries`` (numpy or GPU tensor ``[Q, D]``) in the seen-key index (image features) and in the
         unseen-key index (DNA features), ``max_k`` deep; the key labels are ``Labels`` (or int32 arrays) in key order."""
-        if not torch.is_tensor(queries):
-            queries = torch.as_tensor(np.ascontiguousarray(queries, dtype=np.float32)).to(seen_index.device)
-        for index, labels in ((seen_index, seen_key_labels), (unseen_index, unseen_key_labels)):
-            if (labels.ids if isinstance(labels, Labels) else labels).shape[0] < index.K:
-                raise ValueError("fewer key labels than keys in an index")
+        queries = to_gpu(queries, seen_index.device)
+        seen_key_labels, unseen_key_labels = seen_index.key_labels(seen_key_labels), unseen_index.key_labels(unseen_key_labels)
         sim, idx_seen = seen_index.search(queries, int(max_k))
         _, idx_unseen = unseen_index.search(queries, int(max_k))
         return cls(sim, idx_seen, seen_key_labels, idx_unseen, unseen_key_labels, query_labels, levels=levels)
@@ -63,7 +59,7 @@ class MethodOneSplit:
         key = (id(member), level)
         if key not in self._members:
             l = self.levels.index(level)
-            table = member if torch.is_tensor(member) else torch.as_tensor(np.ascontiguousarray(member, dtype=np.int32)).to(self.sim.device)
+            table = to_gpu(member, self.sim.device, dtype=np.int32)
             self._members[key] = (member, ops.retrieval_match_bits(self.idx_seen, self.seen_keys.dev, member=table, level=l, flag=self.flag),
                                   ops.retrieval_match_bits(self.idx_unseen, self.unseen_keys.dev, member=table, level=l, flag=self.flag))
         return self._members[key][1:]
@@ -115,20 +111,8 @@ def pick_threshold(counts, totals, thresholds):
 def merged_accuracy(split, threshold, k_list, vocab=None):
     """The accuracy tables of the merged lists at ``threshold``: merge, class counts, ``assemble_accuracy``; one download.  Returns
     ``({"micro_acc": ..., "macro_acc": ...}, per_class_acc)`` like ``retrieval.evaluate``."""
-    k_list = list(k_list)
-    if not 1 <= len(k_list) <= 8 or min(k_list) < 1:
-        raise ValueError("k_list: 1 to 8 values, each >= 1")
-    ql = split.labels
-    offsets = ql.level_offsets
-    C, nk = offsets[-1], len(k_list)
-    buf = torch.empty(1 + (1 + nk) * C, dtype=torch.int32, device=split.sim.device)   # [flag | seen | right]
-    flag = buf[:1].copy_(split.flag)
     hit_rank = ops.retrieval_merge_hit_ranks(split.sim, split.A, split.B, threshold)
-    ops.retrieval_class_counts(hit_rank, ql.dev, offsets, [min(k, split.k) for k in k_list], flag=flag, out=buf[1:])
-    host = buf.cpu().numpy()
-    ops.check_retrieval_flag(int(host[0]))
-    return assemble_accuracy(host[1:1 + C], host[1 + C:].reshape(nk, C), ql.ids, offsets, k_list, class_order=ql.class_order,
-                             vocab=vocab, levels=split.levels)
+    return score_hit_ranks(hit_rank, split.labels, k_list, split.k, flag=split.flag, vocab=vocab, levels=split.levels)
 
 
 def member_share(split, threshold, member, ks=(1, 3, 5), level="species"):

@@ -25,7 +25,7 @@ from . import ops
 from ..epoch.eval_epoch import convert_label_dict_to_list_of_dict
 from .method_one import (MethodOneSplit, member_share, merged_accuracy, merged_predictions, pick_threshold,  # noqa: F401
                          sweep)
-from .retrieval import Labels
+from .retrieval import Labels, to_gpu
 
 try:  # optional, as in the epoch drivers
     from tqdm import tqdm
@@ -61,8 +61,8 @@ class MethodTwoSplit(MethodOneSplit):
     ``idx_seen`` the predicted class indices, ``seen_keys`` the class table."""
 
     def __init__(self, conf, class_idx, class_table, idx_unseen, unseen_key_labels, query_labels, levels=None):
-        table = class_table.ids if isinstance(class_table, Labels) else class_table
-        if conf.dim() != 2 or conf.shape[1] > table.shape[0]:
+        class_table = Labels.of(class_table, conf.device)
+        if conf.dim() != 2 or conf.shape[1] > class_table.ids.shape[0]:
             raise ValueError("conf must be [Q, k] with k <= the C rows of the class table")
         super().__init__(conf.contiguous(), class_idx.contiguous(), class_table, idx_unseen, unseen_key_labels, query_labels, levels=levels)
 
@@ -71,11 +71,9 @@ class MethodTwoSplit(MethodOneSplit):
         """``conf`` / ``class_idx`` from ``classifier_confidences``; ``query_features`` (numpy or GPU tensor ``[Q, D]``) are the
         ORIGINAL model's image features of the same queries, searched ``k`` deep in the unseen-key ``RetrievalIndex`` (DNA
         features); ``class_table`` / ``unseen_key_labels`` / ``query_labels`` are ``Labels`` or int32 arrays ``[., L]``."""
-        if not torch.is_tensor(query_features):
-            query_features = torch.as_tensor(np.ascontiguousarray(query_features, dtype=np.float32)).to(unseen_index.device)
+        query_features = to_gpu(query_features, unseen_index.device)
         if query_features.shape[0] != conf.shape[0]:
             raise ValueError("one row of query features per row of confidences")
-        if (unseen_key_labels.ids if isinstance(unseen_key_labels, Labels) else unseen_key_labels).shape[0] < unseen_index.K:
-            raise ValueError("fewer key labels than keys in the index")
+        unseen_key_labels = unseen_index.key_labels(unseen_key_labels)
         _, idx_unseen = unseen_index.search(query_features, int(conf.shape[1]))
         return cls(conf, class_idx, class_table, idx_unseen, unseen_key_labels, query_labels, levels=levels)

@@ -46,6 +46,13 @@ def _f32_shaped(t, shape, name):
         raise ValueError(f"{name} must be contiguous f32 {list(shape)}")
 
 
+def _i32(t, dev, msg, shape=None, dims=None):
+    # a contiguous int32 tensor on the GPU ``dev``, of ``shape`` or of one of ``dims`` dimensions; ``msg`` names the wrapper
+    if (t is None or t.dtype != torch.int32 or not t.is_contiguous() or not t.is_cuda or t.device != dev
+            or (shape is not None and tuple(t.shape) != tuple(shape)) or (dims is not None and t.dim() not in dims)):
+        raise ValueError(msg)
+
+
 def _lora_grads_ok(M, H, dt, dA, dBq, dBv):
     _req(dt.dtype == F32 and dt.is_contiguous() and dt.numel() >= 8 * M, "dt f32 [M,8]")
     _f32_shaped(dA, (8, H), "dA")
@@ -639,16 +646,21 @@ def infonce_fwd_bwd(zs, labels, scale, loss_out, dzs=None, row0=0, n_local=None,
                                            _p(workspace), _stream()))
 
 
+def _topk_outputs(queries, K, k, msg_q, msg_k):
+    """What ``topk_ip`` and ``topk_ip_indexed`` share: the query check and the outputs.  Returns (Q, D, scores, idx)."""
+    _req(queries.dim() == 2 and queries.dtype == F32 and queries.is_contiguous() and queries.is_cuda, msg_q)
+    Q, D = queries.shape
+    _req(Q >= 1 and 1 <= k <= min(16, K) and D % 64 == 0, msg_k)
+    return Q, D, torch.empty(Q, k, dtype=F32, device=queries.device), torch.empty(Q, k, dtype=torch.int64, device=queries.device)
+
+
 def topk_ip(queries, keys, k):
     """Top-k inner products of L2-normalised rows: returns (scores f32 [Q,k], indices int64 [Q,k]) on the GPU."""
-    Q, D = queries.shape
     K = keys.shape[0]
-    _req(queries.dtype == F32 and keys.dtype == F32 and queries.is_contiguous() and keys.is_contiguous()
-         and keys.shape[1] == D and queries.is_cuda and keys.is_cuda, "topk_ip: contiguous f32 GPU [Q,D], [K,D]")
-    _req(1 <= k <= min(16, K) and D % 64 == 0, "topk_ip: 1 <= k <= 16, D % 64 == 0")
+    msg = "topk_ip: contiguous f32 GPU [Q,D], [K,D]"
+    Q, D, scores, idx = _topk_outputs(queries, K, k, msg, "topk_ip: 1 <= k <= 16, D % 64 == 0")
+    _req(keys.dtype == F32 and keys.is_contiguous() and tuple(keys.shape) == (K, D) and keys.is_cuda, msg)
     ws = torch.empty(_l.load().bsclip_topk_ip_workspace_floats(Q, K, D), dtype=F32, device=queries.device)
-    scores = torch.empty(Q, k, dtype=F32, device=queries.device)
-    idx = torch.empty(Q, k, dtype=torch.int64, device=queries.device)
     check(_l.load().bsclip_topk_ip(_p(queries), Q, _p(keys), K, D, k, _p(scores), _p(idx), _p(ws), _stream()))
     return scores, idx
 
@@ -668,15 +680,11 @@ def retrieval_index_build(keys):
 
 def topk_ip_indexed(queries, index, K, k):
     """``topk_ip`` against a prebuilt index of K keys (``retrieval_index_build``): same kernels, bit-identical outputs."""
-    _req(queries.dim() == 2 and queries.dtype == F32 and queries.is_contiguous() and queries.is_cuda,
-         "topk_ip_indexed: contiguous f32 GPU [Q,D]")
-    Q, D = queries.shape
-    _req(Q >= 1 and 1 <= k <= min(16, K) and D % 64 == 0, "topk_ip_indexed: Q >= 1, 1 <= k <= 16, k <= K, D % 64 == 0")
+    Q, D, scores, idx = _topk_outputs(queries, K, k, "topk_ip_indexed: contiguous f32 GPU [Q,D]",
+                                      "topk_ip_indexed: Q >= 1, 1 <= k <= 16, k <= K, D % 64 == 0")
     _req(index.dtype == F32 and index.is_contiguous() and index.device == queries.device
          and index.numel() == _l.load().bsclip_retrieval_index_floats(K, D), "topk_ip_indexed: index is not that of [K,D] keys")
     ws = torch.empty(_l.load().bsclip_topk_ip_indexed_workspace_floats(Q, K, D), dtype=F32, device=queries.device)
-    scores = torch.empty(Q, k, dtype=F32, device=queries.device)
-    idx = torch.empty(Q, k, dtype=torch.int64, device=queries.device)
     check(_l.load().bsclip_topk_ip_indexed(_p(queries), Q, _p(index), K, D, k, _p(scores), _p(idx), _p(ws), _stream()))
     return scores, idx
 
@@ -703,9 +711,8 @@ def retrieval_hit_ranks(idx, key_labels, query_labels, flag=None):
     _req(idx.dim() == 2 and idx.dtype == torch.int64 and idx.is_contiguous() and idx.is_cuda, "retrieval_hit_ranks: idx int64 GPU [Q,k]")
     Q, k = idx.shape
     dev = idx.device
-    _req(key_labels.dim() == 2 and query_labels.dim() == 2 and key_labels.dtype == I32 and query_labels.dtype == I32
-         and key_labels.is_contiguous() and query_labels.is_contiguous() and key_labels.device == dev and query_labels.device == dev,
-         "retrieval_hit_ranks: labels int32 contiguous [K,L], [Q,L] on idx's GPU")
+    for labels in (key_labels, query_labels):
+        _i32(labels, dev, "retrieval_hit_ranks: labels int32 contiguous [K,L], [Q,L] on idx's GPU", dims=(2,))
     K, L = key_labels.shape
     _req(Q >= 1 and K >= 1 and 1 <= k <= 16 and 1 <= L <= 8 and tuple(query_labels.shape) == (Q, L),
          "retrieval_hit_ranks: 1 <= k <= 16, 1 <= L <= 8, query_labels [Q,L]")
@@ -720,9 +727,10 @@ def retrieval_hit_ranks(idx, key_labels, query_labels, flag=None):
 def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=None, out=None):
     """(seen int32 [C], right int32 [nk,C]) with C = level_offsets[-1]: queries per class and those hit within k_list[j].
     ``level_offsets`` / ``k_list`` are host sequences.  ``out``: an int32 buffer of (1 + nk) * C elements to hold both."""
-    _req(hit_rank.dim() == 2 and hit_rank.dtype == I32 and hit_rank.is_contiguous() and hit_rank.is_cuda
-         and query_labels.dtype == I32 and query_labels.is_contiguous() and query_labels.shape == hit_rank.shape
-         and query_labels.device == hit_rank.device, "retrieval_class_counts: hit_rank, query_labels int32 GPU [Q,L]")
+    dev = hit_rank.device
+    msg = "retrieval_class_counts: hit_rank, query_labels int32 GPU [Q,L]"
+    _i32(hit_rank, dev, msg, dims=(2,))
+    _i32(query_labels, dev, msg, shape=hit_rank.shape)
     Q, L = hit_rank.shape
     offs, ks = [int(o) for o in level_offsets], [int(k) for k in k_list]
     nk = len(ks)
@@ -730,11 +738,11 @@ def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=N
     _req(offs[0] == 0 and all(a <= b for a, b in zip(offs, offs[1:])) and offs[-1] >= 1 and min(ks) >= 1,
          "retrieval_class_counts: offsets start at 0 and do not decrease, k >= 1")
     C = offs[-1]
-    dev = hit_rank.device
     flag, own = _eval_flag(flag, dev)
     if out is None:
         out = torch.empty((1 + nk) * C, dtype=I32, device=dev)
-    _req(out.dtype == I32 and out.is_contiguous() and out.numel() == (1 + nk) * C and out.device == dev, "retrieval_class_counts: out int32 [(1+nk)*C]")
+    _i32(out, dev, "retrieval_class_counts: out int32 [(1+nk)*C]")
+    _req(out.numel() == (1 + nk) * C, "retrieval_class_counts: out int32 [(1+nk)*C]")
     seen, right = out[:C], out[C:].view(nk, C)
     c_offs, c_ks = (ctypes.c_int32 * (L + 1))(*offs), (ctypes.c_int32 * nk)(*ks)
     check(_l.load().bsclip_retrieval_class_counts(_p(hit_rank), _p(query_labels), Q, L, ctypes.cast(c_offs, ctypes.c_void_p),
@@ -747,9 +755,10 @@ def retrieval_class_counts(hit_rank, query_labels, level_offsets, k_list, flag=N
 def _masks(name, sim, A, B):
     _req(sim.dim() == 2 and sim.dtype == F32 and sim.is_contiguous() and sim.is_cuda, f"{name}: sim f32 contiguous GPU [Q,k]")
     Q, k = sim.shape
-    _req(A.dtype == I32 and B.dtype == I32 and A.is_contiguous() and B.is_contiguous() and A.dim() in (1, 2) and A.shape == B.shape
-         and A.shape[0] == Q and A.device == sim.device and B.device == sim.device,
-         f"{name}: A, B int32 contiguous [Q,L] (or [Q]) on sim's GPU")
+    msg = f"{name}: A, B int32 contiguous [Q,L] (or [Q]) on sim's GPU"
+    _i32(A, sim.device, msg, dims=(1, 2))
+    _i32(B, sim.device, msg, shape=A.shape)
+    _req(A.shape[0] == Q, msg)
     L = A.shape[1] if A.dim() == 2 else 1
     _req(Q >= 1 and 1 <= k <= 16 and 1 <= L <= 8, f"{name}: Q >= 1, 1 <= k <= 16, 1 <= L <= 8")
     return Q, k, L
@@ -762,18 +771,16 @@ def retrieval_match_bits(idx, key_labels, query_labels=None, member=None, level=
     _req(idx.dim() == 2 and idx.dtype == torch.int64 and idx.is_contiguous() and idx.is_cuda, "retrieval_match_bits: idx int64 GPU [Q,k]")
     Q, k = idx.shape
     dev = idx.device
-    _req(key_labels.dim() == 2 and key_labels.dtype == I32 and key_labels.is_contiguous() and key_labels.device == dev,
-         "retrieval_match_bits: key_labels int32 contiguous [K,L] on idx's GPU")
+    _i32(key_labels, dev, "retrieval_match_bits: key_labels int32 contiguous [K,L] on idx's GPU", dims=(2,))
     K, L = key_labels.shape
     _req(Q >= 1 and K >= 1 and 1 <= k <= 16 and 1 <= L <= 8, "retrieval_match_bits: Q, K >= 1, 1 <= k <= 16, 1 <= L <= 8")
     C = 0
     if member is None:
-        _req(query_labels is not None and query_labels.dtype == I32 and query_labels.is_contiguous() and query_labels.device == dev
-             and tuple(query_labels.shape) == (Q, L), "retrieval_match_bits: query_labels int32 contiguous [Q,L] on idx's GPU")
+        _i32(query_labels, dev, "retrieval_match_bits: query_labels int32 contiguous [Q,L] on idx's GPU", shape=(Q, L))
         bits = torch.empty(Q, L, dtype=I32, device=dev)
     else:
-        _req(member.dim() == 1 and member.dtype == I32 and member.is_contiguous() and member.device == dev and member.numel() >= 1,
-             "retrieval_match_bits: member int32 contiguous [C] on idx's GPU")
+        _i32(member, dev, "retrieval_match_bits: member int32 contiguous [C] on idx's GPU", dims=(1,))
+        _req(member.numel() >= 1, "retrieval_match_bits: member int32 contiguous [C] on idx's GPU")
         _req(0 <= int(level) < L, "retrieval_match_bits: 0 <= level < L")
         C, query_labels = member.numel(), None
         bits = torch.empty(Q, dtype=I32, device=dev)
@@ -804,7 +811,8 @@ def retrieval_threshold_sweep(sim, A, B, level, k_prime, thresholds, out=None):
     _req(0 <= int(level) < L and int(k_prime) >= 1, "retrieval_threshold_sweep: 0 <= level < L, k_prime >= 1")
     if out is None:
         out = torch.zeros(T, dtype=I32, device=sim.device)
-    _req(out.dtype == I32 and out.is_contiguous() and out.numel() == T and out.device == sim.device, "retrieval_threshold_sweep: out int32 [T]")
+    _i32(out, sim.device, "retrieval_threshold_sweep: out int32 [T]")
+    _req(out.numel() == T, "retrieval_threshold_sweep: out int32 [T]")
     check(_l.load().bsclip_retrieval_threshold_sweep(_p(sim), Q, k, _p(A), _p(B), L, int(level), int(k_prime), _p(thresholds), T,
                                                      _p(out), _stream()))
     return out
@@ -845,31 +853,27 @@ def ce_fwd_bwd(logits, targets, C, loss_out, row_loss, dlogits=None, dlogits_spl
         check_ce_flag(int(flag.item()))
 
 
+def _class_topk(name, logits, C, k):
+    ldc = _rowmajor(logits, "logits")
+    B = logits.shape[0]
+    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0, f"{name}: logits f32 [B, >= C], row stride % 4 == 0")
+    _req(1 <= k <= min(16, C), f"{name}: 1 <= k <= 16, k <= C")
+    out = torch.empty(B, k, dtype=F32, device=logits.device)
+    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
+    check(getattr(_l.load(), "bsclip_" + name)(_p(logits), ldc, B, C, k, _p(out), _p(idx), _stream()))
+    return out, idx
+
+
 def class_topk(logits, C, k):
     """The k (<= 16, <= C) largest of ``logits[:, :C]`` per row, descending, ties to the lower class index: (scores f32 [B, k],
     indices int64 [B, k]) on the GPU.  ``logits`` f32 [B, >= C] may be a view into a padded buffer (row stride % 4 == 0)."""
-    ldc = _rowmajor(logits, "logits")
-    B = logits.shape[0]
-    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0, "class_topk: logits f32 [B, >= C], row stride % 4 == 0")
-    _req(1 <= k <= min(16, C), "class_topk: 1 <= k <= 16, k <= C")
-    scores = torch.empty(B, k, dtype=F32, device=logits.device)
-    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
-    check(_l.load().bsclip_class_topk(_p(logits), ldc, B, C, k, _p(scores), _p(idx), _stream()))
-    return scores, idx
+    return _class_topk("class_topk", logits, C, k)
 
 
 def class_softmax_topk(logits, C, k):
     """``F.softmax(logits[:, :C], -1)`` then ``torch.topk(..., k, sorted=True)`` in one kernel: (confidences f32 [B, k], class indices
     int64 [B, k]) on the GPU, ordered by logit descending, ties to the lower class index.  ``logits`` as for ``class_topk``."""
-    ldc = _rowmajor(logits, "logits")
-    B = logits.shape[0]
-    _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0,
-         "class_softmax_topk: logits f32 [B, >= C], row stride % 4 == 0")
-    _req(1 <= k <= min(16, C), "class_softmax_topk: 1 <= k <= 16, k <= C")
-    conf = torch.empty(B, k, dtype=F32, device=logits.device)
-    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
-    check(_l.load().bsclip_class_softmax_topk(_p(logits), ldc, B, C, k, _p(conf), _p(idx), _stream()))
-    return conf, idx
+    return _class_topk("class_softmax_topk", logits, C, k)
 
 
 def _lora_grad_workspace(H, device):

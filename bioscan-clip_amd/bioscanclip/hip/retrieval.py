@@ -20,6 +20,14 @@ from . import ops
 LEVELS = ["order", "family", "genus", "species"]
 
 
+def to_gpu(x, device=None, dtype=np.float32):
+    """A numpy array (made contiguous ``dtype``, uploaded to ``device``, default ``"cuda"``) or a tensor (left where and what it is)
+    as a contiguous tensor: what the wrappers in ``ops`` take."""
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).to(torch.device(device if device is not None else "cuda"))
+    return x.contiguous()
+
+
 def encode_labels(*label_lists, levels=None):
     """Map the strings of each level to dense int32 ids shared by all the given label lists (each a list of ``{level: name}``).
 
@@ -58,6 +66,11 @@ class Labels:
         self.dev = torch.from_numpy(ids).to(torch.device(device if device is not None else "cuda"))
         self._order = None
 
+    @classmethod
+    def of(cls, labels, device=None):
+        """``labels`` itself when it is a ``Labels`` already, else the ``Labels`` of that int32 array on ``device``."""
+        return labels if isinstance(labels, cls) else cls(labels, device)
+
     @property
     def level_offsets(self):
         sizes = (self.ids.max(axis=0) + 1) if len(self.ids) else np.zeros(self.ids.shape[1], dtype=np.int64)
@@ -81,17 +94,21 @@ class RetrievalIndex:
     uploaded, L2-normalised and split into the search kernels' operand once; ``search`` only reads it."""
 
     def __init__(self, keys, device=None):
-        if not torch.is_tensor(keys):
-            keys = torch.as_tensor(np.ascontiguousarray(keys, dtype=np.float32)).to(torch.device(device if device is not None else "cuda"))
+        keys = to_gpu(keys, device)
         self.K, self.D = int(keys.shape[0]), int(keys.shape[1])
         self.device = keys.device
-        self.index = ops.retrieval_index_build(keys.contiguous())
+        self.index = ops.retrieval_index_build(keys)
 
     def search(self, queries, k):
         """(similarities f32 ``[Q, k]``, indices int64 ``[Q, k]``) as GPU tensors -- what ``ops.topk_ip(queries, keys, k)`` returns."""
-        if not torch.is_tensor(queries):
-            queries = torch.as_tensor(np.ascontiguousarray(queries, dtype=np.float32)).to(self.device)
-        return ops.topk_ip_indexed(queries.contiguous(), self.index, self.K, int(k))
+        return ops.topk_ip_indexed(to_gpu(queries, self.device), self.index, self.K, int(k))
+
+    def key_labels(self, labels):
+        """``labels`` (``Labels`` or int32 ``[K', L]``, in key order) as the ``Labels`` of this index's keys; K' < K raises."""
+        labels = Labels.of(labels, self.device)
+        if labels.ids.shape[0] < self.K:
+            raise ValueError(f"{labels.ids.shape[0]} key labels for an index of {self.K} keys")
+        return labels
 
 
 def assemble_accuracy(seen, right, query_ids, level_offsets, k_list, class_order=None, vocab=None, levels=None):
@@ -124,6 +141,31 @@ def assemble_accuracy(seen, right, query_ids, level_offsets, k_list, class_order
     return {"micro_acc": micro, "macro_acc": macro}, per_class
 
 
+def checked_k_list(k_list):
+    """``k_list`` as a list: 1 to 8 values, each >= 1 (what ``bsclip_retrieval_class_counts`` takes)."""
+    k_list = list(k_list)
+    if not 1 <= len(k_list) <= 8 or min(k_list) < 1:
+        raise ValueError("k_list: 1 to 8 values, each >= 1")
+    return k_list
+
+
+def score_hit_ranks(hit_rank, labels, k_list, depth, flag=None, vocab=None, levels=None):
+    """The accuracy tables of one cell from its hit ranks (int32 GPU ``[Q, L]``, each below ``depth`` or equal to it for no hit)
+    and the query ``Labels``: class counts, ONE download, the error-word check, ``assemble_accuracy``.  A k of ``k_list`` above
+    ``depth`` counts hits in the whole list, like the reference's ``pred[:k]``.  ``flag``: the int32 ``[1]`` word the kernels before
+    this one ORed their errors into (default: none so far).  Returns ``(acc, per_class)`` as ``evaluate`` does."""
+    k_list = checked_k_list(k_list)
+    offsets = labels.level_offsets
+    C, nk = offsets[-1], len(k_list)
+    buf = torch.empty(1 + (1 + nk) * C, dtype=torch.int32, device=hit_rank.device)   # [flag | seen | right]: one download per cell
+    word = buf[:1].zero_() if flag is None else buf[:1].copy_(flag)
+    ops.retrieval_class_counts(hit_rank, labels.dev, offsets, [min(k, depth) for k in k_list], flag=word, out=buf[1:])
+    host = buf.cpu().numpy()
+    ops.check_retrieval_flag(int(host[0]))
+    return assemble_accuracy(host[1:1 + C], host[1 + C:].reshape(nk, C), labels.ids, offsets, k_list, class_order=labels.class_order,
+                             vocab=vocab, levels=levels)
+
+
 def evaluate(index, key_label_ids, queries, query_label_ids, k_list, max_k=None, vocab=None, levels=None, return_indices=False):
     """One cell of the accuracy table on the GPU: search ``queries`` in ``index``, match labels, count per class.
 
@@ -133,25 +175,13 @@ def evaluate(index, key_label_ids, queries, query_label_ids, k_list, max_k=None,
     per_class)`` with ``per_class[k][level][class] = float`` -- the structures of ``top_k_micro_accuracy`` /
     ``top_k_macro_accuracy`` -- and, with ``return_indices``, the int64 ``[Q, max_k]`` GPU tensor of key indices as a third item.
     """
-    k_list = list(k_list)
-    if not 1 <= len(k_list) <= 8 or min(k_list) < 1:
-        raise ValueError("k_list: 1 to 8 values, each >= 1")
+    k_list = checked_k_list(k_list)                                   # before the search, which takes its depth from it
     max_k = max(k_list) if max_k is None else int(max_k)
-    kl = key_label_ids if isinstance(key_label_ids, Labels) else Labels(key_label_ids, index.device)
-    ql = query_label_ids if isinstance(query_label_ids, Labels) else Labels(query_label_ids, index.device)
-    if kl.ids.shape[0] < index.K:
-        raise ValueError(f"{kl.ids.shape[0]} key labels for an index of {index.K} keys")
+    kl, ql = index.key_labels(key_label_ids), Labels.of(query_label_ids, index.device)
     _, idx = index.search(queries, max_k)
     if idx.shape[0] != ql.ids.shape[0] or kl.ids.shape[1] != ql.ids.shape[1]:
         raise ValueError("query labels do not match the queries, or key and query labels differ in levels")
-    offsets = ql.level_offsets
-    C, nk = offsets[-1], len(k_list)
-    buf = torch.empty(1 + (1 + nk) * C, dtype=torch.int32, device=idx.device)   # [flag | seen | right]: one download per cell
-    flag = buf[:1].zero_()
+    flag = torch.zeros(1, dtype=torch.int32, device=idx.device)
     hit_rank = ops.retrieval_hit_ranks(idx, kl.dev, ql.dev, flag=flag)
-    ops.retrieval_class_counts(hit_rank, ql.dev, offsets, [min(k, max_k) for k in k_list], flag=flag, out=buf[1:])
-    host = buf.cpu().numpy()
-    ops.check_retrieval_flag(int(host[0]))
-    acc, per_class = assemble_accuracy(host[1:1 + C], host[1 + C:].reshape(nk, C), ql.ids, offsets, k_list,
-                                       class_order=ql.class_order, vocab=vocab, levels=levels)
+    acc, per_class = score_hit_ranks(hit_rank, ql, k_list, max_k, flag=flag, vocab=vocab, levels=levels)
     return (acc, per_class, idx) if return_indices else (acc, per_class)

@@ -63,3 +63,19 @@ def load_checked(module, state_dict, what, allow_missing=(), allow_unexpected=()
         raise RuntimeError(f"{what}: checkpoint does not match the parameter tree -- missing {missing[:8]} "
                            f"({len(missing)} keys), unexpected {unexpected[:8]} ({len(unexpected)} keys)")
     return res
+
+
+def load_model_and_checkpoint(args, device, ckpt_optional=False):
+    """How every script's ``main`` starts its model: ``load_clip_model`` on ``device``, then ``model_config.ckpt_path`` loaded
+    strictly (``load_checked``) unless ``model_config.load_ckpt`` is false.  ``ckpt_optional`` (supervised fine-tuning, which may
+    start from the encoders as initialised): a configuration without ``ckpt_path`` is no error either and ``allow_random_init``
+    defaults to true.  Returns ``(model, loaded)``."""
+    from ..model import simple_clip   # looked up per call: the tests replace load_clip_model
+    mc = args.model_config
+    if ckpt_optional and not hasattr(args, "allow_random_init"):
+        args.allow_random_init = True
+    model = simple_clip.load_clip_model(args, device)
+    if hasattr(mc, "load_ckpt") and mc.load_ckpt is False or ckpt_optional and not hasattr(mc, "ckpt_path"):
+        return model, False
+    load_checked(model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
+    return model, True

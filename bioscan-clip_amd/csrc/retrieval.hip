@@ -223,6 +223,15 @@ inline int pad_keys(int n) { return (n + 255) / 256 * 256; }  // multiple of 256
 
 }  // namespace
 
+// top-k over the rows of a matrix the caller owns: the register lists hold 8 entries up to k = 8, 16 above
+template <bool SOFTMAX>
+static void launch_topk_rows(const float* m, int ld, int nrows, int K, int k, float* out_s, int64_t* out_i, hipStream_t s) {
+    if (k <= 8)
+        hipLaunchKernelGGL((topk_rows_kernel<8, SOFTMAX>), dim3(ceil_div(nrows, 4)), dim3(256), 0, s, m, ld, nrows, K, k, out_s, out_i, k);
+    else
+        hipLaunchKernelGGL((topk_rows_kernel<16, SOFTMAX>), dim3(ceil_div(nrows, 4)), dim3(256), 0, s, m, ld, nrows, K, k, out_s, out_i, k);
+}
+
 extern "C" int64_t bsclip_topk_ip_workspace_floats(int Q, int K, int D) {
     if (Q <= 0 || K <= 0 || D <= 0) return -1;
     const int64_t Kp = pad_keys(K), Qs = Q < TOPK_SLAB ? Q : TOPK_SLAB;
@@ -245,28 +254,37 @@ static int topk_search(const float* queries, int Q, const bf16_t* kP, int K, int
                            queries + (size_t)q0 * D, nq, nq, D, qP);
         const int rc = bsclip_gemm_bf16(qP, 4 * D, kP, 4 * D, sc, Kp, nq, Kp, 4 * D, BSCLIP_EPI_F32, nullptr, stream);
         if (rc) return rc;
-        float* so = scores_out + (size_t)q0 * k;
-        int64_t* io = idx_out + (size_t)q0 * k;
-        if (k <= 8)
-            hipLaunchKernelGGL((topk_rows_kernel<8>), dim3(ceil_div(nq, 4)), dim3(256), 0, s, sc, Kp, nq, K, k, so, io, k);
-        else
-            hipLaunchKernelGGL((topk_rows_kernel<16>), dim3(ceil_div(nq, 4)), dim3(256), 0, s, sc, Kp, nq, K, k, so, io, k);
+        launch_topk_rows<false>(sc, Kp, nq, K, k, scores_out + (size_t)q0 * k, idx_out + (size_t)q0 * k, s);
     }
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
 
-extern "C" int bsclip_topk_ip(const float* queries, int Q, const float* keys, int K, int D, int k, float* scores_out,
-                              int64_t* idx_out, float* workspace, void* stream) {
-    BSCLIP_REQUIRE(queries && keys && scores_out && idx_out && workspace, "bsclip_topk_ip: null pointer");
-    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "bsclip_topk_ip: Q=%d K=%d D=%d (D %% 64 == 0)", Q, K, D);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "bsclip_topk_ip: k=%d (1..16, <= K)", k);
-    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0, "bsclip_topk_ip: workspace must be 16-B aligned");
+// The argument check of the two search entry points.  `indexed`: `keys` is the prebuilt key operand of bsclip_topk_ip_indexed, which
+// the kernels read in 16-byte chunks; bsclip_topk_ip builds its own at the head of the workspace.
+static int topk_check(const char* fn, const float* queries, const float* keys, int Q, int K, int D, int k, const float* scores_out,
+                      const int64_t* idx_out, const float* workspace, bool indexed) {
+    BSCLIP_REQUIRE(queries && keys && scores_out && idx_out && workspace, "%s: null pointer", fn);
+    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "%s: Q=%d K=%d D=%d (D %% 64 == 0)", fn, Q, K, D);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "%s: k=%d (1..16, <= K)", fn, k);
+    BSCLIP_REQUIRE(((((uintptr_t)workspace) | (indexed ? (uintptr_t)keys : 0)) & 15) == 0, "%s: %sworkspace must be 16-B aligned", fn,
+                   indexed ? "index and " : "");
+    return BSCLIP_OK;
+}
+
+// The key operand of the search, bf16 [pad_keys(K), 4 D]: what bsclip_retrieval_index_build keeps and bsclip_topk_ip rebuilds per call.
+static void build_key_operand(const float* keys, int K, int D, bf16_t* kP, void* stream) {
     const int Kp = pad_keys(K);
-    bf16_t* kP = reinterpret_cast<bf16_t*>(workspace);
     hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(Kp, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        keys, K, Kp, D, kP);
-    return topk_search(queries, Q, kP, K, D, k, scores_out, idx_out, workspace + al4((int64_t)Kp * 2 * D), stream);
+}
+
+extern "C" int bsclip_topk_ip(const float* queries, int Q, const float* keys, int K, int D, int k, float* scores_out,
+                              int64_t* idx_out, float* workspace, void* stream) {
+    if (const int rc = topk_check("bsclip_topk_ip", queries, keys, Q, K, D, k, scores_out, idx_out, workspace, false)) return rc;
+    bf16_t* kP = reinterpret_cast<bf16_t*>(workspace);
+    build_key_operand(keys, K, D, kP, stream);
+    return topk_search(queries, Q, kP, K, D, k, scores_out, idx_out, workspace + al4((int64_t)pad_keys(K) * 2 * D), stream);
 }
 
 // ---- key index: the key operand of bsclip_topk_ip, built once and searched many times ------------------------------------------
@@ -281,9 +299,7 @@ extern "C" int bsclip_retrieval_index_build(const float* keys, int K, int D, flo
     BSCLIP_REQUIRE(K > 0 && D > 0 && D % 64 == 0, "bsclip_retrieval_index_build: K=%d D=%d (D %% 64 == 0)", K, D);
     BSCLIP_REQUIRE((((uintptr_t)keys) & 15) == 0 && (((uintptr_t)index) & 15) == 0,
                    "bsclip_retrieval_index_build: keys and index must be 16-B aligned");
-    const int Kp = pad_keys(K);
-    hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(Kp, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       keys, K, Kp, D, reinterpret_cast<bf16_t*>(index));
+    build_key_operand(keys, K, D, reinterpret_cast<bf16_t*>(index), stream);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -296,11 +312,7 @@ extern "C" int64_t bsclip_topk_ip_indexed_workspace_floats(int Q, int K, int D) 
 
 extern "C" int bsclip_topk_ip_indexed(const float* queries, int Q, const float* index, int K, int D, int k, float* scores_out,
                                       int64_t* idx_out, float* workspace, void* stream) {
-    BSCLIP_REQUIRE(queries && index && scores_out && idx_out && workspace, "bsclip_topk_ip_indexed: null pointer");
-    BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "bsclip_topk_ip_indexed: Q=%d K=%d D=%d (D %% 64 == 0)", Q, K, D);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "bsclip_topk_ip_indexed: k=%d (1..16, <= K)", k);
-    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0 && (((uintptr_t)index) & 15) == 0,
-                   "bsclip_topk_ip_indexed: index and workspace must be 16-B aligned");
+    if (const int rc = topk_check("bsclip_topk_ip_indexed", queries, index, Q, K, D, k, scores_out, idx_out, workspace, true)) return rc;
     return topk_search(queries, Q, reinterpret_cast<const bf16_t*>(index), K, D, k, scores_out, idx_out, workspace, stream);
 }
 
@@ -308,21 +320,24 @@ extern "C" int bsclip_topk_ip_indexed(const float* queries, int Q, const float* 
 // The selection kernel of the retrieval search on a logits matrix the caller owns: its 16-byte chunk loads need 16-byte aligned
 // rows (ldc % 4 == 0) and ldc >= C rounded up to 4, which ldc >= C and ldc % 4 == 0 give; columns >= C are masked.
 
-extern "C" int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* scores_out, int64_t* idx_out,
-                                 void* stream) {
-    BSCLIP_REQUIRE(logits && scores_out && idx_out, "bsclip_class_topk: null pointer");
-    BSCLIP_REQUIRE(B >= 1 && C >= 1, "bsclip_class_topk: B=%d C=%d (both >= 1)", B, C);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "bsclip_class_topk: k=%d (1..16, <= C=%d)", k, C);
-    BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "bsclip_class_topk: ldc=%d (>= C=%d, a multiple of 4)", ldc, C);
-    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)scores_out) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
-                   "bsclip_class_topk: logits must be 16-byte, scores_out 4-byte, idx_out 8-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (k <= 8)
-        hipLaunchKernelGGL((topk_rows_kernel<8>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
-    else
-        hipLaunchKernelGGL((topk_rows_kernel<16>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, scores_out, idx_out, k);
+template <bool SOFTMAX>
+static int class_topk_checked(const char* fn, const float* logits, int ldc, int B, int C, int k, float* out_s, int64_t* idx_out,
+                              void* stream) {
+    const char* out_name = SOFTMAX ? "conf_out" : "scores_out";
+    BSCLIP_REQUIRE(logits && out_s && idx_out, "%s: null pointer", fn);
+    BSCLIP_REQUIRE(B >= 1 && C >= 1, "%s: B=%d C=%d (both >= 1)", fn, B, C);
+    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "%s: k=%d (1..16, <= C=%d)", fn, k, C);
+    BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "%s: ldc=%d (>= C=%d, a multiple of 4)", fn, ldc, C);
+    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)out_s) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
+                   "%s: logits must be 16-byte, %s 4-byte, idx_out 8-byte aligned", fn, out_name);
+    launch_topk_rows<SOFTMAX>(logits, ldc, B, C, k, out_s, idx_out, static_cast<hipStream_t>(stream));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
+}
+
+extern "C" int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* scores_out, int64_t* idx_out,
+                                 void* stream) {
+    return class_topk_checked<false>("bsclip_class_topk", logits, ldc, B, C, k, scores_out, idx_out, stream);
 }
 
 // ---- softmax confidences of the k highest class logits (method two: reference scripts/method_two_fine_tuning_and_eval.py:57-62,
@@ -332,19 +347,7 @@ extern "C" int bsclip_class_topk(const float* logits, int ldc, int B, int C, int
 
 extern "C" int bsclip_class_softmax_topk(const float* logits, int ldc, int B, int C, int k, float* conf_out, int64_t* idx_out,
                                          void* stream) {
-    BSCLIP_REQUIRE(logits && conf_out && idx_out, "bsclip_class_softmax_topk: null pointer");
-    BSCLIP_REQUIRE(B >= 1 && C >= 1, "bsclip_class_softmax_topk: B=%d C=%d (both >= 1)", B, C);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "bsclip_class_softmax_topk: k=%d (1..16, <= C=%d)", k, C);
-    BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "bsclip_class_softmax_topk: ldc=%d (>= C=%d, a multiple of 4)", ldc, C);
-    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)conf_out) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
-                   "bsclip_class_softmax_topk: logits must be 16-byte, conf_out 4-byte, idx_out 8-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (k <= 8)
-        hipLaunchKernelGGL((topk_rows_kernel<8, true>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, conf_out, idx_out, k);
-    else
-        hipLaunchKernelGGL((topk_rows_kernel<16, true>), dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, B, C, k, conf_out, idx_out, k);
-    BSCLIP_LAUNCH_CHECK();
-    return BSCLIP_OK;
+    return class_topk_checked<true>("bsclip_class_softmax_topk", logits, ldc, B, C, k, conf_out, idx_out, stream);
 }
 
 // ---- scoring on integer label ids (make_prediction's label lookup + top_k_micro_accuracy / top_k_macro_accuracy counts) -------
@@ -356,18 +359,31 @@ constexpr int EVAL_MAX_K = 8;
 constexpr int EVAL_FLAG_BAD_IDX = 1;    // an idx entry outside [0, K)
 constexpr int EVAL_FLAG_BAD_LABEL = 2;  // a query label outside its level's class range
 
-// 16 lanes per query (4 queries per wave, 16 per block); lane r < k owns rank r: it gathers the L labels of key idx[q, r] and a
-// ballot per level finds the first rank whose label equals the query's.  An idx outside [0, K) is flagged, never dereferenced.
-__global__ __launch_bounds__(256) void hit_ranks_kernel(const int64_t* __restrict__ idx, int Q, int k,
-                                                         const int* __restrict__ key_labels, int K,
-                                                         const int* __restrict__ query_labels, int L, int* __restrict__ hit_rank,
-                                                         int* __restrict__ flag) {
+struct RankSlot {
+    int q, r, sub;  // the query, the rank this lane owns and the query's 16-lane group inside the wave
+    int64_t id;     // idx[q, r]
+    bool ok;        // r < k of a query < Q and id inside [0, K)
+};
+
+// 16 lanes per query (4 queries per wave, 16 per block); lane r < k owns rank r.  An idx outside [0, K) is flagged, never dereferenced.
+__device__ __forceinline__ RankSlot rank_slot(const int64_t* __restrict__ idx, int Q, int k, int K, int* __restrict__ flag) {
     const int lane = threadIdx.x & 63, sub = lane >> 4, r = lane & 15;
     const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool inq = q < Q && r < k;
     const int64_t id = inq ? idx[(size_t)q * k + r] : 0;
     const bool ok = inq && id >= 0 && id < K;
     if (inq && !ok) atomicOr(flag, EVAL_FLAG_BAD_IDX);
+    return {q, r, sub, id, ok};
+}
+
+// Every lane gathers the L labels of its slot's key and a ballot per level says which ranks carry the query's label;
+// store(q * L + l, g) receives the 16 bits of the query's lane group.
+template <class Store>
+__device__ __forceinline__ void match_levels(const RankSlot s, const int* __restrict__ key_labels, const int* __restrict__ query_labels,
+                                             int Q, int L, Store store) {
+    const int q = s.q, r = s.r, sub = s.sub;
+    const int64_t id = s.id;
+    const bool ok = s.ok;
     int kl[EVAL_MAX_LEVELS];
 #pragma unroll
     for (int l = 0; l < EVAL_MAX_LEVELS; ++l) kl[l] = (ok && l < L) ? key_labels[(size_t)id * L + l] : 0;
@@ -376,9 +392,17 @@ __global__ __launch_bounds__(256) void hit_ranks_kernel(const int64_t* __restric
         if (l >= L) break;  // wave-uniform
         const int ql = q < Q ? query_labels[(size_t)q * L + l] : 0;
         const unsigned long long b = __ballot(ok && kl[l] == ql);
-        const unsigned g = (unsigned)(b >> (sub * 16)) & 0xffffu;
-        if (r == l && q < Q) hit_rank[(size_t)q * L + l] = g ? __ffs(g) - 1 : k;
+        if (r == l && q < Q) store((size_t)q * L + l, (unsigned)(b >> (sub * 16)) & 0xffffu);
     }
+}
+
+// hit_rank[q, l] = the first rank whose level-l label equals the query's, or k
+__global__ __launch_bounds__(256) void hit_ranks_kernel(const int64_t* __restrict__ idx, int Q, int k,
+                                                         const int* __restrict__ key_labels, int K,
+                                                         const int* __restrict__ query_labels, int L, int* __restrict__ hit_rank,
+                                                         int* __restrict__ flag) {
+    match_levels(rank_slot(idx, Q, k, K, flag), key_labels, query_labels, Q, L,
+                 [=](size_t at, unsigned g) { hit_rank[at] = g ? __ffs(g) - 1 : k; });
 }
 
 struct CountCfg {
@@ -433,30 +457,16 @@ __global__ __launch_bounds__(256) void match_bits_kernel(const int64_t* __restri
                                                           const int* __restrict__ query_labels, int L,
                                                           const int* __restrict__ member, int C, int level,
                                                           int* __restrict__ bits, int* __restrict__ flag) {
-    const int lane = threadIdx.x & 63, sub = lane >> 4, r = lane & 15;
-    const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const bool inq = q < Q && r < k;
-    const int64_t id = inq ? idx[(size_t)q * k + r] : 0;
-    const bool ok = inq && id >= 0 && id < K;
-    if (inq && !ok) atomicOr(flag, EVAL_FLAG_BAD_IDX);
+    const RankSlot s = rank_slot(idx, Q, k, K, flag);
     if (member) {  // kernel-uniform
-        const int lab = ok ? key_labels[(size_t)id * L + level] : 0;
-        const bool inr = ok && lab >= 0 && lab < C;
-        if (ok && !inr) atomicOr(flag, EVAL_FLAG_BAD_LABEL);
+        const int lab = s.ok ? key_labels[(size_t)s.id * L + level] : 0;
+        const bool inr = s.ok && lab >= 0 && lab < C;
+        if (s.ok && !inr) atomicOr(flag, EVAL_FLAG_BAD_LABEL);
         const unsigned long long b = __ballot(inr && member[lab] != 0);
-        if (r == 0 && q < Q) bits[q] = (int)((unsigned)(b >> (sub * 16)) & 0xffffu);
+        if (s.r == 0 && s.q < Q) bits[s.q] = (int)((unsigned)(b >> (s.sub * 16)) & 0xffffu);
         return;
     }
-    int kl[EVAL_MAX_LEVELS];
-#pragma unroll
-    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) kl[l] = (ok && l < L) ? key_labels[(size_t)id * L + l] : 0;
-#pragma unroll
-    for (int l = 0; l < EVAL_MAX_LEVELS; ++l) {
-        if (l >= L) break;  // wave-uniform
-        const int ql = q < Q ? query_labels[(size_t)q * L + l] : 0;
-        const unsigned long long b = __ballot(ok && kl[l] == ql);
-        if (r == l && q < Q) bits[(size_t)q * L + l] = (int)((unsigned)(b >> (sub * 16)) & 0xffffu);
-    }
+    match_levels(s, key_labels, query_labels, Q, L, [=](size_t at, unsigned g) { bits[at] = (int)g; });
 }
 
 // bit r set exactly when slot r takes the seen-key prediction: (double)sim[q, r] > t, strict, false for a NaN
@@ -513,12 +523,16 @@ __global__ __launch_bounds__(256) void threshold_sweep_kernel(const float* __res
 
 }  // namespace
 
+// the rank depth and level count every scoring entry point takes
+#define EVAL_REQUIRE_K(fn) BSCLIP_REQUIRE(k >= 1 && k <= 16, fn ": k=%d (1..16)", k)
+#define EVAL_REQUIRE_L(fn) BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, fn ": L=%d (1..%d)", L, EVAL_MAX_LEVELS)
+
 extern "C" int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, const int32_t* key_labels, int K,
                                           const int32_t* query_labels, int L, int32_t* hit_rank, int32_t* flag, void* stream) {
     BSCLIP_REQUIRE(idx && key_labels && query_labels && hit_rank && flag, "bsclip_retrieval_hit_ranks: null pointer");
     BSCLIP_REQUIRE(Q > 0 && K > 0, "bsclip_retrieval_hit_ranks: Q=%d K=%d", Q, K);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_hit_ranks: k=%d (1..16)", k);
-    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_hit_ranks: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    EVAL_REQUIRE_K("bsclip_retrieval_hit_ranks");
+    EVAL_REQUIRE_L("bsclip_retrieval_hit_ranks");
     BSCLIP_REQUIRE((((uintptr_t)idx) & 7) == 0 && ((((uintptr_t)key_labels) | ((uintptr_t)query_labels) | ((uintptr_t)hit_rank) |
                                                     ((uintptr_t)flag)) & 3) == 0,
                    "bsclip_retrieval_hit_ranks: idx must be 8-B aligned, the int32 buffers 4-B aligned");
@@ -534,7 +548,7 @@ extern "C" int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int3
     BSCLIP_REQUIRE(hit_rank && query_labels && level_offsets && k_list && seen && right && flag,
                    "bsclip_retrieval_class_counts: null pointer");
     BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_class_counts: Q=%d", Q);
-    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_class_counts: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    EVAL_REQUIRE_L("bsclip_retrieval_class_counts");
     BSCLIP_REQUIRE(nk >= 1 && nk <= EVAL_MAX_K, "bsclip_retrieval_class_counts: nk=%d (1..%d)", nk, EVAL_MAX_K);
     BSCLIP_REQUIRE(((((uintptr_t)hit_rank) | ((uintptr_t)query_labels) | ((uintptr_t)seen) | ((uintptr_t)right) | ((uintptr_t)flag)) &
                     3) == 0, "bsclip_retrieval_class_counts: the int32 buffers must be 4-B aligned");
@@ -567,8 +581,8 @@ extern "C" int bsclip_retrieval_match_bits(const int64_t* idx, int Q, int k, con
                                            int32_t* bits, int32_t* flag, void* stream) {
     BSCLIP_REQUIRE(idx && key_labels && bits && flag && (member || query_labels), "bsclip_retrieval_match_bits: null pointer");
     BSCLIP_REQUIRE(Q > 0 && K > 0, "bsclip_retrieval_match_bits: Q=%d K=%d", Q, K);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_match_bits: k=%d (1..16)", k);
-    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_match_bits: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    EVAL_REQUIRE_K("bsclip_retrieval_match_bits");
+    EVAL_REQUIRE_L("bsclip_retrieval_match_bits");
     if (member) {
         BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_match_bits: level=%d (0 <= level < L=%d)", level, L);
         BSCLIP_REQUIRE(C > 0, "bsclip_retrieval_match_bits: C=%d member entries", C);
@@ -586,8 +600,8 @@ extern "C" int bsclip_retrieval_merge_hit_ranks(const float* sim, int Q, int k, 
                                                 double threshold, int32_t* hit_rank, void* stream) {
     BSCLIP_REQUIRE(sim && A && B && hit_rank, "bsclip_retrieval_merge_hit_ranks: null pointer");
     BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_merge_hit_ranks: Q=%d", Q);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_merge_hit_ranks: k=%d (1..16)", k);
-    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_merge_hit_ranks: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    EVAL_REQUIRE_K("bsclip_retrieval_merge_hit_ranks");
+    EVAL_REQUIRE_L("bsclip_retrieval_merge_hit_ranks");
     BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)hit_rank)) & 3) == 0,
                    "bsclip_retrieval_merge_hit_ranks: sim and the int32 buffers must be 4-B aligned");
     hipLaunchKernelGGL(merge_hit_ranks_kernel, dim3(ceil_div(Q, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), sim, Q, k, A,
@@ -600,8 +614,8 @@ extern "C" int bsclip_retrieval_threshold_sweep(const float* sim, int Q, int k, 
                                                 int k_prime, const double* thresholds, int T, int32_t* counts, void* stream) {
     BSCLIP_REQUIRE(sim && A && B && thresholds && counts, "bsclip_retrieval_threshold_sweep: null pointer");
     BSCLIP_REQUIRE(Q > 0 && T > 0, "bsclip_retrieval_threshold_sweep: Q=%d T=%d", Q, T);
-    BSCLIP_REQUIRE(k >= 1 && k <= 16, "bsclip_retrieval_threshold_sweep: k=%d (1..16)", k);
-    BSCLIP_REQUIRE(L >= 1 && L <= EVAL_MAX_LEVELS, "bsclip_retrieval_threshold_sweep: L=%d (1..%d)", L, EVAL_MAX_LEVELS);
+    EVAL_REQUIRE_K("bsclip_retrieval_threshold_sweep");
+    EVAL_REQUIRE_L("bsclip_retrieval_threshold_sweep");
     BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_threshold_sweep: level=%d (0 <= level < L=%d)", level, L);
     BSCLIP_REQUIRE(k_prime >= 1, "bsclip_retrieval_threshold_sweep: k_prime=%d (>= 1)", k_prime);
     BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)counts)) & 3) == 0 &&

@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from bioscanclip.epoch.inference_epoch import get_feature_and_label  # noqa: E402
 from bioscanclip.hip import ops  # noqa: E402
+from bioscanclip.hip.retrieval import LEVELS, to_gpu  # noqa: E402
 
 All_TYPE_OF_FEATURES_OF_QUERY = [
     "encoded_image_feature",
@@ -33,7 +34,6 @@ All_TYPE_OF_FEATURES_OF_QUERY = [
     "concatenated_feature",
 ]
 All_TYPE_OF_FEATURES_OF_KEY = All_TYPE_OF_FEATURES_OF_QUERY + ["all_key_features"]
-LEVELS = ["order", "family", "genus", "species"]
 
 
 def search_topk(query_feature, keys_feature, max_k, device=None):
@@ -42,10 +42,7 @@ def search_topk(query_feature, keys_feature, max_k, device=None):
     The arithmetic of ``normalize`` + ``IndexFlatIP.add`` + ``.search`` (:415-422) on the GPU.  There is no CPU path: without
     the HIP library or a GPU this raises.
     """
-    device = torch.device(device if device is not None else "cuda")
-    q = torch.as_tensor(np.ascontiguousarray(query_feature, dtype=np.float32)).to(device)
-    k = torch.as_tensor(np.ascontiguousarray(keys_feature, dtype=np.float32)).to(device)
-    sims, idx = ops.topk_ip(q, k, int(max_k))
+    sims, idx = ops.topk_ip(to_gpu(query_feature, device), to_gpu(keys_feature, device), int(max_k))
     return sims.cpu().numpy(), idx.cpu().numpy()
 
 
@@ -165,12 +162,23 @@ def inference_and_print_result(keys_dict, seen_dict, unseen_dict, args=None, sma
 HIP_EVAL_MODES = ("host", "gpu")
 
 
-def select_eval(args):
-    """``hip_eval=host`` (default): ``inference_and_print_result``; ``hip_eval=gpu``: ``inference_and_print_result_gpu``."""
+def eval_mode(args):
+    """``hip_eval=host`` (default) or ``gpu``; anything else is refused."""
     mode = str(getattr(args, "hip_eval", "host"))
     if mode not in HIP_EVAL_MODES:
         raise ValueError(f"hip_eval must be one of {HIP_EVAL_MODES}, not {mode!r}")
-    return inference_and_print_result_gpu if mode == "gpu" else inference_and_print_result
+    return mode
+
+
+def select_eval(args):
+    """``hip_eval=host`` (default): ``inference_and_print_result``; ``hip_eval=gpu``: ``inference_and_print_result_gpu``."""
+    return inference_and_print_result_gpu if eval_mode(args) == "gpu" else inference_and_print_result
+
+
+def _k_list(args):
+    """``args.inference_and_eval_setting.k_list``; a configuration without the setting gets 1, 3, 5."""
+    ies = getattr(args, "inference_and_eval_setting", None)
+    return list(getattr(ies, "k_list", [1, 3, 5])) if ies is not None else [1, 3, 5]
 
 
 def inference_and_print_result_gpu(keys_dict, seen_dict, unseen_dict, args=None, small_species_list=None, k_list=None,
@@ -197,7 +205,7 @@ def inference_and_print_result_gpu(keys_dict, seen_dict, unseen_dict, args=None,
 
     def query_of(split, q, feature):
         if (split, q) not in queries:
-            queries[split, q] = torch.as_tensor(np.ascontiguousarray(feature, dtype=np.float32)).to("cuda")
+            queries[split, q] = to_gpu(feature)
         return queries[split, q]
 
     keys_label = "label_list"
@@ -242,10 +250,9 @@ def main(argv=None):
     format it was extracted with and is reused only by a run of the same format.  ``hip_eval=gpu`` (default host) scores the
     table with ``inference_and_print_result_gpu``."""
     from bioscanclip.hip.engine import OPERAND_FORMATS, set_operand_format
-    from bioscanclip.model.simple_clip import load_clip_model
     from bioscanclip.util.config import load_config
     from bioscanclip.util.synthetic import SyntheticEvalLoader
-    from bioscanclip.util.util import load_checked, remove_extra_pre_fix
+    from bioscanclip.util.util import load_model_and_checkpoint
     here = os.path.dirname(os.path.abspath(__file__))
     args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
     mc = args.model_config
@@ -253,8 +260,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("inference_and_eval needs a ROCm GPU: the encoders and the top-k search run in libbsclip_hip.so")
     device = torch.device("cuda", 0)
-    ies = getattr(args, "inference_and_eval_setting", None)
-    k_list = list(getattr(ies, "k_list", [1, 3, 5])) if ies is not None else [1, 3, 5]
+    k_list = _k_list(args)
     root = str(getattr(args, "project_root_path", "."))
     folder = os.path.join(root, "extracted_embedding", str(getattr(mc, "dataset", "synthetic")), str(mc.model_output_name))
     feats_path = os.path.join(folder, "extracted_feature_from_val_split.npz")
@@ -271,12 +277,8 @@ def main(argv=None):
             print(f"Cached features were extracted with {cached} operands, this run uses {operands}: extracting again")
     if splits is None:
         print("Initialize model...")
-        model = load_clip_model(args, device)
+        model, _ = load_model_and_checkpoint(args, device)
         set_operand_format(model, operands)
-        if hasattr(mc, "load_ckpt") and mc.load_ckpt is False:
-            pass
-        else:
-            load_checked(model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
         model.eval()
         with_text = hasattr(mc, "language")
         bs, n = 24, int(getattr(args, "synthetic_eval_batches", 2))   # the reference evaluates at batch 24 (:846)

@@ -36,25 +36,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from bioscanclip.epoch.inference_epoch import get_feature_and_label  # noqa: E402
 from bioscanclip.hip.method_one import harmonic_mean as _harmonic_mean  # noqa: E402
-from inference_and_eval import LEVELS, make_prediction, top_k_macro_accuracy, top_k_micro_accuracy  # noqa: E402
+from inference_and_eval import (LEVELS, _k_list, eval_mode, make_prediction, top_k_macro_accuracy,  # noqa: E402
+                                top_k_micro_accuracy)
 
 K_LIST = None
-HIP_EVAL_MODES = ("host", "gpu")
 MAX_K = 5   # the search depth of both searches (:50, :54)
-
-
-def eval_mode(args):
-    """``hip_eval=host`` (default) or ``gpu``; anything else is refused (``inference_and_eval.select_eval``)."""
-    mode = str(getattr(args, "hip_eval", "host"))
-    if mode not in HIP_EVAL_MODES:
-        raise ValueError(f"hip_eval must be one of {HIP_EVAL_MODES}, not {mode!r}")
-    return mode
-
-
-def _k_list(args):
-    """``args.inference_and_eval_setting.k_list``; a configuration without the setting gets 1, 3, 5 (``inference_and_eval.main``)."""
-    ies = getattr(args, "inference_and_eval_setting", None)
-    return list(getattr(ies, "k_list", [1, 3, 5])) if ies is not None else [1, 3, 5]
+# the keys of one split's dictionary in search_threshold_with_harmonic_mean: the two lists of the first search, the second's, the truth
+SPLIT_KEYS = ('pred_labels_from_search_with_seen_keys', 'pred_similarity_from_search_with_seen_keys',
+              'pred_labels_from_search_with_unseen_keys', 'gt_label')
 
 
 def _key_features(original_model, key_dataloaders, device, key_type):
@@ -102,39 +91,47 @@ def get_final_pred_and_acc(args, pred_labels_from_search_with_seen_keys, similar
             "per_class_acc": per_class_acc}
 
 
+def merge_checked(args, names, lists, gt_labels, threshold):
+    """``make_final_pred`` of both methods: ``lists`` = (first predictions, their scores, second predictions), ``names`` what the
+    length report calls them."""
+    n = [len(x) for x in lists]
+    if n[0] != n[1] != n[2]:   # the reference's chained comparison (:107-108), kept as it is
+        for name, count in zip(names, n):
+            print(f"{name}: {count}")
+        sys.exit()
+    return decide_prediction_with_threshold(args, *lists, threshold), gt_labels
+
+
 def make_final_pred(args, pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
                     pred_labels_from_search_with_unseen_keys, gt_labels, threshold):
-    n = [len(pred_labels_from_search_with_seen_keys), len(similarity_from_search_with_seen_keys),
-         len(pred_labels_from_search_with_unseen_keys)]
-    if n[0] != n[1] != n[2]:   # the reference's chained comparison (:107-108), kept as it is
-        print(f"pred_labels_from_search_with_seen_keys: {n[0]}")
-        print(f"similarity_from_search_with_seen_keys: {n[1]}")
-        print(f"pred_labels_from_search_with_unseen_keys: {n[2]}")
-        sys.exit()
-    return decide_prediction_with_threshold(args, pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
-                                            pred_labels_from_search_with_unseen_keys, threshold), gt_labels
+    names = ('pred_labels_from_search_with_seen_keys', 'similarity_from_search_with_seen_keys', 'pred_labels_from_search_with_unseen_keys')
+    return merge_checked(args, names, (pred_labels_from_search_with_seen_keys, similarity_from_search_with_seen_keys,
+                                       pred_labels_from_search_with_unseen_keys), gt_labels, threshold)
 
 
 def harmonic_mean(l):
     return _harmonic_mean(l)
 
 
-def search_threshold_with_harmonic_mean(args, all_split_data, num_intervals=1000):
-    """Host path: every merged list is rebuilt for every threshold, as the reference does (no progress bar)."""
+def search_threshold(args, all_split_data, grid, keys, make_final_pred):
+    """``search_threshold_with_harmonic_mean`` of both methods over the thresholds ``grid``; ``keys`` name a split's four entries in
+    ``make_final_pred``'s order."""
     best_threshold, max_score = None, float('-inf')
     k_list = _k_list(args)
-    for threshold in np.linspace(0, 1, num_intervals):
+    for threshold in grid:
         acc_list = []
         for split in all_split_data:
-            final_pred_labels, gt_labels = make_final_pred(args, split['pred_labels_from_search_with_seen_keys'],
-                                                           split['pred_similarity_from_search_with_seen_keys'],
-                                                           split['pred_labels_from_search_with_unseen_keys'], split['gt_label'],
-                                                           threshold=threshold)
+            final_pred_labels, gt_labels = make_final_pred(args, *(split[key] for key in keys), threshold=threshold)
             acc_list.append(top_k_micro_accuracy(final_pred_labels, gt_labels, k_list=k_list)[1]['species'])
         score = harmonic_mean(acc_list)
         if score > max_score:
             max_score, best_threshold = score, threshold
     return best_threshold
+
+
+def search_threshold_with_harmonic_mean(args, all_split_data, num_intervals=1000):
+    """Host path: every merged list is rebuilt for every threshold, as the reference does (no progress bar)."""
+    return search_threshold(args, all_split_data, np.linspace(0, 1, num_intervals), SPLIT_KEYS, make_final_pred)
 
 
 def get_all_unique_species_from_dataloader(dataloader):
@@ -240,14 +237,11 @@ def method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_q
 def score_predictions_on_host(args, seen, unseen, searched_threshold=None, num_intervals=1000):
     """The host path from predictions on: each of ``seen`` / ``unseen`` is (seen-key predictions, similarities as lists,
     unseen-key predictions, ground truth)."""
-    data = [{'pred_labels_from_search_with_seen_keys': s[0], 'pred_similarity_from_search_with_seen_keys': s[1],
-             'pred_labels_from_search_with_unseen_keys': s[2], 'gt_label': s[3]} for s in (seen, unseen)]
     print("Searching best threshold.")
     if searched_threshold is None:
-        best_threshold = search_threshold_with_harmonic_mean(args, data, num_intervals=num_intervals)
-    else:
-        best_threshold = searched_threshold
-    return tuple(get_final_pred_and_acc(args, s[0], s[1], s[2], s[3], best_threshold=best_threshold) for s in (seen, unseen))
+        searched_threshold = search_threshold_with_harmonic_mean(args, [dict(zip(SPLIT_KEYS, s)) for s in (seen, unseen)],
+                                                                 num_intervals=num_intervals)
+    return tuple(get_final_pred_and_acc(args, *s, best_threshold=searched_threshold) for s in (seen, unseen))
 
 
 def print_acc_for_google_doc(seen_output_dict, unseen_output_dict, K_LIST=None):
@@ -287,10 +281,9 @@ def main(argv=None):
     ``SyntheticEvalLoader`` with distinct seeds.  The reference's last membership check passes the test-unseen species list twice
     (:358-359); here the unseen queries are checked against val + test unseen species in both places.  ``hip_eval=gpu`` (default
     host) scores on the GPU.  Returns ``{"val": (seen, unseen), "test": (seen, unseen)}`` output dictionaries."""
-    from bioscanclip.model.simple_clip import load_clip_model
     from bioscanclip.util.config import load_config
     from bioscanclip.util.synthetic import SyntheticEvalLoader
-    from bioscanclip.util.util import load_checked, remove_extra_pre_fix
+    from bioscanclip.util.util import load_model_and_checkpoint
     here = os.path.dirname(os.path.abspath(__file__))
     args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
     eval_mode(args)
@@ -309,30 +302,23 @@ def main(argv=None):
     mk = lambda seed: SyntheticEvalLoader(bs, n, with_text=False, seed=seed)
     seen_keys, val_unseen_keys, test_unseen_keys = mk(5301), mk(5302), mk(5303)
     seen_val, unseen_val, seen_test, unseen_test = mk(5304), mk(5305), mk(5306), mk(5307)
-    original_model = load_clip_model(args, device)
-    if not (hasattr(mc, "load_ckpt") and mc.load_ckpt is False):
-        load_checked(original_model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
+    original_model, _ = load_model_and_checkpoint(args, device)
     original_model.eval()
 
-    val = method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_val, unseen_val, seen_keys, val_unseen_keys,
-                                                          test_unseen_keys, device)
-    print_acc_for_google_doc(*val, K_LIST=K_LIST)
     seen_species = get_all_unique_species_from_dataloader(seen_keys)
     unseen_species = (get_all_unique_species_from_dataloader(val_unseen_keys)
                       + get_all_unique_species_from_dataloader(test_unseen_keys))
-    print("For seen")
-    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(val[0]), seen_species)
-    print("For unseen")
-    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(val[1]), unseen_species)
-
-    test = method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen_test, unseen_test, seen_keys, val_unseen_keys,
-                                                           test_unseen_keys, device, searched_threshold=val[0]['best_threshold'])
-    print_acc_for_google_doc(*test, K_LIST=K_LIST)
-    print("For seen")
-    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(test[0]), seen_species)
-    print("For unseen")
-    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(test[1]), unseen_species)
-    return {"val": val, "test": test}
+    results, threshold = {}, None
+    for part, seen, unseen in (("val", seen_val, unseen_val), ("test", seen_test, unseen_test)):
+        results[part] = method_1_inference_and_eval_for_seen_and_unseen(args, original_model, seen, unseen, seen_keys, val_unseen_keys,
+                                                                        test_unseen_keys, device, searched_threshold=threshold)
+        threshold = results[part][0]['best_threshold']              # the val threshold is the test splits' searched_threshold
+        print_acc_for_google_doc(*results[part], K_LIST=K_LIST)
+        print("For seen")
+        check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(results[part][0]), seen_species)
+        print("For unseen")
+        check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(results[part][1]), unseen_species)
+    return results
 
 
 if __name__ == '__main__':

@@ -58,11 +58,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bioscanclip.epoch import fine_tuning_epoch as _epoch  # noqa: E402
 from bioscanclip.epoch.inference_epoch import get_feature_and_label  # noqa: E402
 from bioscanclip.util.util import EncoderWithExtraLayer  # noqa: E402
-from inference_and_eval import LEVELS, make_prediction, top_k_micro_accuracy  # noqa: E402
+from inference_and_eval import LEVELS, make_prediction  # noqa: E402
 from method_one_eval import (MAX_K, MergedOnGpu, _k_list, _key_features, _predictions_of,  # noqa: E402,F401
                              check_for_acc_about_correct_predict_seen_or_unseen, decide_prediction_with_threshold, eval_mode,
-                             get_all_unique_species_from_dataloader, get_final_pred_and_acc, harmonic_mean, print_acc_for_google_doc,
-                             score_splits_on_gpu)
+                             get_all_unique_species_from_dataloader, get_final_pred_and_acc, harmonic_mean, merge_checked,
+                             print_acc_for_google_doc, score_splits_on_gpu, search_threshold)
 
 K_LIST = None
 
@@ -98,14 +98,12 @@ def inference_with_fine_tuned_image_encoder(image_encoder, dataloader, species_l
     return conf.tolist(), pred_labels, gt_labels
 
 
+SPLIT_KEYS = ('pred_labels_from_a', 'pred_confidence_from_a', 'pred_labels_from_b', 'gt_labels')   # :117-131, :190-199
+
+
 def make_final_pred(args, pred_labels_from_a, pred_confidence_from_a, pred_labels_from_b, gt_labels, threshold):
-    n = [len(pred_labels_from_a), len(pred_confidence_from_a), len(pred_labels_from_b)]
-    if n[0] != n[1] != n[2]:   # the reference's chained comparison (:120-121), kept as it is
-        print(f"pred_labels_from_a: {n[0]}")
-        print(f"pred_confidence_from_a: {n[1]}")
-        print(f"pred_labels_from_b: {n[2]}")
-        sys.exit()
-    return decide_prediction_with_threshold(args, pred_labels_from_a, pred_confidence_from_a, pred_labels_from_b, threshold), gt_labels
+    # the length report prints the three arguments' names, which here are also the first three dictionary keys
+    return merge_checked(args, SPLIT_KEYS[:3], (pred_labels_from_a, pred_confidence_from_a, pred_labels_from_b), gt_labels, threshold)
 
 
 def inference_with_original_image_encoder_and_dna_encoder(original_model, seen_dataloader, unseen_dataloader,
@@ -119,31 +117,17 @@ def inference_with_original_image_encoder_and_dna_encoder(original_model, seen_d
 
 def search_threshold_with_harmonic_mean(args, all_split_data, num_intervals=1000):
     """Host path: every merged list is rebuilt for each of the ``num_intervals + 1`` thresholds (:179), as the reference does."""
-    best_threshold, max_score = None, float('-inf')
-    k_list = _k_list(args)
-    for threshold in np.linspace(0, 1, num_intervals + 1):
-        acc_list = []
-        for split in all_split_data:
-            final_pred_labels, gt_labels = make_final_pred(args, split['pred_labels_from_a'], split['pred_confidence_from_a'],
-                                                           split['pred_labels_from_b'], split['gt_labels'], threshold=threshold)
-            acc_list.append(top_k_micro_accuracy(final_pred_labels, gt_labels, k_list=k_list)[1]['species'])
-        score = harmonic_mean(acc_list)
-        if score > max_score:
-            max_score, best_threshold = score, threshold
-    return best_threshold
+    return search_threshold(args, all_split_data, np.linspace(0, 1, num_intervals + 1), SPLIT_KEYS, make_final_pred)
 
 
 def score_predictions_on_host(args, seen, unseen, searched_threshold=None, num_intervals=1000):
     """The host path from predictions on: each of ``seen`` / ``unseen`` is (classifier predictions, confidences as lists, search
     predictions, ground truth)."""
-    data = [{'pred_labels_from_a': s[0], 'pred_confidence_from_a': s[1], 'pred_labels_from_b': s[2], 'gt_labels': s[3]}
-            for s in (seen, unseen)]
     if searched_threshold is None:
         print("Searching best threshold.")
-        best_threshold = search_threshold_with_harmonic_mean(args, data, num_intervals=num_intervals)
-    else:
-        best_threshold = searched_threshold
-    return tuple(get_final_pred_and_acc(args, s[0], s[1], s[2], s[3], best_threshold=best_threshold) for s in (seen, unseen))
+        searched_threshold = search_threshold_with_harmonic_mean(args, [dict(zip(SPLIT_KEYS, s)) for s in (seen, unseen)],
+                                                                 num_intervals=num_intervals)
+    return tuple(get_final_pred_and_acc(args, *s, best_threshold=searched_threshold) for s in (seen, unseen))
 
 
 def score_confidences_on_gpu(args, confidences, idx_to_all_labels, unseen_keys, unseen_key_labels, query_features,
@@ -251,7 +235,7 @@ def main(argv=None):
     from bioscanclip.model.simple_clip import load_clip_model
     from bioscanclip.util.config import load_config
     from bioscanclip.util.synthetic import SyntheticEvalLoader
-    from bioscanclip.util.util import load_checked, remove_extra_pre_fix
+    from bioscanclip.util.util import load_model_and_checkpoint
     here = os.path.dirname(os.path.abspath(__file__))
     args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
     eval_mode(args)
@@ -279,9 +263,7 @@ def main(argv=None):
     species_level_label_to_index_dict, idx_to_all_labels = load_all_seen_species_name_and_create_label_map(train_seen)
     print(f"{len(idx_to_all_labels)} seen species")
 
-    original_model = load_clip_model(args, device)
-    if not (hasattr(mc, "load_ckpt") and mc.load_ckpt is False):
-        load_checked(original_model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
+    original_model, _ = load_model_and_checkpoint(args, device)
     original_model.eval()
     # the reference deep-copies original_model.image_encoder (:459); here the copy is a second model with the first one's parameters
     copy_of_model = load_clip_model(args, device)

@@ -29,10 +29,9 @@ import torch.nn as nn  # noqa: E402
 
 from bioscanclip.epoch.fine_tuning_epoch import evaluate_epoch, fine_tuning_epoch_image_and_dna  # noqa: E402
 from bioscanclip.hip.optim import FusedAdamW  # noqa: E402
-from bioscanclip.model.simple_clip import load_clip_model  # noqa: E402
 from bioscanclip.util.config import load_config  # noqa: E402
 from bioscanclip.util.synthetic import SyntheticEvalLoader  # noqa: E402
-from bioscanclip.util.util import EncoderWithExtraLayer, load_checked, remove_extra_pre_fix  # noqa: E402
+from bioscanclip.util.util import EncoderWithExtraLayer, load_model_and_checkpoint  # noqa: E402
 
 K_VALUES = [1, 3, 5]
 
@@ -62,13 +61,9 @@ def main(argv=None):
     torch.cuda.set_device(device)
 
     print("Initialize model...")
-    if not hasattr(args, "allow_random_init"):
-        args.allow_random_init = True
-    model = load_clip_model(args, device)
-    if hasattr(mc, "load_ckpt") and mc.load_ckpt is False or not hasattr(mc, "ckpt_path"):
+    model, loaded = load_model_and_checkpoint(args, device, ckpt_optional=True)
+    if not loaded:
         print("no checkpoint (model_config.load_ckpt=false or no model_config.ckpt_path): fine-tuning the encoders as initialised")
-    else:
-        load_checked(model, remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu")), f"checkpoint {mc.ckpt_path}")
 
     print("Construct dataloader...")
     batch_size = int(mc.batch_size)

@@ -183,6 +183,46 @@ def test_match_bits_refuse_an_index_outside_the_keys():
     assert flag.item() == 0
 
 
+def _hit_ranks_and_bits(Q, k, L, K, bad=None):
+    """Both entry points on the same idx / key labels / query labels (6 classes, so ranks repeat), each with a caller-owned flag:
+    (hit_rank [Q, L], bits [Q, L], the two flag words)."""
+    from bioscanclip.hip import ops
+    rng = np.random.RandomState(10000 * Q + 100 * k + L)
+    key_labels = rng.randint(0, 6, size=(K, L)).astype(np.int32)          # exactly K rows: nothing to read at row K
+    query_labels = rng.randint(0, 6, size=(Q, L)).astype(np.int32)
+    idx = rng.randint(0, K, size=(Q, k)).astype(np.int64)
+    if bad is not None:
+        idx[bad] = K
+    idx_d, kd, qd = torch.from_numpy(idx).cuda(), torch.from_numpy(key_labels).cuda(), torch.from_numpy(query_labels).cuda()
+    flags = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(2)]
+    hit_rank = ops.retrieval_hit_ranks(idx_d, kd, qd, flag=flags[0])
+    bits = ops.retrieval_match_bits(idx_d, kd, qd, flag=flags[1])
+    return hit_rank.cpu().numpy(), bits.cpu().numpy(), [f.item() for f in flags]
+
+
+@pytest.mark.parametrize("L", [1, 8])
+@pytest.mark.parametrize("k", [1, 5, 16])
+@pytest.mark.parametrize("Q", [1, 17, 213])    # one lane group; one past the 16 queries of a block; the size test_56 uses
+def test_hit_ranks_equal_the_lowest_set_bit_of_match_bits(Q, k, L):
+    """The two kernels share their opening (lane roles, idx bounds rule, label gather, per-level ballot): what one stores as a mask
+    the other stores as its lowest set bit, or k where the mask is 0."""
+    hit_rank, bits, flags = _hit_ranks_and_bits(Q, k, L, K=97)
+    assert flags == [0, 0]
+    assert hit_rank.shape == bits.shape == (Q, L)
+    assert (bits >> k == 0).all()                                          # no bit at or above k, which np_ctz would not see
+    assert (hit_rank == np_ctz(bits, k)).all()
+
+
+def test_hit_ranks_and_match_bits_flag_the_same_bad_index():
+    """An idx entry equal to K sets bit 1 of both callers' flags and is not dereferenced; every other query still agrees."""
+    Q, k = 213, 5
+    hit_rank, bits, flags = _hit_ranks_and_bits(Q, k, 8, K=97, bad=(100, 3))
+    assert flags == [1, 1]
+    keep = np.arange(Q) != 100
+    assert (bits >> k == 0).all()
+    assert (hit_rank[keep] == np_ctz(bits[keep], k)).all()
+
+
 @pytest.mark.parametrize("Q,k,L", [(1, 1, 1), (67, 5, 4), (300, 16, 4)])
 def test_member_masks_equal_numpy(Q, k, L):
     from bioscanclip.hip import ops

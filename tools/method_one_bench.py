@@ -12,12 +12,8 @@ ends in a download); the runs alternate host, GPU after one untimed GPU-path run
 anything is reported.  Appends one JSON line to ``--out`` and prints it.  A tool, not a gate: no test asserts a time.
 """
 import argparse
-import contextlib
-import io
-import json
 import os
 import sys
-import time
 import types
 
 import numpy as np
@@ -29,13 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "bioscan-clip_amd", "scripts"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import method_one_eval as M  # noqa: E402
-from retrieval_eval_bench import tree_hash  # noqa: E402
-
-TABLE_KEYS = ("micro_acc", "macro_acc", "per_class_acc")
-
-
-def label(s):
-    return {"order": f"o{s % 19}", "family": f"f{s % 494}", "genus": f"g{s % 3441}", "species": f"s{s}"}
+from eval_bench_common import append_line, compare_and_time, label  # noqa: E402
 
 
 def make_sets(rng, n_keys, n_queries, n_species, dim):
@@ -68,16 +58,6 @@ def gpu_path(args, sets, species_list):
     return outs, [M.check_for_acc_about_correct_predict_seen_or_unseen(o["merged"], species_list) for o in outs]
 
 
-def timed(fn, *a):
-    sink = io.StringIO()
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    with contextlib.redirect_stdout(sink):
-        outs, shares = fn(*a)
-    torch.cuda.synchronize()
-    return time.perf_counter() - t, outs, shares
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keys", type=int, default=21118)
@@ -94,35 +74,14 @@ def main():
     rng = np.random.default_rng(0)
     sets = make_sets(rng, a.keys, a.queries, a.species, a.dim)
     species_list = sorted({lab["species"] for lab in sets[3]})
-    timed(gpu_path, args, sets, species_list)                     # untimed: code objects, allocator
-    host_s, gpu_s, tables_equal, threshold_equal = [], [], True, True
-    for _ in range(a.repeats):
-        th, out_h, share_h = timed(host_path, args, sets, species_list)
-        tg, out_g, share_g = timed(gpu_path, args, sets, species_list)
-        tables_equal &= all(g[k] == h[k] for h, g in zip(out_h, out_g) for k in TABLE_KEYS) and share_h == share_g
-        threshold_equal &= all(g["best_threshold"] == h["best_threshold"] for h, g in zip(out_h, out_g))
-        host_s.append(th)
-        gpu_s.append(tg)
-    if not (tables_equal and threshold_equal):
-        raise RuntimeError("the GPU path's outputs differ from the host path's: nothing to time")
     big = make_sets(rng, a.keys, a.gpu_queries, a.species, a.dim)
-    big_species = sorted({lab["species"] for lab in big[3]})
-    timed(gpu_path, args, big, big_species)
-    big_s = [timed(gpu_path, args, big, big_species)[0] for _ in range(a.repeats)]
-    line = {"metric": "method_one_eval_seconds", "host_s": min(host_s), "gpu_s": min(gpu_s), "host_over_gpu": min(host_s) / min(gpu_s),
-            "host_runs_s": host_s, "gpu_runs_s": gpu_s, "queries_per_split": a.queries, "splits": 2,
-            "gpu_large_s": min(big_s), "gpu_large_runs_s": big_s, "gpu_large_queries_per_split": a.gpu_queries,
-            "keys_per_index": a.keys, "dim": a.dim, "species": a.species, "k_list": [1, 3, 5], "thresholds": 1000,
-            "tables_equal": bool(tables_equal), "best_threshold_equal": bool(threshold_equal),
-            "best_threshold": float(out_h[0]["best_threshold"]),
-            "top1_species": [out_h[0]["micro_acc"][1]["species"], out_h[1]["micro_acc"][1]["species"]],
+    times = compare_and_time(host_path, gpu_path, (args, sets, species_list), (args, big, sorted({lab["species"] for lab in big[3]})),
+                                a.repeats)
+    line = {"metric": "method_one_eval_seconds", **times, "queries_per_split": a.queries, "gpu_large_queries_per_split": a.gpu_queries,
+            "keys_per_index": a.keys, "dim": a.dim, "species": a.species, "thresholds": 1000,
             "clock": "host perf_counter around the whole evaluation from features on, device synchronised; best of the runs listed; "
-                     "the host path is timed at queries_per_split only (its cost is linear in the queries)",
-            "tree_hash": tree_hash()}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(json.dumps(line) + "\n")
-    print(json.dumps(line))
+                     "the host path is timed at queries_per_split only (its cost is linear in the queries)"}
+    append_line(a.out, line)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ untimed GPU-path run; the outputs are compared for equality before anything is r
 prints it.  A tool, not a gate: no test asserts a time.
 """
 import argparse
-import json
 import os
 import sys
 import types
@@ -29,8 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import method_two_fine_tuning_and_eval as M  # noqa: E402
 from bioscanclip.hip import ops  # noqa: E402
-from method_one_bench import TABLE_KEYS, label, timed  # noqa: E402
-from retrieval_eval_bench import tree_hash  # noqa: E402
+from eval_bench_common import append_line, compare_and_time, label  # noqa: E402
 
 
 def make_sets(rng, n_keys, n_queries, n_classes, n_unseen, dim):
@@ -107,37 +105,16 @@ def main():
     rng = np.random.default_rng(0)
     sets = make_sets(rng, a.keys, a.queries, a.classes, a.unseen_species, a.dim)
     species_list = sorted({lab["species"] for lab in sets[2]})
-    timed(gpu_path, args, sets, species_list)                     # untimed: code objects, allocator
-    host_s, gpu_s, tables_equal, threshold_equal = [], [], True, True
-    for _ in range(a.repeats):
-        th, out_h, share_h = timed(host_path, args, sets, species_list)
-        tg, out_g, share_g = timed(gpu_path, args, sets, species_list)
-        tables_equal &= all(g[k] == h[k] for h, g in zip(out_h, out_g) for k in TABLE_KEYS) and share_h == share_g
-        threshold_equal &= all(g["best_threshold"] == h["best_threshold"] for h, g in zip(out_h, out_g))
-        host_s.append(th)
-        gpu_s.append(tg)
-    if not (tables_equal and threshold_equal):
-        raise RuntimeError("the GPU path's outputs differ from the host path's: nothing to time")
     big = make_sets(rng, a.keys, a.gpu_queries, a.classes, a.unseen_species, a.dim)
-    big_species = sorted({lab["species"] for lab in big[2]})
-    timed(gpu_path, args, big, big_species)
-    big_s = [timed(gpu_path, args, big, big_species)[0] for _ in range(a.repeats)]
-    line = {"metric": "method_two_eval_seconds", "host_s": min(host_s), "gpu_s": min(gpu_s), "host_over_gpu": min(host_s) / min(gpu_s),
-            "host_runs_s": host_s, "gpu_runs_s": gpu_s, "queries_per_split": a.queries, "splits": 2,
-            "gpu_large_s": min(big_s), "gpu_large_runs_s": big_s, "gpu_large_queries_per_split": a.gpu_queries,
+    times = compare_and_time(host_path, gpu_path, (args, sets, species_list), (args, big, sorted({lab["species"] for lab in big[2]})),
+                                a.repeats)
+    line = {"metric": "method_two_eval_seconds", **times, "queries_per_split": a.queries, "gpu_large_queries_per_split": a.gpu_queries,
             "softmax_topk_us": kernel_us(big[3][0][0], a.classes, M.MAX_K), "softmax_topk_rows": a.gpu_queries,
-            "keys_per_index": a.keys, "classes": a.classes, "unseen_species": a.unseen_species, "dim": a.dim, "k_list": [1, 3, 5],
-            "thresholds": 1001, "tables_equal": bool(tables_equal), "best_threshold_equal": bool(threshold_equal),
-            "best_threshold": float(out_h[0]["best_threshold"]),
-            "top1_species": [out_h[0]["micro_acc"][1]["species"], out_h[1]["micro_acc"][1]["species"]],
+            "keys_per_index": a.keys, "classes": a.classes, "unseen_species": a.unseen_species, "dim": a.dim, "thresholds": 1001,
             "clock": "host perf_counter around the whole evaluation from logits and features on, device synchronised; best of the runs "
                      "listed; the host path is timed at queries_per_split only (its cost is linear in the queries); softmax_topk_us: "
-                     "events around 200 back-to-back launches on softmax_topk_rows x classes logits, k = 5",
-            "tree_hash": tree_hash()}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(json.dumps(line) + "\n")
-    print(json.dumps(line))
+                     "events around 200 back-to-back launches on softmax_topk_rows x classes logits, k = 5"}
+    append_line(a.out, line)
 
 
 if __name__ == "__main__":

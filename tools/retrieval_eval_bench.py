@@ -12,14 +12,8 @@ reported.  Appends one JSON line (both times, the ratio, the hash of the product
 a gate: no test asserts a time.
 """
 import argparse
-import contextlib
-import glob
-import hashlib
-import io
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -27,21 +21,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bioscan-clip_amd"))
 sys.path.insert(0, os.path.join(ROOT, "bioscan-clip_amd", "scripts"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import inference_and_eval as E  # noqa: E402
-
-
-def tree_hash():
-    """sha256 over the product sources (kernels, header, package, scripts) and this tool: names and contents, in sorted order."""
-    pats = ["bioscan-clip_amd/csrc/*.hip", "bioscan-clip_amd/csrc/*.h", "bioscan-clip_amd/csrc/Makefile", "include/*.h",
-            "bioscan-clip_amd/bioscanclip/**/*.py", "bioscan-clip_amd/scripts/*.py", "tools/retrieval_eval_bench.py"]
-    files = sorted({f for p in pats for f in glob.glob(os.path.join(ROOT, p), recursive=True)})
-    h = hashlib.sha256()
-    for f in files:
-        h.update(os.path.relpath(f, ROOT).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read() + b"\0")
-    return h.hexdigest()[:16]
+from eval_bench_common import append_line, timed  # noqa: E402
 
 
 def make_split(rng, n, species, centres, noise, for_key_set=False):
@@ -57,16 +40,6 @@ def make_split(rng, n, species, centres, noise, for_key_set=False):
         split["all_key_features"] = np.concatenate((feat["image"], feat["dna"], feat["lang"]), axis=0)
         split["all_key_features_label"] = labels + labels + labels
     return split
-
-
-def timed(fn, splits, k_list):
-    sink = io.StringIO()
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    with contextlib.redirect_stdout(sink):
-        acc, per_class, _ = fn(*splits, k_list=k_list)
-    torch.cuda.synchronize()
-    return time.perf_counter() - t, acc, per_class, sink.getvalue()
 
 
 def main():
@@ -87,11 +60,11 @@ def main():
     splits = (make_split(rng, a.keys, rng.integers(0, n_seen_species, a.keys), centres, 1.0, for_key_set=True),
               make_split(rng, a.queries, rng.integers(0, n_seen_species, a.queries), centres, 1.0),
               make_split(rng, a.queries, rng.integers(n_seen_species, a.species, a.queries), centres, 1.0))
-    timed(E.inference_and_print_result_gpu, splits, k_list)   # untimed: code objects, allocator
+    timed(E.inference_and_print_result_gpu, *splits, k_list=k_list)   # untimed: code objects, allocator
     host_s, gpu_s = [], []
     for _ in range(a.repeats):
-        th, acc_h, pc_h, out_h = timed(E.inference_and_print_result, splits, k_list)
-        tg, acc_g, pc_g, out_g = timed(E.inference_and_print_result_gpu, splits, k_list)
+        th, (acc_h, pc_h, _), out_h = timed(E.inference_and_print_result, *splits, k_list=k_list)
+        tg, (acc_g, pc_g, _), out_g = timed(E.inference_and_print_result_gpu, *splits, k_list=k_list)
         if not (acc_h == acc_g and pc_h == pc_g and out_h == out_g):
             raise RuntimeError("the GPU path's tables differ from the host path's: nothing to time")
         host_s.append(th)
@@ -101,12 +74,8 @@ def main():
             "host_runs_s": host_s, "gpu_runs_s": gpu_s, "cells": cells, "keys": a.keys, "queries_per_split": a.queries, "dim": a.dim,
             "species": a.species, "k_list": k_list, "tables_equal": True,
             "top1_species_seen_image_to_dna": acc_h["encoded_image_feature"]["encoded_dna_feature"]["seen"]["micro_acc"][1]["species"],
-            "clock": "host perf_counter around the whole call, device synchronised; best of the runs listed",
-            "tree_hash": tree_hash()}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "a") as f:
-        f.write(json.dumps(line) + "\n")
-    print(json.dumps(line))
+            "clock": "host perf_counter around the whole call, device synchronised; best of the runs listed"}
+    append_line(a.out, line)
 
 
 if __name__ == "__main__":
