@@ -98,6 +98,7 @@ SIGNATURES = {
     "bsclip_ce_fwd_bwd": (I, [P, I, P, I, I, P, P, P, I, P, I, P, P]),
     "bsclip_class_topk": (I, [P, I, I, I, I, P, P, P]),
     "bsclip_class_softmax_topk": (I, [P, I, I, I, I, P, P, P]),
+    "bsclip_silhouette_samples": (I, [P, I, I, I, P, I, P, P, P]),
     "bsclip_comm_unique_id_bytes": (I, []),
     "bsclip_comm_unique_id": (I, [P]),
     "bsclip_comm_init": (I, [POINTER(c_void_p), P, I, I]),

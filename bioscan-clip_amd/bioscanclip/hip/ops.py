@@ -876,6 +876,40 @@ def class_softmax_topk(logits, C, k):
     return _class_topk("class_softmax_topk", logits, C, k)
 
 
+def check_silhouette_flag(word):
+    """Raise for the error bits ``silhouette_samples`` ORs into its flag word (``word``: its value on the host)."""
+    if word & 2:
+        raise ValueError("silhouette_samples: seg_start is not a non-decreasing sequence from 0 to N")
+    if word & 1:
+        raise ValueError("silhouette_samples: the features hold a NaN or an infinity (or a squared distance overflows float32)")
+
+
+def silhouette_samples(x_sorted, seg_start, D=None, out=None, flag=None):
+    """Silhouette coefficients f32 [N] of the class-sorted rows ``x_sorted[:, :D]`` (f32 GPU [N, >= D], row stride % 4 == 0; D
+    defaults to the width), class c being the rows ``[seg_start[c], seg_start[c+1])`` (``seg_start`` int32 GPU [C + 1]), in the
+    sorted order.  ``out``: an f32 buffer of >= N elements to write them to (the rest is left alone).  ``flag`` as for
+    ``retrieval_hit_ranks``: without it the error word is read back here and bad input raises; with a caller's word nothing
+    synchronises and the caller runs ``check_silhouette_flag`` on it."""
+    ld = _rowmajor(x_sorted, "x_sorted")
+    N = x_sorted.shape[0]
+    D = x_sorted.shape[1] if D is None else int(D)
+    dev = x_sorted.device
+    _req(x_sorted.dtype == F32 and 1 <= D <= x_sorted.shape[1] and ld % 4 == 0 and x_sorted.data_ptr() % 16 == 0,
+         "silhouette_samples: x_sorted f32 [N, >= D], row stride % 4 == 0, 16-byte aligned")
+    _i32(seg_start, dev, "silhouette_samples: seg_start int32 contiguous [C + 1] on x_sorted's GPU", dims=(1,))
+    C = seg_start.numel() - 1
+    _req(N >= 3 and 2 <= C <= N - 1, "silhouette_samples: N >= 3 samples in 2 .. N - 1 classes")
+    if out is None:
+        out = torch.empty(N, dtype=F32, device=dev)
+    _req(out.dtype == F32 and out.dim() == 1 and out.is_contiguous() and out.numel() >= N and out.device == dev,
+         "silhouette_samples: out f32 contiguous [>= N] on x_sorted's GPU")
+    flag, own = _eval_flag(flag, dev)
+    check(_l.load().bsclip_silhouette_samples(_p(x_sorted), ld, N, D, _p(seg_start), C, _p(out), _p(flag), _stream()))
+    if own:
+        check_silhouette_flag(int(flag.item()))
+    return out[:N]
+
+
 def _lora_grad_workspace(H, device):
     return _stream_ws(("lora_grad", H), device, _l.load().bsclip_lora_grad_workspace_floats(H))
 

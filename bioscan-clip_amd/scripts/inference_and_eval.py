@@ -2,6 +2,7 @@
 inner-product top-k search on the GPU (``bsclip_topk_ip`` instead of faiss ``IndexFlatIP``), micro / macro top-k accuracy.
 
 Mirrored entry points (same names, argument meaning and return shapes as the reference):
+    calculate_silhouette_score :407-411   (``inference_and_eval_setting.silhouette=true``; ``bsclip_silhouette_samples``, GPU only)
     make_prediction            :414-445
     top_k_micro_accuracy       :448-464
     top_k_macro_accuracy       :467-511
@@ -44,6 +45,17 @@ def search_topk(query_feature, keys_feature, max_k, device=None):
     """
     sims, idx = ops.topk_ip(to_gpu(query_feature, device), to_gpu(keys_feature, device), int(max_k))
     return sims.cpu().numpy(), idx.cpu().numpy()
+
+
+def calculate_silhouette_score(args, image_features, labels):
+    """Reference :407-411 with sklearn's ``silhouette_samples`` on the GPU (``bioscanclip/hip/silhouette.py``): ``labels[1]`` is the
+    list of label dicts; prints one line per level and returns ``{level: mean}``.  Runs on the GPU whatever ``hip_eval`` says."""
+    from bioscanclip.hip.silhouette import silhouette_by_level
+    label_list = [labels[1][i] for i in range(len(labels[1]))]
+    by_level = silhouette_by_level(image_features, label_list, levels=LEVELS)
+    for level in LEVELS:
+        print(f"The silhouette score for {level} level is : {by_level[level]['mean']}")
+    return {level: by_level[level]["mean"] for level in LEVELS}
 
 
 def make_prediction(query_feature, keys_feature, keys_label, with_similarity=False, with_indices=False, max_k=5):
@@ -181,6 +193,12 @@ def _k_list(args):
     return list(getattr(ies, "k_list", [1, 3, 5])) if ies is not None else [1, 3, 5]
 
 
+def _silhouette(args):
+    """``args.inference_and_eval_setting.silhouette`` (default false): print the silhouette scores of both query splits' image
+    features after the accuracy table."""
+    return bool(getattr(getattr(args, "inference_and_eval_setting", None), "silhouette", False))
+
+
 def inference_and_print_result_gpu(keys_dict, seen_dict, unseen_dict, args=None, small_species_list=None, k_list=None,
                                    with_predictions=False):
     """``inference_and_print_result`` with the evaluation resident on the GPU: same cell loop, skip rules, printed table, ``acc_dict``
@@ -290,7 +308,11 @@ def main(argv=None):
             np.savez(feats_path, keys=np.array(splits[0], dtype=object), seen=np.array(splits[1], dtype=object),
                      unseen=np.array(splits[2], dtype=object), operands=np.array(operands))
     keys_dict, seen_dict, unseen_dict = splits
-    return evaluate_splits(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
+    result = evaluate_splits(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
+    if _silhouette(args):
+        for split in (seen_dict, unseen_dict):
+            calculate_silhouette_score(args, split["encoded_image_feature"], (split["file_name_list"], split["label_list"]))
+    return result
 
 
 if __name__ == "__main__":

@@ -478,6 +478,24 @@ int bsclip_class_topk(const float* logits, int ldc, int B, int C, int k, float* 
  *   np.linspace(0, 1, num_intervals + 1). */
 int bsclip_class_softmax_topk(const float* logits, int ldc, int B, int C, int k, float* conf_out, int64_t* idx_out, void* stream);
 
+/* ---- silhouette coefficients (reference scripts/inference_and_eval.py:407-411) ------------------------------------------
+ * silhouette_samples: sklearn's `silhouette_samples(image_features, gt_list)` with the euclidean metric, as
+ *   calculate_silhouette_score (scripts/inference_and_eval.py:407-411) calls it once per taxonomic level.  The caller sorts the samples by class, so class c is the row
+ *   range [seg_start[c], seg_start[c+1]) of x_sorted (f32 [N, ld], 16-byte aligned, ld >= D, ld % 4 == 0; what lies between D and
+ *   ld is not read as features); seg_start is int32 [C + 1], on the device.  For row i of class A with n_A members:
+ *   a = sum_{j in A} d(i,j) / (n_A - 1), b = min over the classes B != A of sum_{j in B} d(i,j) / n_B, out_sorted[i] =
+ *   (b - a) / max(a, b), f32 [N]; 0 for a singleton class and where the quotient is no number (a = b = 0).  d(i,j) =
+ *   sqrt(sum_k (x_ik - x_jk)^2) from the DIFFERENCES, f32 accumulation (never the Gram form, which cancels for near-duplicate
+ *   rows); d(i,i) = 0 exactly.  The sums over a class are carried in double and added in column order: no float atomics, a
+ *   repeated call gives the same bits.  Rows of out_sorted beyond N are not written.
+ *   *flag is one int32 device word the caller clears (as for bsclip_retrieval_hit_ranks): bit 0 = a distance was no finite
+ *   number (a NaN or inf feature, or an overflow of the squared distance in f32); bit 1 = seg_start is not a non-decreasing
+ *   sequence from 0 to N -- checked on the device before any use, and then nothing is computed and out_sorted is left as it was.
+ *   Refused on the host (-1, bsclip_last_error): null pointers, N < 3, C < 2 or C > N - 1, D < 1, ld < D or ld % 4 != 0, a
+ *   misaligned pointer. */
+int bsclip_silhouette_samples(const float* x_sorted, int ld, int N, int D, const int32_t* seg_start, int C, float* out_sorted,
+                              int32_t* flag, void* stream);
+
 /* ---- RCCL collectives of the global-batch step ---------------------------------------------------
  * One process per GPU.  bsclip_comm_unique_id on rank 0 -> the caller ships the bsclip_comm_unique_id_bytes() bytes to the
  * other ranks (any channel) -> bsclip_comm_init on every rank (ncclCommInitRank).  The collectives run on `comm_stream`;
