@@ -243,6 +243,23 @@ class _Layer:
         self.qkv32 = self.wqkv3 = self.w3 = self.w3t = self.wqkvT3 = None
 
 
+# What the sequences of one ViT block work on below the attention (ViTEngine._workspace makes one per block).  Blocks 0 .. L-2: all
+# B * 197 rows.  The last block: the B token-0 rows, as views of row stride S * w (tok0) of the same stream buffers -- the head reads
+# token 0 only (timm global_pool='token') and within a block a token depends on the others through K and V alone, so attention runs
+# for query 0 and the out-projection, LayerNorm 2 and the MLP, forward and backward, do 1/197 of the work for the same values.
+#   M, q_rows        row count, and the attention kernels' query-rows flag (1 = query 0 only)
+#   x                the residual stream before the block, after attention, after the MLP
+#   ctx, h2, act     operands of the out-projection, fc1 and fc2 (exact mode: ctx in f32; full fine-tuning: h2 / act kept per block)
+#   z, st2           gelu' codes (exact mode: the f32 fc1 pre-activation), LayerNorm-2 statistics
+#   mlp8             the MLP runs on fp8 operands
+#   split            exact mode: the attention and LayerNorm kernels write the next GEMM's split operand themselves (else a
+#                    split3_rows pass over the f32 rows does)
+#   g, dxb           the residual-gradient stream and the dX GEMMs' 16-bit operand
+#   dz, dh, dctx     outputs of the fc2, fc1 and out-projection dX GEMMs; zero: the whole dctx buffer where dctx covers only some of
+#                    the rows the attention backward reads, so that it must be cleared first (else None)
+_Rows = namedtuple("_Rows", "M q_rows x ctx h2 act z st2 mlp8 split g dxb dz dh dctx zero")
+
+
 class EncoderEngineBase:
     """Shared pieces of the ViT and BERT engines: the mode, LoRA bookkeeping and the flat trainable buffer."""
 
@@ -250,6 +267,11 @@ class EncoderEngineBase:
         self.mode, self.device = mode, device
         self.full_ft = mode.full_ft
         self.fp8 = mode.fp8 and not mode.full_ft     # full fine-tuning has no fp8 path
+        # what the request comes to in this engine: full fine-tuning and fp8 trunks keep the f32 residual stream, full fine-tuning the
+        # f32 gradient stream too; the exact mode is the LoRA-regime engines' alone
+        self.resid_bf16 = mode.resid_stream_bf16 and not mode.full_ft and not self.fp8
+        self.grad_bf16 = mode.grad_stream_bf16 and not mode.full_ft
+        self._exact = mode.exact and not self.fp8 and not mode.full_ft
         # fp16 operands: every frozen weight, the head weight's per-forward cast and the workspace's 16-bit buffers are IEEE fp16, the
         # kernels get BSCLIP_OPERANDS_FP16.  The ViT trains on them; the BERT engines are inference-only.
         self.fp16, self.h16 = mode.fp16, F16 if mode.fp16 else BF16
@@ -392,7 +414,7 @@ class EncoderEngineBase:
 
     # ------------------------------------------------------------------------------ exact mode (BSCLIP_PARITY=2)
     def exact(self):
-        return self.mode.exact and not self.fp8 and not self.full_ft
+        return self._exact
 
     def _ex_weight(self, w_f32, lora=None):
         """[hi | hi | lo] rows of a frozen f32 weight (LoRA folded in f32 when given: refreshed by the caller every step)."""
@@ -402,10 +424,13 @@ class EncoderEngineBase:
             ops.split3_weight(w, dst)
         return w, dst
 
-    def _ex_gemm(self, a_f32, w3, out, epi, scratch, M=None, **kw):
-        """out = epilogue(a_f32 @ W^T) with both operands split: a_f32 f32 [M, K] (row stride free) -> [hi | lo | hi] in ``scratch``."""
+    def _ex_gemm(self, a_f32, w3, out, epi, scratch, M=None, presplit=False, **kw):
+        """out = epilogue(a_f32 @ W^T) with both operands split: a_f32 f32 [M, K] (row stride free) -> [hi | lo | hi] in ``scratch``.
+        ``presplit``: the kernel that produced a_f32 wrote that split into ``scratch`` itself (see _ex_gemm3): no split3_rows pass."""
         M = a_f32.shape[0] if M is None else M
         K = w3.shape[1] // 3
+        if presplit:
+            return self._ex_gemm3(scratch, w3, out, epi, M, **kw)
         a3 = ops.split3_rows(a_f32, scratch, M=M, K=K)
         return ops.gemm(a3, w3, out, epi, M=M, K=3 * K, **kw)
 
@@ -513,15 +538,16 @@ class ViTEngine(EncoderEngineBase):
         h16 = self.h16     # the 16-bit operand buffers (and the 16-bit residual stream) are fp16 in an fp16 engine
         z = lambda *s, dt=h16: torch.empty(*s, dtype=dt, device=dev)
         ws = {"B": B, "M": M, "gen": next(_WS_GEN)}
-        mode = self.mode
-        ws["cols"] = z(B * 196, 3 * H if (mode.patch_split and not self.full_ft) else H)
-        rb = ws["resid_bf16"] = mode.resid_stream_bf16 and not self.full_ft and not self.fp8
-        if self.exact():
-            assert not rb and not mode.grad_stream_bf16, "the exact forward runs on the f32 streams"
+        rows = lambda l: B if l == L - 1 else M     # the last block's MLP runs on the token-0 rows alone (_Rows)
+        ws["cols"] = z(B * 196, 3 * H if (self.mode.patch_split and not self.full_ft) else H)
+        rb, ex = self.resid_bf16, self.exact()
+        ws["resid_bf16"], ws["grad_bf16"] = rb, self.grad_bf16
+        if ex:
+            assert not rb and not self.grad_bf16, "the exact forward runs on the f32 streams"
             # per layer, all f32: LN1 output, q | k | v, attention output, fc1 pre-activation -- what the exact backward reads
             ws["y32s"], ws["ctx32s"] = [z(M, H, dt=F32) for _ in range(L)], [z(M, H, dt=F32) for _ in range(L)]
             ws["qkv32s"] = [z(M, 3 * H, dt=F32) for _ in range(L)]
-            ws["z32s"] = [z(M if l < L - 1 else B, FF, dt=F32) for l in range(L)]
+            ws["z32s"] = [z(rows(l), FF, dt=F32) for l in range(L)]
             ws["y32"], ws["cls32"] = z(M, H, dt=F32), z(B, H, dt=F32)
             ws["a3"] = z(M, 3 * FF)                                   # [hi | lo | hi] rows of the current GEMM's A operand
             ws["whead3"] = z(self.out_dim, 3 * H)
@@ -533,26 +559,24 @@ class ViTEngine(EncoderEngineBase):
         ws["x"] = [z(M, H, dt=h16 if rb else F32) for _ in range(2 * L + 1)]   # residual stream after every sub-layer
         ws["h1"] = [z(M, H + KPAD) for _ in range(L)]                 # LN1 output + LoRA t (QKV operand)
         ws["st1"] = [z(M, 2, dt=F32) for _ in range(L)]
-        ws["st2"] = [z(M, 2, dt=F32) for _ in range(L)]
+        ws["st2"] = [z(rows(l), 2, dt=F32) for l in range(L)]
         ws["qkv"] = [z(M, 3 * H) for _ in range(L)]
         ws["ctx"] = [z(M, H) for _ in range(L)]
         ws["lse"] = [z(B, self.heads, S, dt=F32) for _ in range(L)]
-        ws["z"] = [z(M, FF, dt=torch.uint8) for _ in range(L)]        # gelu'(fc1 pre-activation), 8-bit codes
+        ws["z"] = [z(rows(l), FF, dt=torch.uint8) for l in range(L)]   # gelu'(fc1 pre-activation), 8-bit codes
         ws["h2"] = z(M, H)
         ws["act"] = z(M, FF)
         if self.full_ft:  # inputs of fc1 / fc2 per block: operands of their weight-gradient GEMMs
-            ws["h2s"] = [z(M, H) for _ in range(L)]
-            ws["acts"] = [z(M, FF) for _ in range(L)]
+            ws["h2s"] = [z(rows(l), H) for l in range(L)]
+            ws["acts"] = [z(rows(l), FF) for l in range(L)]
         if self.fp8:  # fp8 GEMM operands: LN1 output per block (lora_grad reads it again) + its bf16 t block, LN2 / GELU shared
             ws["h1_8"] = [z(M, H, dt=ops.FP8) for _ in range(L)]
             ws["t"] = [z(M, KPAD) for _ in range(L)]
             ws["h2_8"], ws["act8"] = z(M, H, dt=ops.FP8), z(M, FF, dt=ops.FP8)
         ws["clsn"] = z(B, H)
         ws["st_f"] = z(B, 2, dt=F32)
-        ws["h2_c"], ws["act_c"], ws["z_c"], ws["st_c"] = z(B, H), z(B, FF), z(B, FF, dt=torch.uint8), z(B, 2, dt=F32)   # last-block token-0 path
         # backward temporaries (16-bit ones in the operand format: an fp16 engine's gradient stream and dX operands are fp16, in
         # units of the tower's static gradient scale 2^FP16_GRAD_SCALE_LOG2)
-        ws["grad_bf16"] = mode.grad_stream_bf16 and not self.full_ft
         assert ws["grad_bf16"] or not self.fp16, "the fp16 backward runs on the 16-bit gradient stream"
         ws["dx"] = None if ws["grad_bf16"] else torch.zeros(M, H, dtype=F32, device=dev)
         ws["dxb"] = torch.zeros(M, H, dtype=h16, device=dev)
@@ -569,7 +593,19 @@ class ViTEngine(EncoderEngineBase):
         if self.fp16:   # the head's dW in 2^s units, before bsclip_add_scaled_f32 takes the scale off into .grad
             ws["gw_head"] = torch.empty(self.out_dim, H, dtype=F32, device=dev)
         ws["dclsn"] = z(B, H)
-        ws["dz_c"], ws["dh_c"] = z(B, FF), z(B, H)
+        g, ctx, dctx = ws["dxb" if ws["grad_bf16"] else "dx"], ws["ctx32s" if ex else "ctx"], ws["dctx32" if ex else "dctx"]
+        ws["rows"] = []
+        for l in range(L):
+            last = l == L - 1
+            v = (lambda t: tok0(t, B)) if last else (lambda t: t)
+            if self.full_ft:
+                h2, act = ws["h2s"][l], ws["acts"][l]
+            else:
+                h2, act = (z(B, H), z(B, FF)) if last else (ws["h2"], ws["act"])
+            ws["rows"].append(_Rows(
+                M=rows(l), q_rows=int(last), x=[v(t) for t in ws["x"][2 * l:2 * l + 3]], ctx=v(ctx[l]), h2=h2, act=act,
+                z=ws["z32s" if ex else "z"][l], st2=ws["st2"][l], mlp8=self.fp8 and not last, split=not last, g=v(g), dxb=v(ws["dxb"]),
+                dz=z(B, FF) if last else ws["dz"], dh=z(B, H) if last else ws["dh"], dctx=v(dctx), zero=dctx if last else None))
         return self._keep_workspace(ws)
 
     def backward_probes(self):
@@ -583,54 +619,46 @@ class ViTEngine(EncoderEngineBase):
     def anomaly_probes(self):
         """(name, tensor) of the forward's saved activations in execution order (BSCLIP_DETECT_ANOMALY).  The last block's
         sub-layers exist on the token-0 rows only."""
-        ws, L, B = self.ws, len(self.layers), self.ws["B"]
+        ws = self.ws
         qkv, ctx = ("qkv32s", "ctx32s") if self.exact() else ("qkv", "ctx")
         yield "the patch embedding + position table", ws["x"][0]
-        for l in range(L):
+        for l, r in enumerate(ws["rows"]):
             yield f"blocks.{l}.attn.qkv output", ws[qkv][l]
-            if l < L - 1:
+            if not r.q_rows:
                 yield f"blocks.{l}.attn output", ws[ctx][l]
-            x1, x2 = ws["x"][2 * l + 1], ws["x"][2 * l + 2]
-            if l == L - 1:
-                x1, x2 = tok0(x1, B), tok0(x2, B)
-            yield f"blocks.{l} residual stream after attention", x1
-            yield f"blocks.{l} residual stream after the MLP", x2
+            yield f"blocks.{l} residual stream after attention", r.x[1]
+            yield f"blocks.{l} residual stream after the MLP", r.x[2]
 
     # -------------------------------------------------------------------------------------------- forward
     def _forward_exact(self, image, ws):
         """BSCLIP_PARITY=2: the same block sequence with every Linear and every attention product on split-bf16 operands (f32 in / out), exact-erf GELU; what
         ``_backward_exact`` reads -- per layer the f32 LN1 output, q | k | v, attention output and fc1 pre-activation, the
         LayerNorm statistics, lse, the f32 residual stream -- stays resident."""
-        B, H, S, M, L, FF = image.shape[0], self.H, self.S, ws["M"], len(self.layers), self.FF
+        B, H, S, M = image.shape[0], self.H, self.S, ws["M"]
         scale = 64 ** -0.5
         x, a3 = ws["x"], ws["a3"]
         self._ex_forward_weights()
         ops.im2col_patch16(image, ws["cols"])
         ops.gemm(ws["cols"], self.w_patch3, x[0], EPI_PATCH_F32, bias=self.b_patch, resid=self.pos)
         ops.vit_cls_rows(x[0], self.cls, self.pos, B, S, H)
-        for l, lay in enumerate(self.layers):
+        for l, (lay, r) in enumerate(zip(self.layers, ws["rows"])):
             has = self._lora_index[l] is not None
-            y32, qkv32, ctx32, z32 = ws["y32s"][l], ws["qkv32s"][l], ws["ctx32s"][l], ws["z32s"][l]
+            y32, qkv32 = ws["y32s"][l], ws["qkv32s"][l]
             # the LayerNorm writes the QKV GEMM's split operand itself (and the f32 copy the LoRA gradients read in the backward)
             ops.layernorm_fwd(x[2 * l], lay.ln1[0], lay.ln1[1], 1e-6, y_f32=y32, y_split3=a3, stats=ws["st1"][l])
             ops.split3_weight(lay.qkv32, lay.wqkv3, lora_a=self.lora_a(l) if has else None, lora_b=self.lora_b(l) if has else None)
             self._ex_gemm3(a3, lay.wqkv3, qkv32, EPI_F32, M, bias=lay.b_qkv)
-            ops.attn_fwd_f32(qkv32, B, S, self.heads, scale, ctx32, ws["lse"][l], ctx_split3=a3 if l < L - 1 else None)
-            if l == L - 1:   # token-0 rows only, as the default path (and as its backward expects)
-                self._ex_gemm(tok0(ctx32, B), lay.w3[0], tok0(x[2 * l + 1], B), EPI_RESID_F32, a3, bias=lay.b_proj,
-                              resid=tok0(x[2 * l], B))
-                ops.layernorm_fwd(tok0(x[2 * l + 1], B), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"], y_f32=ws["cls32"],
-                                  stats=ws["st_c"])
-                self._ex_gemm(ws["cls32"], lay.w3[1], z32, EPI_F32, a3, bias=lay.b_fc1)
-                g3 = ops.gelu_split3(z32, a3, M=B)
-                ops.gemm(g3, lay.w3[2], tok0(x[2 * l + 2], B), EPI_RESID_F32, bias=lay.b_fc2, resid=tok0(x[2 * l + 1], B), M=B)
-                continue
-            self._ex_gemm3(a3, lay.w3[0], x[2 * l + 1], EPI_RESID_F32, M, bias=lay.b_proj, resid=x[2 * l])   # a3: written by the attention kernel
-            ops.layernorm_fwd(x[2 * l + 1], lay.ln2[0], lay.ln2[1], 1e-6, y_split3=a3, stats=ws["st2"][l])
-            self._ex_gemm3(a3, lay.w3[1], z32, EPI_F32, M, bias=lay.b_fc1)
-            g3 = ops.gelu_split3(z32, a3)
-            ops.gemm(g3, lay.w3[2], x[2 * l + 2], EPI_RESID_F32, bias=lay.b_fc2, resid=x[2 * l + 1])
-        ops.layernorm_fwd(tok0(x[-1], B), self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], y_f32=ws["cls32"], stats=ws["st_f"])
+            ops.attn_fwd_f32(qkv32, B, S, self.heads, scale, ws["ctx32s"][l], ws["lse"][l], ctx_split3=a3 if r.split else None)
+            self._ex_gemm(r.ctx, lay.w3[0], r.x[1], EPI_RESID_F32, a3, M=r.M, presplit=r.split, bias=lay.b_proj, resid=r.x[0])
+            if r.split:     # a3: written by the LayerNorm
+                ops.layernorm_fwd(r.x[1], lay.ln2[0], lay.ln2[1], 1e-6, y_split3=a3, stats=r.st2)
+                self._ex_gemm3(a3, lay.w3[1], r.z, EPI_F32, r.M, bias=lay.b_fc1)
+            else:
+                ops.layernorm_fwd(r.x[1], lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=r.h2, y_f32=ws["cls32"], stats=r.st2)
+                self._ex_gemm(ws["cls32"], lay.w3[1], r.z, EPI_F32, a3, bias=lay.b_fc1)
+            g3 = ops.gelu_split3(r.z, a3, M=r.M)
+            ops.gemm(g3, lay.w3[2], r.x[2], EPI_RESID_F32, bias=lay.b_fc2, resid=r.x[1], M=r.M)
+        ops.layernorm_fwd(ws["rows"][-1].x[2], self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], y_f32=ws["cls32"], stats=ws["st_f"])
         ops.split3_weight(self.extra(0), ws["whead3"])
         out = torch.empty(B, self.out_dim, dtype=F32, device=self.device)
         self._ex_gemm(ws["cls32"], ws["whead3"], out, EPI_F32, a3, bias=self.extra(1))
@@ -651,8 +679,7 @@ class ViTEngine(EncoderEngineBase):
         ops.gemm(ws["cols"], self.w_patch3 if ws["cols"].shape[1] == 3 * H else self.w_patch, x[0], EPI_P, bias=self.b_patch,
                  resid=self.pos)
         ops.vit_cls_rows(x[0], self.cls, self.pos, B, S, H)
-        L = len(self.layers)
-        for l, lay in enumerate(self.layers):
+        for l, (lay, r) in enumerate(zip(self.layers, ws["rows"])):
             if self.fp8:
                 ops.layernorm_fwd_fp8(x[2 * l], lay.ln1[0], lay.ln1[1], 1e-6, ws["h1_8"][l], t_aug=ws["t"][l],
                                       lora_a=self.lora_a(l), stats=ws["st1"][l])
@@ -662,31 +689,17 @@ class ViTEngine(EncoderEngineBase):
                 ops.layernorm_fwd(x[2 * l], lay.ln1[0], lay.ln1[1], 1e-6, y_bf16=ws["h1"][l], lora_a=self.lora_a(l),
                                   stats=ws["st1"][l])
                 ops.gemm(ws["h1"][l], lay.waug, ws["qkv"][l], EPI_BF16, bias=lay.b_qkv)
-            if l == L - 1:
-                # The head reads token 0 of the last block only (timm global_pool='token'), and within a block a token's
-                # output depends on the other tokens through K and V alone: attention for query 0, then proj / LN2 / MLP on
-                # the B token-0 rows (row stride S*H) instead of all B*197.  Same values, 1/197 of the GEMM work.
-                ops.attn_fwd(ws["qkv"][l], B, S, self.heads, scale, ws["ctx"][l], ws["lse"][l], q_rows=1)
-                ops.gemm(tok0(ws["ctx"][l], B), lay.w_proj, tok0(x[2 * l + 1], B), EPI_R, bias=lay.b_proj,
-                         resid=tok0(x[2 * l], B))
-                ops.layernorm_fwd(tok0(x[2 * l + 1], B), lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=ws["h2_c"],
-                                  stats=ws["st_c"])
-                ops.gemm(ws["h2_c"], lay.w_fc1, ws["act_c"], EPI_GELU_BF16, bias=lay.b_fc1, aux=ws["z_c"])
-                ops.gemm(ws["act_c"], lay.w_fc2, tok0(x[2 * l + 2], B), EPI_R, bias=lay.b_fc2,
-                         resid=tok0(x[2 * l + 1], B))
+            ops.attn_fwd(ws["qkv"][l], B, S, self.heads, scale, ws["ctx"][l], ws["lse"][l], q_rows=r.q_rows)
+            ops.gemm(r.ctx, lay.w_proj, r.x[1], EPI_R, bias=lay.b_proj, resid=r.x[0])
+            if r.mlp8:
+                ops.layernorm_fwd_fp8(r.x[1], lay.ln2[0], lay.ln2[1], 1e-6, ws["h2_8"], stats=r.st2)
+                ops.gemm_fp8(ws["h2_8"], lay.w_fc1_8, ws["act8"], lay.s_fc1, lay.b_fc1, EPI_GELU_FP8, aux=r.z)
+                ops.gemm_fp8(ws["act8"], lay.w_fc2_8, r.x[2], lay.s_fc2, lay.b_fc2, EPI_RESID_F32, resid=r.x[1])
                 continue
-            ops.attn_fwd(ws["qkv"][l], B, S, self.heads, scale, ws["ctx"][l], ws["lse"][l])
-            ops.gemm(ws["ctx"][l], lay.w_proj, x[2 * l + 1], EPI_R, bias=lay.b_proj, resid=x[2 * l])
-            if self.fp8:
-                ops.layernorm_fwd_fp8(x[2 * l + 1], lay.ln2[0], lay.ln2[1], 1e-6, ws["h2_8"], stats=ws["st2"][l])
-                ops.gemm_fp8(ws["h2_8"], lay.w_fc1_8, ws["act8"], lay.s_fc1, lay.b_fc1, EPI_GELU_FP8, aux=ws["z"][l])
-                ops.gemm_fp8(ws["act8"], lay.w_fc2_8, x[2 * l + 2], lay.s_fc2, lay.b_fc2, EPI_RESID_F32, resid=x[2 * l + 1])
-                continue
-            h2, act = (ws["h2s"][l], ws["acts"][l]) if self.full_ft else (ws["h2"], ws["act"])   # dW needs them per layer
-            ops.layernorm_fwd(x[2 * l + 1], lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=h2, stats=ws["st2"][l])
-            ops.gemm(h2, lay.w_fc1, act, EPI_GELU_BF16, bias=lay.b_fc1, aux=ws["z"][l])
-            ops.gemm(act, lay.w_fc2, x[2 * l + 2], EPI_R, bias=lay.b_fc2, resid=x[2 * l + 1])
-        ops.layernorm_fwd(tok0(x[-1], B), self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], stats=ws["st_f"])
+            ops.layernorm_fwd(r.x[1], lay.ln2[0], lay.ln2[1], 1e-6, y_bf16=r.h2, stats=r.st2)
+            ops.gemm(r.h2, lay.w_fc1, r.act, EPI_GELU_BF16, bias=lay.b_fc1, aux=r.z)
+            ops.gemm(r.act, lay.w_fc2, r.x[2], EPI_R, bias=lay.b_fc2, resid=r.x[1])
+        ops.layernorm_fwd(ws["rows"][-1].x[2], self.ln_f[0], self.ln_f[1], 1e-6, y_bf16=ws["clsn"], stats=ws["st_f"])
         out = torch.empty(B, self.out_dim, dtype=F32, device=self.device)
         ops.gemm(ws["clsn"], self.w_head_bf, out, EPI_F32, bias=self.extra(1))
         return out
@@ -698,7 +711,9 @@ class ViTEngine(EncoderEngineBase):
 
     def backward(self, dout):
         """The LoRA, fp8, fp16 and full fine-tuning backward.  Full fine-tuning (hip/engine_ft.py) differs by what the hooks
-        ``_dw`` / ``_ln_dw`` / ``_below_layer0`` add -- no-ops here -- and by the chain continuing through block 0."""
+        ``_dw`` / ``_ln_dw`` / ``_below_layer0`` add -- no-ops here -- and by the chain continuing through block 0.  One block body
+        for every block: ``ws["rows"][l]`` (_Rows) says which rows of which buffers the MLP, LayerNorm-2 and out-projection backward
+        of block l work on -- the last block's are the token-0 rows, as only those carry a gradient from the head."""
         if self.exact():
             return self._backward_exact(dout)
         ws = self.ws
@@ -720,51 +735,31 @@ class ViTEngine(EncoderEngineBase):
         if not g16:
             dx.zero_()
         dxb.zero_()
-        dx_c, dxb_c = tok0(R, B), tok0(dxb, B)
-        self._ln_dw(tok0(x[-1], B), ws["st_f"], 0, "norm.w", "norm.b", g_gemm=ws["dclsn"])
-        ops.layernorm_bwd(tok0(x[-1], B), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dclsn"], dx_f32=None if g16 else dx_c, dx_bf16=dxb_c)
-        L = len(self.layers)
-        for l in range(L - 1, -1, -1):
-            lay = self.layers[l]
-            if l == L - 1:
-                # Only token 0 of the last block feeds the head, so the residual gradient entering this block is zero
-                # on the other 196 rows of every image: its MLP backward, LN2 backward and proj backward run on the B
-                # token-0 rows only (row stride S*H), 1/197 of the work.
-                probe("grad_stream", dxb_c)
-                self._dw(dxb_c, ws["act_c"], B, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
-                ops.gemm(dxb_c, lay.w_fc2_t, ws["dz_c"], EPI_DGELU_BF16, aux=ws["z_c"])
-                probe("dfc1_out", ws["dz_c"])
-                self._dw(ws["dz_c"], ws["h2_c"], B, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
-                ops.gemm(ws["dz_c"], lay.w_fc1_t, ws["dh_c"], EPI_BF16)
-                probe("dln2_out", ws["dh_c"])
-                self._ln_dw(tok0(x[2 * l + 1], B), ws["st_c"], 0, f"{l}.n2.w", f"{l}.n2.b", g_gemm=ws["dh_c"])
-                ops.layernorm_bwd(tok0(x[2 * l + 1], B), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c,
-                                  g_gemm=ws["dh_c"], dx_f32=None if g16 else dx_c, dx_bf16=dxb_c)
-                probe("grad_stream", dxb_c)
-                self._dw(dxb_c, tok0(ws["ctx"][l], B), B, H, H, f"{l}.proj.w", f"{l}.proj.b")
-                ws["dctx"].zero_()
-                ops.gemm(dxb_c, lay.w_proj_t, tok0(ws["dctx"], B), EPI_BF16)
-            else:
-                h2, act = (ws["h2s"][l], ws["acts"][l]) if ft else (ws["h2"], ws["act"])   # the dW hooks' operands, as the forward chose them
-                probe("grad_stream", dxb)
-                self._dw(dxb, act, M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
-                ops.gemm(dxb, lay.w_fc2_t, ws["dz"], EPI_DGELU_BF16, aux=ws["z"][l])
-                probe("dfc1_out", ws["dz"])
-                self._dw(ws["dz"], h2, M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
-                ops.gemm(ws["dz"], lay.w_fc1_t, ws["dh"], EPI_BF16)
-                probe("dln2_out", ws["dh"])
-                self._ln_dw(x[2 * l + 1], ws["st2"][l], 0, f"{l}.n2.w", f"{l}.n2.b", g_gemm=ws["dh"])
-                ops.layernorm_bwd(x[2 * l + 1], ws["st2"][l], lay.ln2[0], 0, g_resid=R, g_gemm=ws["dh"],
-                                  dx_f32=None if g16 else dx, dx_bf16=dxb)
-                probe("grad_stream", dxb)
-                self._dw(dxb, ws["ctx"][l], M, H, H, f"{l}.proj.w", f"{l}.proj.b")
-                ops.gemm(dxb, lay.w_proj_t, ws["dctx"], EPI_BF16)
+        r = ws["rows"][-1]
+        self._ln_dw(r.x[2], ws["st_f"], 0, "norm.w", "norm.b", g_gemm=ws["dclsn"])
+        ops.layernorm_bwd(r.x[2], ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dclsn"], dx_f32=None if g16 else r.g, dx_bf16=r.dxb)
+        for l in range(len(self.layers) - 1, -1, -1):
+            lay, r = self.layers[l], ws["rows"][l]
+            probe("grad_stream", r.dxb)
+            self._dw(r.dxb, r.act, r.M, H, FF, f"{l}.fc2.w", f"{l}.fc2.b")
+            ops.gemm(r.dxb, lay.w_fc2_t, r.dz, EPI_DGELU_BF16, aux=r.z)
+            probe("dfc1_out", r.dz)
+            self._dw(r.dz, r.h2, r.M, FF, H, f"{l}.fc1.w", f"{l}.fc1.b")
+            ops.gemm(r.dz, lay.w_fc1_t, r.dh, EPI_BF16)
+            probe("dln2_out", r.dh)
+            self._ln_dw(r.x[1], r.st2, 0, f"{l}.n2.w", f"{l}.n2.b", g_gemm=r.dh)
+            ops.layernorm_bwd(r.x[1], r.st2, lay.ln2[0], 0, g_resid=r.g, g_gemm=r.dh, dx_f32=None if g16 else r.g, dx_bf16=r.dxb)
+            probe("grad_stream", r.dxb)
+            self._dw(r.dxb, r.ctx, r.M, H, H, f"{l}.proj.w", f"{l}.proj.b")
+            if r.zero is not None:
+                r.zero.zero_()
+            ops.gemm(r.dxb, lay.w_proj_t, r.dctx, EPI_BF16)
             probe("dattn_out", ws["dctx"])
             lb = self.lora_b(l)
             # dt / dB partial sums out of the attention backward (the fp16 backward has this form only)
             part = lb is not None and (self.mode.attn_lora or f16) and not self.fp8
             ops.attn_bwd(ws["qkv"][l], ws["dctx"], ws["lse"][l], B, S, self.heads, scale, ws["dqkv"],
-                         q_rows=1 if l == L - 1 else 0, lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
+                         q_rows=r.q_rows, lora=(ws["h1"][l][:, H:], lb, ws["dtp"], ws["dbp"]) if part else None)
             probe("dqkv", ws["dqkv"])
             self._dw(ws["dqkv"], ws["h1"][l], M, 3 * H, H, f"{l}.qkv.w", f"{l}.qkv.b")
             self._lora_grads(l, ws, ws["h1"][l], ws["h1_8"][l] if self.fp8 else None, part, gs)
@@ -792,27 +787,19 @@ class ViTEngine(EncoderEngineBase):
         ops.colsum(dout, B, self.out_dim, self.extra(1, grad=True))
         self._ex_gemm(dout, ops.split3_transpose(self.extra(0), ws["wheadT3"], 1), ws["dcls32"], EPI_F32, a3)
         dx.zero_()
-        dx_c = tok0(dx, B)
-        ops.layernorm_bwd(tok0(x[-1], B), ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dcls32"], dx_f32=dx_c)
-        dx3 = False     # a3 holds the split of dx (written by the LayerNorm backward that produced dx: no split3_rows pass)
+        r = ws["rows"][-1]
+        ops.layernorm_bwd(r.x[2], ws["st_f"], self.ln_f[0], 0, g_gemm=ws["dcls32"], dx_f32=r.g)
         for l in range(L - 1, -1, -1):
-            lay = self.layers[l]
-            if l == L - 1:    # token-0 rows only (see backward)
-                self._ex_gemm(dx_c, lay.w3t[2], ws["g32"], EPI_F32, a3, M=B)
-                g3 = ops.dgelu_split3(ws["g32"], ws["z32s"][l], dst=a3, M=B)
-                ops.gemm(g3, lay.w3t[1], ws["dh32"], EPI_F32, M=B)
-                ops.layernorm_bwd(tok0(x[2 * l + 1], B), ws["st_c"], lay.ln2[0], 0, g_resid=dx_c, g_gemm=ws["dh32"], dx_f32=dx_c, M=B)
-                ws["dctx32"].zero_()
-                self._ex_gemm(dx_c, lay.w3t[0], tok0(ws["dctx32"], B), EPI_F32, a3, M=B)
-            else:
-                if dx3:
-                    self._ex_gemm3(a3, lay.w3t[2], ws["g32"], EPI_F32, M)
-                else:
-                    self._ex_gemm(dx, lay.w3t[2], ws["g32"], EPI_F32, a3)
-                g3 = ops.dgelu_split3(ws["g32"], ws["z32s"][l], dst=a3)
-                ops.gemm(g3, lay.w3t[1], ws["dh32"], EPI_F32)
-                ops.layernorm_bwd(x[2 * l + 1], ws["st2"][l], lay.ln2[0], 0, g_resid=dx, g_gemm=ws["dh32"], dx_f32=dx, dx_split3=a3)
-                self._ex_gemm3(a3, lay.w3t[0], ws["dctx32"], EPI_F32, M)
+            lay, r = self.layers[l], ws["rows"][l]
+            # r.split: a3 holds the split of r.g, left there by the LayerNorm backward that produced r.g
+            self._ex_gemm(r.g, lay.w3t[2], ws["g32"], EPI_F32, a3, M=r.M, presplit=r.split)
+            g3 = ops.dgelu_split3(ws["g32"], r.z, dst=a3, M=r.M)
+            ops.gemm(g3, lay.w3t[1], ws["dh32"], EPI_F32, M=r.M)
+            ops.layernorm_bwd(r.x[1], r.st2, lay.ln2[0], 0, g_resid=r.g, g_gemm=ws["dh32"], dx_f32=r.g,
+                              dx_split3=a3 if r.split else None, M=r.M)
+            if r.zero is not None:
+                r.zero.zero_()
+            self._ex_gemm(r.g, lay.w3t[0], r.dctx, EPI_F32, a3, M=r.M, presplit=r.split)
             ops.attn_bwd_f32(ws["qkv32s"][l], ws["dctx32"], ws["ctx32s"][l], ws["lse"][l], B, S, self.heads, scale, ws["dqkv32"],
                              dqkv_split3=a3 if l > 0 else None)      # the QKV dX GEMM's operand, written split by the attention kernel
             has = self._lora_index[l] is not None
@@ -824,7 +811,6 @@ class ViTEngine(EncoderEngineBase):
                                           lora_b=self.lora_b(l) if has else None)
                 self._ex_gemm3(a3, wt, ws["dh32"], EPI_F32, M)
                 ops.layernorm_bwd(x[2 * l], ws["st1"][l], lay.ln1[0], 0, g_resid=dx, g_gemm=ws["dh32"], dx_f32=dx, dx_split3=a3)
-                dx3 = True
 
 # ======================================================================================================= BERT
 class BertEngine(EncoderEngineBase):
@@ -906,7 +892,7 @@ class BertEngine(EncoderEngineBase):
         ws["emb"] = z(M, H, dt=F32)
         ws["yb"] = [z(M, H + KPAD) for _ in range(L + 1)]   # LN outputs feeding each layer's QKV GEMM (+ LoRA t)
         mode = self.mode
-        rb = ws["resid_bf16"] = mode.resid_stream_bf16 and not self.full_ft and not self.fp8
+        rb = ws["resid_bf16"] = self.resid_bf16
         sdt = h16 if rb else F32
         ws["y"] = z(M, H, dt=F32)                           # f32 copy of the current layer input (residual; bf16 stream: head input only)
         ws["ym"] = None if rb else z(M, H, dt=F32)
@@ -933,7 +919,7 @@ class BertEngine(EncoderEngineBase):
             ws["t"] = [z(M, KPAD) for _ in range(L)]
             ws["ymb8"], ws["act8"] = z(M, H, dt=ops.FP8), z(M, FF, dt=ops.FP8)
         if self.exact():
-            assert not rb and not mode.grad_stream_bf16, "the exact forward runs on the f32 streams"
+            assert not rb and not self.grad_bf16, "the exact forward runs on the f32 streams"
             # per layer, all f32: the layer input (ys[l]; ys[L] = the last hidden state), q | k | v, attention output, intermediate
             # pre-activation -- what the exact backward reads
             ws["ys"] = [ws["y"]] + [z(M, H, dt=F32) for _ in range(L)]
@@ -959,7 +945,7 @@ class BertEngine(EncoderEngineBase):
                 ws["mp"], ws["mp32"] = z(B, H), z(B, H, dt=F32)
             return self._keep_workspace(ws)
         # backward temporaries
-        ws["grad_bf16"] = mode.grad_stream_bf16 and not self.full_ft
+        ws["grad_bf16"] = self.grad_bf16
         gdt = BF16 if ws["grad_bf16"] else F32       # residual-gradient stream (mode.grad_stream_bf16)
         ws["ds"] = z(M, H, dt=gdt)
         ws["dsb"] = z(M, H)
