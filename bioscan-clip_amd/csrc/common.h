@@ -184,16 +184,22 @@ __device__ __forceinline__ float dgelu_f(float x) {
 }
 
 // ---- OCP fp8 e4m3 (gfx950: e4m3fn, max 448, no infinities) ---------------------------------------------
-// v_cvt_pk_fp8_f32 rounds to nearest even; inputs are clamped to +-448 first so an overflow saturates instead of becoming
-// NaN (0x7f).  Four values -> one dword, element i in byte i.
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-    a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f);
-    b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
-    c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f);
-    d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
+// v_cvt_pk_fp8_f32 rounds to nearest even and gives an overflow the NaN code 0x7f, so finite values and infinities are clamped to
+// +-448 first: they saturate.  A NaN skips the clamp -- v_med3_f32 returns the smaller bound when an operand is NaN, which turned
+// every NaN into -448 (0xfe) and hid it from whatever looks downstream (BSCLIP_DETECT_ANOMALY) -- and converts to 0x7f / 0xff.
+// Four values -> one dword, element i in byte i.
+__device__ __forceinline__ float sat_e4m3(float v) {
+    const float c = __builtin_amdgcn_fmed3f(v, -448.0f, 448.0f);
+    return v != v ? v : c;
+}
+// the bare conversion: for callers that have bounded their values themselves (|v| <= 448 or NaN)
+__device__ __forceinline__ unsigned cvt_fp8x4(float a, float b, float c, float d) {
     int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
     w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return (unsigned)w;
+}
+__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
+    return cvt_fp8x4(sat_e4m3(a), sat_e4m3(b), sat_e4m3(c), sat_e4m3(d));
 }
 __device__ __forceinline__ float fp8_to_f32(unsigned w, int byte) {  // byte is a compile-time constant at every call site
     switch (byte) {

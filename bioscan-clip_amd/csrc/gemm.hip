@@ -1016,9 +1016,14 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                         *reinterpret_cast<unsigned*>(slab2 + (16 * i + fr) * S8 + (64 * wc + 32 * ni + 16 * j + 4 * fq)) =
                             dg8_pack4(dg0, dg1);
                         if constexpr (EPI == BSCLIP_EPI_GELU_FP8) {  // the next GEMM's fp8 operand: e4m3, scale 1, saturated
+                            // The saturation is taken on the pre-activation x: gelu(x) <= x (x cdf, cdf <= 1), so x >= 448 -> 448 is the
+                            // upper bound, +inf included (whose table arithmetic is inf - inf); a NaN x fails the comparison and
+                            // keeps its NaN gelu, which converts to the NaN code.  No lower bound is needed: gelu >= -0.17 down to
+                            // x ~ -7e17, where x Phi(-8) itself passes -448 (and -inf is inf - inf = NaN: it shows as the NaN code).
+                            auto sat = [](float x, float gl) { return x >= 448.0f ? 448.0f : gl; };
                             *reinterpret_cast<unsigned*>((g ? smem + 64 * SB : smem) + (16 * i + fr) * S8 +
                                                          (64 * wc + 32 * ni + 16 * j + 4 * fq)) =
-                                pack_fp8x4(gl0[0], gl0[1], gl1[0], gl1[1]);
+                                cvt_fp8x4(sat(v[0], gl0[0]), sat(v[1], gl0[1]), sat(v[2], gl1[0]), sat(v[3], gl1[1]));
                             continue;
                         }
                         o.x = pack_h2<F16>(gl0[0], gl0[1]);

@@ -124,7 +124,11 @@ int bsclip_epi_args_size(void);
  *   (bsclip_lora_baug_set).  ld_* in bf16 elements, % 8 == 0.
  * form: 1 = v_mfma_f32_16x16x32_fp8_fp8 (bf16 MFMA rate, half the operand bytes); 2 = v_mfma_scale_f32_16x16x128_f8f6f4 with
  *   unit block scales (2x the bf16 MFMA rate).  Identical results (exact products, f32 accumulation; summation order differs).
- * epilogue: BSCLIP_EPI_BF16, _F32, _RESID_F32 (+ dropout), _GELU_FP8.  args->bias is required. */
+ * epilogue: BSCLIP_EPI_BF16, _F32, _RESID_F32 (+ dropout), _GELU_FP8.  args->bias is required.
+ * Every e4m3 value this library writes (bsclip_layernorm_fwd_fp8, _GELU_FP8, bsclip_quantize_rows_fp8) is rounded to nearest even at
+ *   scale 1 and saturated at +-448: a finite value beyond the bound and +-inf become 0x7e / 0xfe.  A NaN is NOT saturated: it is
+ *   written as the NaN code (0x7f / 0xff) and stays NaN through the next GEMM, where a non-finite check can see it.  _GELU_FP8
+ *   saturates on its pre-activation x (x >= 448, +inf included, -> 0x7e); x = -inf or NaN gives the NaN code. */
 typedef struct bsclip_fp8_args {
     uint32_t struct_size; /* = sizeof(bsclip_fp8_args) */
     int form;
@@ -224,7 +228,8 @@ int bsclip_attn_bwd_pers_diag(const void* qkv, int ld_qkv, const void* dctx, int
 int bsclip_layernorm_fwd(const void* x, int ld_x, int x_bf16, int M, int H, const float* gamma, const float* beta,
                          float eps, void* y_bf16, int ld_y, float* y_f32, void* y_split3, int ld_y3, const float* lora_a, float* stats,
                          float dropout_p, uint32_t dropout_seed, void* stream);
-/* fp8 operand variant (configs[4]): y_fp8 [M, ld_y bytes] = e4m3(LN(x)) (scale 1, saturated), t_aug bf16 [M, ld_t] = the LoRA
+/* fp8 operand variant (configs[4]): y_fp8 [M, ld_y bytes] = e4m3(LN(x)) (scale 1, saturated at +-448; a NaN row -- a NaN or an
+ * infinity in x -- is written as NaN codes, see bsclip_gemm_fp8), t_aug bf16 [M, ld_t] = the LoRA
  * block (t in cols [0,8), zeros to col 64) when lora_a != NULL -- the operands of bsclip_gemm_fp8.  Other arguments as above. */
 int bsclip_layernorm_fwd_fp8(const void* x, int ld_x, int x_bf16, int M, int H, const float* gamma, const float* beta,
                              float eps, void* y_fp8, int ld_y, void* t_aug, int ld_t, float* y_f32, const float* lora_a,
