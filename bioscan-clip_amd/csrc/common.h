@@ -309,3 +309,25 @@ void bsclip_launch_attn_bwd_x3(const float* qkv, int ld_qkv, const float* dctx, 
 int bsclip_gemm_infonce(int mode, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                         const int64_t* labels, const float* cnt, const float* lse_row, const float* lse_col, float* part,
                         float logit_scale, float coef, int n_valid, int row_base, void* stream);
+
+// gemm.hip, internal: nb <= BSCLIP_GEMM_BATCH_MAX products of one shape in ONE launch of the 128x128 gemm_nt_kernel program, the
+// product on blockIdx.z and its operand pointers in a table passed by value.  epilogue: BSCLIP_EPI_F32, or BSCLIP_EPI_RESID_F32
+// accumulating into C in place.  bsclip_gemm_batched_ok: bsclip_gemm_bf16 would run this shape on the same 128x128 tile.
+constexpr int BSCLIP_GEMM_BATCH_MAX = 6;
+struct bsclip_gemm_batch {
+    const void* A[BSCLIP_GEMM_BATCH_MAX];
+    const void* B[BSCLIP_GEMM_BATCH_MAX];
+    void* C[BSCLIP_GEMM_BATCH_MAX];
+};
+bool bsclip_gemm_batched_ok(int M, int N, int K, int epilogue);
+int bsclip_gemm_bf16_batched(const bsclip_gemm_batch& t, int nb, int lda, int ldb, int ldc, int M, int N, int K, int epilogue,
+                             void* stream);
+
+// norm.hip, internal: bsclip_l2norm_bwd of nb <= 3 separately allocated [M, D] problems in one launch (problem on blockIdx.y)
+struct bsclip_l2norm_bwd_batch {
+    const float* y[3];
+    const float* inv_norm[3];
+    const float* dy[3];
+    float* dx[3];
+};
+int bsclip_l2norm_bwd_batched(const bsclip_l2norm_bwd_batch& t, int nb, int M, int D, void* stream);

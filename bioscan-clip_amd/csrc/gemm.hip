@@ -232,122 +232,25 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const bf
                                                                          const bf16_t* __restrict__ B, int ldb,
                                                                          void* __restrict__ C, int ldc, int M, int N,
                                                                          int K, int tiles_n, EpiArgs e) {
-    constexpr int NW = WAVES_M * WAVES_N;
-    constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;  // per-wave output tile
-    if constexpr (epi_is_resid(EPI)) BSCLIP_DROP_RESOLVE(e.drop);
-    constexpr int TM = WTM / 16, TN = WTN / 16;
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-    constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-    constexpr int A_PER_WAVE = BM / 8 / NW, B_PER_WAVE = BN / 8 / NW;
-    static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "staging split");
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_BYTES];
+#include "gemm_nt_body.h"   // the workgroup program, shared with gemm_nt_batched_kernel
+}
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = wg % tiles_n, tile_m = wg / tiles_n;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-
-    // ---- staging sources: wave-instruction q covers tile rows [8q, 8q+8); lane -> (row, swizzled chunk) ----
-    const bf16_t* a_src[A_PER_WAVE];
-    const bf16_t* b_src[B_PER_WAVE];
-#pragma unroll
-    for (int i = 0; i < A_PER_WAVE; ++i) {
-        const int row = (wave + i * NW) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        const int grow = min(m0 + row, M - 1);
-        a_src[i] = A + (size_t)grow * lda + c * 8;
+// Up to BSCLIP_GEMM_BATCH_MAX products of ONE shape in one launch (the small-N InfoNCE: 4 tiles per product, 6 products): problem
+// blockIdx.z takes its operand pointers from the table, passed by value, and runs the same workgroup program -- the same text,
+// gemm_nt_body.h, so gemm_nt_kernel itself compiles to what it was.  No bias, bf16 operands.  The RESID epilogue accumulates in
+// place: resid is the problem's own C.
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_batched_kernel(bsclip_gemm_batch t, int lda, int ldb, int ldc,
+                                                                                 int M, int N, int K, int tiles_n, EpiArgs e) {
+    constexpr bool HAS_BIAS = false, F16 = false;
+    const bf16_t* __restrict__ A = static_cast<const bf16_t*>(t.A[blockIdx.z]);
+    const bf16_t* __restrict__ B = static_cast<const bf16_t*>(t.B[blockIdx.z]);
+    void* __restrict__ C = t.C[blockIdx.z];
+    if constexpr (epi_is_resid(EPI)) {
+        e.resid = static_cast<const float*>(C);
+        e.ld_resid = ldc;
     }
-#pragma unroll
-    for (int i = 0; i < B_PER_WAVE; ++i) {
-        const int row = (wave + i * NW) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        const int grow = min(n0 + row, N - 1);
-        b_src[i] = B + (size_t)grow * ldb + c * 8;
-    }
-    auto stage = [&](int buf, int k0) {
-        char* sA = smem + buf * STAGE_BYTES;
-        char* sB = sA + A_BYTES;
-#pragma unroll
-        for (int i = 0; i < A_PER_WAVE; ++i) glds16(a_src[i] + k0, sA + (wave + i * NW) * 1024);
-#pragma unroll
-        for (int i = 0; i < B_PER_WAVE; ++i) glds16(b_src[i] + k0, sB + (wave + i * NW) * 1024);
-    };
-
-    // ---- fragment read offsets (bytes) within a tile ----
-    const int fr = lane & 15, fq = lane >> 4;
-    const int sw = fr >> 1;  // (row>>1)&7 for rows that are 16-aligned + fr
-    const int a_off0 = (wm * WTM + fr) * ROW_BYTES + ((fq ^ sw) << 4);        // ks = 0
-    const int b_off0 = (wn * WTN + fr) * ROW_BYTES + ((fq ^ sw) << 4);
-    // ks = 1 adds chunk 4: (4 + fq) ^ sw == (fq ^ sw) ^ 4  -> byte offset ^ 64
-
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = K / BK;
-    stage(0, 0);
-    __syncthreads();  // drains the LDS-DMA (vmcnt(0)) and publishes the tile
-
-    for (int t = 0; t < nk; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < nk) stage(cur ^ 1, (t + 1) * BK);
-        const char* sA = smem + cur * STAGE_BYTES;
-        const char* sB = sA + A_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 af[TM], bfr[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                bfr[j] = *reinterpret_cast<const bf16x8*>(sB + ((b_off0 ^ (ks << 6)) + j * 16 * ROW_BYTES));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[i] = *reinterpret_cast<const bf16x8*>(sA + ((a_off0 ^ (ks << 6)) + i * 16 * ROW_BYTES));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = mfma16x16x32<F16>(bfr[j], af[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: lane holds C[m][n..n+3] with m = ... + (lane&15), n = ... + (lane>>4)*4 ----
-    f32x4 bias[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        bias[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (HAS_BIAS) bias[j] = *reinterpret_cast<const f32x4*>(e.bias + n0 + wn * WTN + j * 16 + fq * 4);
-    }
-    // bias is consumed before the row guards: a loaded register live across a divergent branch makes hipcc wait
-    // vmcnt(0) (which also drains the previous row's stores) at the top of every guarded block
-    if constexpr (HAS_BIAS) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] += bias[j];
-    }
-    // Row guards only on the last (partial) M tile: per-row divergent branches make hipcc drain vmcnt(0) -- loads AND
-    // the previous row's stores -- at the top of every guarded block.
-    auto store_rows = [&](auto guard) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm * WTM + i * 16 + fr;
-            if (!decltype(guard)::value || m < M) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int n = n0 + wn * WTN + j * 16 + fq * 4;
-                    epilogue_store<EPI, F16>(acc[i][j], m, n, C, ldc, e);
-                }
-            }
-        }
-    };
-    if (m0 + BM <= M) store_rows(std::false_type{});
-    else store_rows(std::true_type{});
+#include "gemm_nt_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1188,15 +1091,10 @@ void launch_pp(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int 
                        ldb, C, ldc, M, N, K, tiles_n, e);
 }
 
-// F16: fp16 operands (BSCLIP_OPERANDS_FP16).  The same tile selection as bf16, except that the duo kernel (bsclip_gemm_set_tile(5),
-// BSCLIP_GEMM_DUO=1) has no fp16 form: the ping-pong kernel takes its shapes.
-template <int EPI, bool HB, bool F16>
-void launch_epi(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
-                const EpiArgs& e, hipStream_t s) {
-    if (EPI == BSCLIP_EPI_GELU_BF16 && !g_lut_ready) {  // once per process, stream-ordered ahead of the first consumer
-        hipLaunchKernelGGL(gelu_lut_init_kernel, dim3(ceil_div(GELU_LUT_N + 1, 256)), dim3(256), 0, s);
-        g_lut_ready = true;
-    }
+// which kernel launch_epi runs for a shape (the switch below): 1 = 128x128, 2 = 256x128, 3 = 256x256 plain, 4 = ping-pong, 5 = duo,
+// 8 = persistent.  bsclip_gemm_bf16_batched asks too: it only has the 128x128 form and must agree with the single launch.
+template <int EPI, bool F16>
+int pick_tile(int M, int N, int K) {
     int tile = g_tile_override;
     if (tile == 0) {
         // 256x256 (8 waves, 1 block/CU) halves L2->LDS traffic per FLOP; fall back when N is not a multiple of
@@ -1218,6 +1116,19 @@ void launch_epi(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int
     }
     if (F16 && tile == 5) tile = 4;
     if ((tile == 3 || tile == 4 || tile == 6 || tile == 7 || tile == 8) && N % 256 != 0) tile = 2;
+    return tile;
+}
+
+// F16: fp16 operands (BSCLIP_OPERANDS_FP16).  The same tile selection as bf16, except that the duo kernel (bsclip_gemm_set_tile(5),
+// BSCLIP_GEMM_DUO=1) has no fp16 form: the ping-pong kernel takes its shapes.
+template <int EPI, bool HB, bool F16>
+void launch_epi(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
+                const EpiArgs& e, hipStream_t s) {
+    if (EPI == BSCLIP_EPI_GELU_BF16 && !g_lut_ready) {  // once per process, stream-ordered ahead of the first consumer
+        hipLaunchKernelGGL(gelu_lut_init_kernel, dim3(ceil_div(GELU_LUT_N + 1, 256)), dim3(256), 0, s);
+        g_lut_ready = true;
+    }
+    const int tile = pick_tile<EPI, F16>(M, N, K);
     switch (tile) {
         case 4: launch_pp<EPI, HB, F16>(A, lda, B, ldb, C, ldc, M, N, K, e, s); break;
         case 5:
@@ -1570,6 +1481,45 @@ int bsclip_gemm_infonce(int mode, const void* A, int lda, const void* B, int ldb
         hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LOSS_W, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
                            ldc, M, N, K, tiles_n, e);
     }
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// several small products of one shape in one launch (called by loss.hip; not part of the public ABI)
+// ---------------------------------------------------------------------------------------------------------------
+// true when bsclip_gemm_bf16 runs this shape on the 128x128 tile -- the only form the batched launch has.  The caller falls back
+// to one bsclip_gemm_bf16 per product otherwise (bsclip_gemm_set_tile), so both ways always run the same workgroup program.
+bool bsclip_gemm_batched_ok(int M, int N, int K, int epilogue) {
+    if (M <= 0 || N <= 0 || N % 128 != 0 || K <= 0 || K % 64 != 0) return false;
+    if (epilogue == BSCLIP_EPI_F32) return pick_tile<BSCLIP_EPI_F32, false>(M, N, K) == 1;
+    if (epilogue == BSCLIP_EPI_RESID_F32) return pick_tile<BSCLIP_EPI_RESID_F32, false>(M, N, K) == 1;
+    return false;
+}
+
+// C_i = A_i[M,K] . B_i[N,K]^T (BSCLIP_EPI_F32) or C_i += A_i . B_i^T (BSCLIP_EPI_RESID_F32, in place), i < nb
+int bsclip_gemm_bf16_batched(const bsclip_gemm_batch& t, int nb, int lda, int ldb, int ldc, int M, int N, int K, int epilogue,
+                             void* stream) {
+    BSCLIP_REQUIRE(nb >= 1 && nb <= BSCLIP_GEMM_BATCH_MAX, "bsclip_gemm_bf16_batched: nb=%d", nb);
+    BSCLIP_REQUIRE(bsclip_gemm_batched_ok(M, N, K, epilogue), "bsclip_gemm_bf16_batched: M=%d N=%d K=%d epilogue=%d is not a 128x128 shape",
+                   M, N, K, epilogue);
+    BSCLIP_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && ldc >= N && ldc % 4 == 0,
+                   "bsclip_gemm_bf16_batched: lda=%d ldb=%d ldc=%d", lda, ldb, ldc);
+    for (int i = 0; i < nb; ++i)
+        BSCLIP_REQUIRE(t.A[i] && t.B[i] && t.C[i] && (((uintptr_t)t.A[i] | (uintptr_t)t.B[i] | (uintptr_t)t.C[i]) & 15) == 0,
+                       "bsclip_gemm_bf16_batched: operand %d null or not 16-B aligned", i);
+    EpiArgs e{};
+    e.n_total = N;
+    e.drop = make_drop(0.f, 0);
+    const int tiles_m = ceil_div(M, 128), tiles_n = N / 128;
+    const dim3 grid(tiles_m * tiles_n, 1, nb);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (epilogue == BSCLIP_EPI_F32)
+        hipLaunchKernelGGL((gemm_nt_batched_kernel<128, 128, 2, 2, BSCLIP_EPI_F32>), grid, dim3(256), 0, s, t, lda, ldb, ldc, M, N, K,
+                           tiles_n, e);
+    else
+        hipLaunchKernelGGL((gemm_nt_batched_kernel<128, 128, 2, 2, BSCLIP_EPI_RESID_F32>), grid, dim3(256), 0, s, t, lda, ldb, ldc, M,
+                           N, K, tiles_n, e);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

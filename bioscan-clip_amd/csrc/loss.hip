@@ -20,7 +20,10 @@
 //     dz^a += W z^b, accumulated in f32.
 // Slab form (bsclip_infonce_set_impl(1), kept for A/B timing and as a second implementation to test against): logits in row
 // slabs of <= 1024 rows as f32 in the workspace, a separate row-reduce / dL/dG kernel reads them back.
+// Batched slab form (the default up to 1024 padded rows, i.e. one slab): the slab form's arithmetic with the logits of all directed
+// pairs kept side by side and one launch per stage over all modalities / pairs (see g_infonce_impl below).
 #include <math.h>
+#include <stdlib.h>
 
 #include "common.h"
 
@@ -33,10 +36,22 @@ __device__ __forceinline__ void split_bf(float x, bf16_t& hi, bf16_t& lo) {
     lo = f2bf(x - bf2f(hi));
 }
 
+// The kernels below come in two launch forms that share their per-row code (the *_rows / *_tile / *_elems device functions): one
+// launch per modality or directed pair (the slab form), and one launch over all of them with the modality / pair on a second grid
+// dimension (the batched form at Np <= SLAB_ROWS).  Up to three separately allocated source tensors go by value:
+struct ModPtrs {
+    const float* z[3];
+};
+// directed pair p in [0, nmod (nmod - 1)) in the order of the (a, b) loops: a = p / (nmod - 1), b skips a
+__device__ __host__ __forceinline__ void pair_ab(int p, int nmod, int& a, int& b) {
+    a = p / (nmod - 1);
+    b = p % (nmod - 1);
+    b += (b >= a);
+}
+
 // One wave per row i in [0, Np): zn = z/max(||z||,eps) (rows >= N are zero), inv, PA = [hi|hi|lo], PB = [hi|lo|hi]
-__global__ __launch_bounds__(256) void loss_prep_kernel(const float* __restrict__ z, int N, int Np, int D,
-                                                         float* __restrict__ zn, float* __restrict__ inv,
-                                                         bf16_t* __restrict__ PA, bf16_t* __restrict__ PB) {
+__device__ __forceinline__ void loss_prep_rows(const float* __restrict__ z, int N, int Np, int D, float* __restrict__ zn,
+                                               float* __restrict__ inv, bf16_t* __restrict__ PA, bf16_t* __restrict__ PB) {
     const int lane = threadIdx.x & 63;
     const int row = (blockIdx.x * 256 + threadIdx.x) >> 6;
     if (row >= Np) return;
@@ -70,10 +85,21 @@ __global__ __launch_bounds__(256) void loss_prep_kernel(const float* __restrict_
         *reinterpret_cast<uint2*>(pb + 2 * D) = hh;
     }
 }
+__global__ __launch_bounds__(256) void loss_prep_kernel(const float* __restrict__ z, int N, int Np, int D,
+                                                         float* __restrict__ zn, float* __restrict__ inv,
+                                                         bf16_t* __restrict__ PA, bf16_t* __restrict__ PB) {
+    loss_prep_rows(z, N, Np, D, zn, inv, PA, PB);
+}
+// modality blockIdx.y; zn / inv / PA / PB are the workspace arrays of modality 0, one modality after the other
+__global__ __launch_bounds__(256) void loss_prep_batched_kernel(ModPtrs src, int N, int Np, int D, float* __restrict__ zn,
+                                                                 float* __restrict__ inv, bf16_t* __restrict__ PA,
+                                                                 bf16_t* __restrict__ PB) {
+    const size_t m = blockIdx.y;
+    loss_prep_rows(src.z[m], N, Np, D, zn + m * Np * D, inv + m * Np, PA + m * Np * 3 * D, PB + m * Np * 3 * D);
+}
 
 // PBt[d, :] = [zn^T hi | zn^T lo | zn^T hi]  (bf16 [D, 3*Np]) through a 64x64 f32 LDS tile
-__global__ __launch_bounds__(256) void loss_transpose_split_kernel(const float* __restrict__ zn, int Np, int D,
-                                                                    bf16_t* __restrict__ PBt) {
+__device__ __forceinline__ void loss_transpose_split_tile(const float* __restrict__ zn, int Np, int D, bf16_t* __restrict__ PBt) {
     __shared__ float tile[64][65];
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;  // r over Np rows, c over D cols
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -89,6 +115,16 @@ __global__ __launch_bounds__(256) void loss_transpose_split_kernel(const float* 
         dst[2 * Np] = h;
     }
 }
+__global__ __launch_bounds__(256) void loss_transpose_split_kernel(const float* __restrict__ zn, int Np, int D,
+                                                                    bf16_t* __restrict__ PBt) {
+    loss_transpose_split_tile(zn, Np, D, PBt);
+}
+// modality blockIdx.z
+__global__ __launch_bounds__(256) void loss_transpose_split_batched_kernel(const float* __restrict__ zn, int Np, int D,
+                                                                            bf16_t* __restrict__ PBt) {
+    const size_t m = blockIdx.z;
+    loss_transpose_split_tile(zn + m * Np * D, Np, D, PBt + m * D * 3 * Np);
+}
 
 // cnt[i] = #{j : label_j == label_i}; one thread per i (N <= 8192: O(N^2) int compares, negligible)
 __global__ void loss_count_kernel(const int64_t* __restrict__ labels, int N, float* __restrict__ cnt) {
@@ -101,10 +137,9 @@ __global__ void loss_count_kernel(const int64_t* __restrict__ labels, int N, flo
 }
 
 // One wave per row i < N of G (cosines, ld = Np): LSE_i of s*G over j < N, and contrib_i = cnt_i*LSE_i - sum_j T_ij s G_ij
-__global__ __launch_bounds__(256) void loss_row_reduce_kernel(const float* __restrict__ G, int row0, int nrows, int N,
-                                                               int Np, float s, const int64_t* __restrict__ labels,
-                                                               const float* __restrict__ cnt, float* __restrict__ lse,
-                                                               float* __restrict__ contrib) {
+__device__ __forceinline__ void loss_row_reduce_rows(const float* __restrict__ G, int row0, int nrows, int N, int Np, float s,
+                                                     const int64_t* __restrict__ labels, const float* __restrict__ cnt,
+                                                     float* __restrict__ lse, float* __restrict__ contrib) {
     const int lane = threadIdx.x & 63;
     const int r = (blockIdx.x * 256 + threadIdx.x) >> 6;  // row inside the slab
     if (r >= nrows) return;
@@ -128,13 +163,30 @@ __global__ __launch_bounds__(256) void loss_row_reduce_kernel(const float* __res
         contrib[row] = cnt[row] * l - dot;
     }
 }
+__global__ __launch_bounds__(256) void loss_row_reduce_kernel(const float* __restrict__ G, int row0, int nrows, int N,
+                                                               int Np, float s, const int64_t* __restrict__ labels,
+                                                               const float* __restrict__ cnt, float* __restrict__ lse,
+                                                               float* __restrict__ contrib) {
+    loss_row_reduce_rows(G, row0, nrows, N, Np, s, labels, cnt, lse, contrib);
+}
+// directed pair blockIdx.y: all N rows of its kept logits matrix G[p] ([Np, Np]); lse / contrib are indexed by slot a * nmod + b
+__global__ __launch_bounds__(256) void loss_row_reduce_batched_kernel(const float* __restrict__ G, int nmod, int N, int Np, float s,
+                                                                       const int64_t* __restrict__ labels,
+                                                                       const float* __restrict__ cnt, float* __restrict__ lse,
+                                                                       float* __restrict__ contrib) {
+    const int p = blockIdx.y;
+    int a, b;
+    pair_ab(p, nmod, a, b);
+    const size_t slot = a * nmod + b;
+    loss_row_reduce_rows(G + (size_t)p * Np * Np, 0, N, N, Np, s, labels, cnt, lse + slot * Np, contrib + slot * Np);
+}
 
 // W[i_local, j] = coef * ( cnt_i exp(sG - lse_ab[i]) + cnt_j exp(sG - lse_ba[j]) - 2 T_ij ), j < N, else 0,
 // written as the split GEMM operand [hi | hi | lo] (bf16 [n_local, 3*Np]).
-__global__ __launch_bounds__(256) void loss_w_kernel(const float* __restrict__ G, int N, int Np, int row0, int n_local,
-                                                      float s, float coef, const int64_t* __restrict__ labels,
-                                                      const float* __restrict__ cnt, const float* __restrict__ lse_ab,
-                                                      const float* __restrict__ lse_ba, bf16_t* __restrict__ W) {
+__device__ __forceinline__ void loss_w_elems(const float* __restrict__ G, int N, int Np, int row0, int n_local, float s,
+                                             float coef, const int64_t* __restrict__ labels, const float* __restrict__ cnt,
+                                             const float* __restrict__ lse_ab, const float* __restrict__ lse_ba,
+                                             bf16_t* __restrict__ W) {
     const long total = (long)n_local * Np;
     for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
         const int il = (int)(it / Np), j = (int)(it % Np);
@@ -152,6 +204,24 @@ __global__ __launch_bounds__(256) void loss_w_kernel(const float* __restrict__ G
         dst[Np] = h;
         dst[2 * Np] = l;
     }
+}
+__global__ __launch_bounds__(256) void loss_w_kernel(const float* __restrict__ G, int N, int Np, int row0, int n_local,
+                                                      float s, float coef, const int64_t* __restrict__ labels,
+                                                      const float* __restrict__ cnt, const float* __restrict__ lse_ab,
+                                                      const float* __restrict__ lse_ba, bf16_t* __restrict__ W) {
+    loss_w_elems(G, N, Np, row0, n_local, s, coef, labels, cnt, lse_ab, lse_ba, W);
+}
+// directed pair blockIdx.y: rows [row0, row0 + n_local) of its kept logits matrix G[p] -> W[p] ([n_local, 3 Np], w_stride apart)
+__global__ __launch_bounds__(256) void loss_w_batched_kernel(const float* __restrict__ G, int nmod, int N, int Np, int row0,
+                                                              int n_local, float s, float coef,
+                                                              const int64_t* __restrict__ labels, const float* __restrict__ cnt,
+                                                              const float* __restrict__ lse, bf16_t* __restrict__ W,
+                                                              size_t w_stride) {
+    const int p = blockIdx.y;
+    int a, b;
+    pair_ab(p, nmod, a, b);
+    loss_w_elems(G + ((size_t)p * Np + row0) * Np, N, Np, row0, n_local, s, coef, labels, cnt, lse + (size_t)(a * nmod + b) * Np,
+                 lse + (size_t)(b * nmod + a) * Np, W + p * w_stride);
 }
 
 // loss = scale * sum over the directed pairs a != b of contrib[(a*nmod+b)*Np + i], i < N -- single workgroup, fixed order
@@ -196,9 +266,16 @@ __global__ __launch_bounds__(256) void infonce_combine_kernel(const float* __res
 
 // 0 = by size (default): below 2 048 padded rows a product is <= 8 x 8 tiles of the 256 x 256 GEMM -- at the bench's N = 256 ONE
 // tile per directed pair, 255 CUs idle -- and the slab form on 128 x 128 tiles is faster (0.18 vs 0.28 ms at N = 256, 1.35 vs
-// 1.27 at N = 2 048, 8.3 vs 4.5 at N = 8 192: profiles/r02_e_infonce_fused_vs_slab.log); 1 = f32 logits slabs + separate reduce
-// kernels; 2 = fused epilogues
+// 1.27 at N = 2 048, 8.3 vs 4.5 at N = 8 192: profiles/r02_e_infonce_fused_vs_slab.log).  Up to SLAB_ROWS padded rows (one slab)
+// the slab form is launched BATCHED: even on 128 x 128 tiles a product is 4 workgroups at N = 256, and the section is a strict
+// chain of 41 such launches (nmod = 3) between the towers' forward and backward, where nothing overlaps with it.  The batched
+// form keeps the logits of all directed pairs (pass 2 re-formed each one), and runs every stage as one launch over all
+// modalities / pairs: 10 launches (9 at nmod = 2), the same device code per element, so the same bits as impl 1
+// (tests/test_11_infonce_batched_gpu.py; timings: profiles/infonce_batched.jsonl);
+// 1 = f32 logits slabs + separate reduce kernels, one launch per modality / pair / slab; 2 = fused epilogues
 int g_infonce_impl = 0;
+// BSCLIP_INFONCE_BATCHED=0: impl 0 takes the launch-by-launch slab form below SLAB_ROWS too (A/B switch, read once at load)
+const bool g_infonce_batched_off = getenv("BSCLIP_INFONCE_BATCHED") && atoi(getenv("BSCLIP_INFONCE_BATCHED")) == 0;
 
 inline int64_t align4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 
@@ -220,8 +297,10 @@ Layout make_layout(int N, int nmod, int D) {
     L.PA = o;      o += align4((int64_t)nmod * Np * 3 * D / 2);
     L.PB = o;      o += align4((int64_t)nmod * Np * 3 * D / 2);
     L.PBt = o;     o += align4((int64_t)nmod * D * 3 * Np / 2);
-    L.G = o;       o += align4(SL * Np);
-    L.W = o;       o += align4(SL * 3 * Np / 2);
+    // one slab (Np <= SLAB_ROWS): room for the logits and dL/dG of every directed pair at once (the batched form)
+    const int64_t keep = Np <= SLAB_ROWS ? nmod * (nmod - 1) : 1;
+    L.G = o;       o += align4(keep * SL * Np);
+    L.W = o;       o += align4(keep * SL * 3 * Np / 2);
     L.lse = o;     o += align4((int64_t)nmod * nmod * Np);
     L.contrib = o; o += align4((int64_t)nmod * nmod * Np);
     L.cnt = o;     o += align4(Np);
@@ -267,6 +346,80 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     const bool fused = g_infonce_impl == 2 || (g_infonce_impl == 0 && Np >= 2048);
     const size_t opA = (size_t)Np * 3 * D;  // elements per modality in PA / PB
     const size_t opT = (size_t)D * 3 * Np;  // elements per modality in PBt
+    const int ndir = nmod * (nmod - 1);
+    const bool want_dz = dz && n_local > 0;
+    // the batched form: one slab, and the GEMM would run every product on the 128x128 tile anyway (bsclip_gemm_set_tile can say no)
+    const bool batched = g_infonce_impl == 0 && !g_infonce_batched_off && Np <= SLAB_ROWS &&
+                         bsclip_gemm_batched_ok(N, Np, 3 * D, BSCLIP_EPI_F32) &&
+                         (!want_dz || (bsclip_gemm_batched_ok(n_local, D, 3 * Np, BSCLIP_EPI_F32) &&
+                                       bsclip_gemm_batched_ok(n_local, D, 3 * Np, BSCLIP_EPI_RESID_F32)));
+    if (batched) {
+        ModPtrs src{};
+        for (int m = 0; m < nmod; ++m) {
+            BSCLIP_REQUIRE(z[m], "bsclip_infonce_fwd_bwd: z[%d] is null", m);
+            src.z[m] = z[m];
+        }
+        hipLaunchKernelGGL(loss_prep_batched_kernel, dim3(ceil_div(Np, 4), nmod), dim3(256), 0, s, src, N, Np, D, zn, inv, PA, PB);
+        if (want_dz)
+            hipLaunchKernelGGL(loss_transpose_split_batched_kernel, dim3(D / 64, Np / 64, nmod), dim3(256), 0, s, zn, Np, D, PBt);
+        hipLaunchKernelGGL(loss_count_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, labels, N, cnt);
+        BSCLIP_LAUNCH_CHECK();
+
+        // ---- pass 1: the logits of every directed pair, formed once and kept; row LSE + loss contribution ----
+        const size_t g_stride = (size_t)Np * Np;                 // floats per pair in G
+        const size_t w_stride = (size_t)L.slab * 3 * Np;         // bf16 elements per pair in W
+        bsclip_gemm_batch gl{};
+        for (int p = 0; p < ndir; ++p) {
+            int a, b;
+            pair_ab(p, nmod, a, b);
+            gl.A[p] = PA + a * opA;
+            gl.B[p] = PB + b * opA;
+            gl.C[p] = G + p * g_stride;
+        }
+        int rc = bsclip_gemm_bf16_batched(gl, ndir, 3 * D, 3 * D, Np, N, Np, 3 * D, BSCLIP_EPI_F32, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(loss_row_reduce_batched_kernel, dim3(ceil_div(N, 4), ndir), dim3(256), 0, s, G, nmod, N, Np, scale, labels,
+                           cnt, lse, contrib);
+        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, contrib, nmod, Np, N, 1.0f / ((float)ndir * (float)N),
+                           loss_out);
+        BSCLIP_LAUNCH_CHECK();
+        if (!want_dz) return BSCLIP_OK;
+
+        // ---- pass 2: dL/dG of every pair from the kept logits, then dz_a = sum_b W_ab zn_b: the first partner written, the
+        // second added (the association of the slab form: one K loop over both partners would round differently) ----
+        const float coef = scale / ((float)ndir * (float)N);
+        for (int a = 0; a < nmod; ++a) BSCLIP_REQUIRE(dz[a], "bsclip_infonce_fwd_bwd: dz[%d] is null", a);
+        long blocks = ((long)n_local * Np + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(loss_w_batched_kernel, dim3((unsigned)blocks, ndir), dim3(256), 0, s, G, nmod, N, Np, row0, n_local, scale,
+                           coef, labels, cnt, lse, W, w_stride);
+        for (int k = 0; k < nmod - 1; ++k) {   // k-th partner of every a: pair a * (nmod - 1) + k
+            bsclip_gemm_batch gd{};
+            for (int a = 0; a < nmod; ++a) {
+                const int p = a * (nmod - 1) + k;
+                int pa, b;
+                pair_ab(p, nmod, pa, b);
+                gd.A[a] = W + p * w_stride;
+                gd.B[a] = PBt + b * opT;
+                gd.C[a] = dacc + (size_t)a * Np * D;
+            }
+            rc = bsclip_gemm_bf16_batched(gd, nmod, 3 * Np, 3 * Np, D, n_local, D, 3 * Np,
+                                          k == 0 ? BSCLIP_EPI_F32 : BSCLIP_EPI_RESID_F32, stream);
+            if (rc) return rc;
+        }
+        // Jacobian of the in-loss F.normalize: dz = (g - zn (zn . g)) / ||z||
+        bsclip_l2norm_bwd_batch nb{};
+        for (int a = 0; a < nmod; ++a) {
+            nb.y[a] = zn + ((size_t)a * Np + row0) * D;
+            nb.inv_norm[a] = inv + (size_t)a * Np + row0;
+            nb.dy[a] = dacc + (size_t)a * Np * D;
+            nb.dx[a] = dz[a];
+        }
+        rc = bsclip_l2norm_bwd_batched(nb, nmod, n_local, D, stream);
+        if (rc) return rc;
+        BSCLIP_LAUNCH_CHECK();
+        return BSCLIP_OK;
+    }
 
     for (int m = 0; m < nmod; ++m) {
         BSCLIP_REQUIRE(z[m], "bsclip_infonce_fwd_bwd: z[%d] is null", m);
@@ -279,7 +432,6 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     hipLaunchKernelGGL(loss_count_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, labels, N, cnt);
     BSCLIP_LAUNCH_CHECK();
 
-    const int ndir = nmod * (nmod - 1);
     // ---- pass 1: row LSE + loss contribution of every directed pair ----
     for (int a = 0; a < nmod; ++a)
         for (int b = 0; b < nmod; ++b) {

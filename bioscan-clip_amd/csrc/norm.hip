@@ -352,10 +352,8 @@ __global__ __launch_bounds__(LN_BLOCK) void l2norm_fwd_kernel(const float* __res
 }
 
 // dx = inv * (dy - y (y . dy))   (exact for ||x|| > eps, which holds for every non-degenerate embedding)
-__global__ __launch_bounds__(LN_BLOCK) void l2norm_bwd_kernel(const float* __restrict__ y,
-                                                               const float* __restrict__ inv_norm,
-                                                               const float* __restrict__ dy, int M, int D,
-                                                               float* __restrict__ dx) {
+__device__ __forceinline__ void l2norm_bwd_rows(const float* __restrict__ y, const float* __restrict__ inv_norm,
+                                                const float* __restrict__ dy, int M, int D, float* __restrict__ dx) {
     const int lane = threadIdx.x & 63;
     const int row = (blockIdx.x * LN_BLOCK + threadIdx.x) >> 6;
     if (row >= M) return;
@@ -374,6 +372,19 @@ __global__ __launch_bounds__(LN_BLOCK) void l2norm_bwd_kernel(const float* __res
         const f32x4 g = *reinterpret_cast<const f32x4*>(gr + c);
         *reinterpret_cast<f32x4*>(dx + (size_t)row * D + c) = (g - a * dot) * inv;
     }
+}
+
+__global__ __launch_bounds__(LN_BLOCK) void l2norm_bwd_kernel(const float* __restrict__ y,
+                                                               const float* __restrict__ inv_norm,
+                                                               const float* __restrict__ dy, int M, int D,
+                                                               float* __restrict__ dx) {
+    l2norm_bwd_rows(y, inv_norm, dy, M, D, dx);
+}
+
+// the same rows for up to three separately allocated problems: problem blockIdx.y
+__global__ __launch_bounds__(LN_BLOCK) void l2norm_bwd_batched_kernel(bsclip_l2norm_bwd_batch t, int M, int D) {
+    const int p = blockIdx.y;
+    l2norm_bwd_rows(t.y[p], t.inv_norm[p], t.dy[p], M, D, t.dx[p]);
 }
 
 int ln_grid(int M, int resident_per_cu = 8) {
@@ -525,6 +536,16 @@ extern "C" int bsclip_l2norm_bwd(const float* y, const float* inv_norm, const fl
     BSCLIP_REQUIRE(y && inv_norm && dy && dx && M > 0 && D % 4 == 0, "bsclip_l2norm_bwd: bad args (M=%d D=%d)", M, D);
     hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(ceil_div(M, LN_BLOCK / 64)), dim3(LN_BLOCK), 0,
                        static_cast<hipStream_t>(stream), y, inv_norm, dy, M, D, dx);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+int bsclip_l2norm_bwd_batched(const bsclip_l2norm_bwd_batch& t, int nb, int M, int D, void* stream) {
+    BSCLIP_REQUIRE(nb >= 1 && nb <= 3 && M > 0 && D % 4 == 0, "bsclip_l2norm_bwd_batched: bad args (nb=%d M=%d D=%d)", nb, M, D);
+    for (int i = 0; i < nb; ++i)
+        BSCLIP_REQUIRE(t.y[i] && t.inv_norm[i] && t.dy[i] && t.dx[i], "bsclip_l2norm_bwd_batched: null pointer in problem %d", i);
+    hipLaunchKernelGGL(l2norm_bwd_batched_kernel, dim3(ceil_div(M, LN_BLOCK / 64), nb), dim3(LN_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), t, M, D);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -1,10 +1,12 @@
-"""InfoNCE forward + backward time, fused epilogues vs f32 logits slabs, at the loss sizes of BASELINE configs[1..3]."""
+"""InfoNCE forward + backward time, fused epilogues vs f32 logits slabs, at the loss sizes of BASELINE configs[1..3] and of the
+headline step (N = 256, three modalities).  Up to 1 024 padded rows the default is the slab form in batched launches; "logits slabs"
+is the same arithmetic launch by launch (BSCLIP_INFONCE_BATCHED=0 makes the default take that form too)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bioscan-clip_amd"))
 import torch
 from bioscanclip.hip import ops
-for N, nmod, nl in ((256, 2, 256), (2048, 3, 256), (8192, 3, 1024)):
+for N, nmod, nl in ((256, 2, 256), (256, 3, 256), (2048, 3, 256), (8192, 3, 1024)):
     g = torch.Generator().manual_seed(N)
     zs = [torch.nn.functional.normalize(torch.randn(N, 768, generator=g), dim=-1).cuda() for _ in range(nmod)]
     label = torch.arange(N).cuda()
