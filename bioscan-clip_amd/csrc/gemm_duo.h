@@ -92,12 +92,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
             for (int j = 0; j < 4; ++j) acc[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 fa[2][4], fb[2][4];  // [ks][tile]
 
-#define DUO_BARRIER()                       \
-    do {                                    \
-        __builtin_amdgcn_sched_barrier(0);  \
-        __builtin_amdgcn_s_barrier();       \
-        __builtin_amdgcn_sched_barrier(0);  \
-    } while (0)
     // fragments of one 32-deep k-step (ks) at a time, so the MFMAs of ks = 0 start while the reads of ks = 1 are in flight
     auto readAB = [&](int slotA, int slotB, int ks, bool withB) {
         const char* pa = smem + slotA * PIECE;
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
         // ---- phase (t,0): pieces 3t, 3t+1 landed; 3t+2 (and 3t+3) may fly ----
         if (has1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        DUO_BARRIER();
+        GEMM_BARRIER();
         if (t == 0) stamp(1);
         readAB(sA0, sB, 0, true);
         readAB(sA0, sB, 1, true);
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
         // ---- phase (t,1): piece 3t+2 landed; 3t+3, 3t+4 may fly ----
         if (has1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DUO_BARRIER();
+        GEMM_BARRIER();
         readAB(sA1, sB, 0, false);
         readAB(sA1, sB, 1, false);
         __builtin_amdgcn_sched_barrier(0);
@@ -158,7 +152,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
         sA0 = sA0 + 3 >= NSLOT ? sA0 + 3 - NSLOT : sA0 + 3;
         sA1 = sA1 + 3 >= NSLOT ? sA1 + 3 - NSLOT : sA1 + 3;
     }
-#undef DUO_BARRIER
     stamp(2);
 
     // ---- epilogue -------------------------------------------------------------------------------------------------
@@ -243,20 +236,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
             for (int it = 0; it < 16; ++it) {
                 const int r = it * 8 + (tid >> 5);
                 const int m = min(m0 + 128 * (r >> 6) + 64 * mi + (r & 63), M - 1);
-                const int n = n0 + (tid & 31) * 4;
-                if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
-                    R[it] = *reinterpret_cast<const f32x4*>(e.resid + (size_t)m * e.ld_resid + n);
-                } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
-                    R[it] = bf4_to_f32(*reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(e.resid) + (size_t)m * e.ld_resid + n));
-                } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
-                    R[it] = dg8_unpack4(*reinterpret_cast<const unsigned*>(e.aux + (size_t)m * e.ld_aux + n));
-                } else if constexpr (epi_is_patch(EPI)) {
-                    R[it] = *reinterpret_cast<const f32x4*>(e.resid + (size_t)(1 + m % 196) * e.ld_resid + n);
-                } else {
-                    R[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
+                R[it] = epi_cook<EPI>(epi_fetch<EPI>(e, m, n0 + (tid & 31) * 4));
             }
         };
+        auto st = [](auto* p, auto w) { nt_store(p, w); };
         prefetch(0, pre[0]);
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -275,31 +258,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo_kernel(const bf16_t* __res
                 const int n = n0 + (tid & 31) * 4;
                 f32x4 v = *reinterpret_cast<const f32x4*>(slab + r * SF + (tid & 31) * 16);
                 if (m < M) {
-                    if constexpr (EPI == BSCLIP_EPI_F32) {
-                        nt_store(static_cast<float*>(C) + (size_t)m * ldc + n, v);
-                    } else if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
+                    if constexpr (epi_is_resid(EPI)) {
                         if (e.drop.thr16) v = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, v);
-                        v += pre[mi][it];
-                        nt_store(static_cast<float*>(C) + (size_t)m * ldc + n, v);
-                    } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
-                        v *= pre[mi][it];
-                        uint2 o;
-                        o.x = pack_bf2(v[0], v[1]);
-                        o.y = pack_bf2(v[2], v[3]);
-                        nt_store(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, o);
-                    } else if constexpr (EPI == BSCLIP_EPI_PATCH_F32) {
-                        const int b = m / 196, p = m - b * 196;
-                        v += pre[mi][it];
-                        nt_store(static_cast<float*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n, v);
-                    } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
-                        if (e.drop.thr16) v = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, v);
-                        v += pre[mi][it];
-                        nt_store(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, f32_to_bf4(v));
-                    } else if constexpr (EPI == BSCLIP_EPI_PATCH_BF16) {
-                        const int b = m / 196, p = m - b * 196;
-                        v += pre[mi][it];
-                        nt_store(static_cast<bf16_t*>(C) + (size_t)(b * 197 + 1 + p) * ldc + n, f32_to_bf4(v));
                     }
+                    epi_finish_store<EPI, false, true>(v, pre[mi][it], m, n, C, ldc, st);
                 }
             }
         }

@@ -28,7 +28,6 @@ constexpr bool pers_supported(int epi) {
 }
 
 typedef unsigned pers_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned pers_u32x2 __attribute__((ext_vector_type(2)));
 template <bool NT, class T>
 __device__ __forceinline__ void pers_store(void* p, T v, bool skip = false) {
     if (skip) return;   // diagnostic build only (tools/gemm_pers_phases.py ABL=1): is the slow start of a tile's K loop the stores?
@@ -158,12 +157,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                     acc[mi][ni][i][j] = mfma16x16x32<F16>(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j]);
         __builtin_amdgcn_s_setprio(0);
     };
-#define PERS_BARRIER()                         \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
     // diagnostic build, per workgroup (100 MHz ticks): {start, end, tiles done, s_memtime cycles start -> end, tile 1: K loop start, K loop end, then after each
     // of the 8 epilogue barriers (stage q / store q, q = 0..3), tile 0: K loop start, K loop end, tile 1: end of K-tile 0..15};
     // 32 slots per workgroup
@@ -190,7 +183,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
     dmaA(1, 0, 2 * BK);
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     if constexpr (GELU) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PERS_BARRIER();
+    GEMM_BARRIER();
     zero_acc();
 
     const int wq = wave & 3;
@@ -198,7 +191,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
     for (;;) {
         const int vn = v + (int)gridDim.x;
         const bool hasN = vn < ntiles;   // wave-uniform
-        if (g == 1) PERS_BARRIER();      // group 1 runs one barrier behind group 0 through the K loop
+        if (g == 1) GEMM_BARRIER();      // group 1 runs one barrier behind group 0 through the K loop
         stamp(done == 0 ? 14 : done == 1 ? 4 : 99);
         for (int t = 0; t < nk; ++t) {
             const int set = (p + t) & 1;
@@ -216,23 +209,23 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                 asm volatile("" : "+s"(vv));
                 plan_tile(vv);
             }
-            PERS_BARRIER();
+            GEMM_BARRIER();
             mma(0, 0);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             // ---- phase 1 ----
             if (do1) dmaB(set ^ 1, 0, k1);
             readA(base, 1);
             if (plan) plan_rows(nxtA, nm0, M - 1, lda);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             mma(1, 0);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             // ---- phase 2 ----
             if (do1) dmaB(set ^ 1, 1, k1);
             readB(base, 1);
             if (plan) plan_rows(nxtB, nn0, N - 1, ldb);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             mma(1, 1);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             // ---- phase 3 ----
             if (in2) {
                 dmaA(set, 0, (t + 2) * 2 * BK);
@@ -244,12 +237,12 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            PERS_BARRIER();
+            GEMM_BARRIER();
             mma(0, 1);
-            PERS_BARRIER();
+            GEMM_BARRIER();
             stamp(done == 1 ? 16 + t : 99);   // diagnostic build: end of K-tile t of the second tile
         }
-        if (g == 0) PERS_BARRIER();  // balance group 1's extra barrier
+        if (g == 0) GEMM_BARRIER();  // balance group 1's extra barrier
         stamp(done == 0 ? 15 : done == 1 ? 5 : 99);
 
         // ---- epilogue of tile (m0, n0); staging in set E and the spare only ----
@@ -355,28 +348,21 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
             // Raw (unconverted) words, so that nothing waits for a load where it is issued.  bf16 residual rows (2 VGPRs per piece)
             // and 8-bit gelu' codes (1 VGPR) are fetched for ALL FOUR slabs of the tile up front -- the fragment registers are dead
             // here -- so only the first slab's consume can see HBM latency; f32 residual rows (4 VGPRs) stay one slab ahead.
-            constexpr bool RAW2 = EPI == BSCLIP_EPI_RESID_BF16, RAW1 = EPI == BSCLIP_EPI_DGELU_BF16;
-            constexpr int DEPTH = (RAW2 || RAW1) ? 4 : 2;
-            using raw_t = std::conditional_t<RAW2, uint2, std::conditional_t<RAW1, unsigned, f32x4>>;
+            using raw_t = epi_raw_t<EPI>;
+            constexpr int DEPTH = std::is_same_v<raw_t, f32x4> ? 2 : 4;
             raw_t pre[DEPTH][8];
             auto prefetch = [&](int q, raw_t (&R)[8]) {
 #pragma unroll
                 for (int it = 0; it < 8; ++it) {
                     const int m = min(m0 + 128 * g + 32 * q + it * 4 + wq, M - 1);
-                    const int n = n0 + le * 4;
-                    if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
-                        R[it] = *reinterpret_cast<const f32x4*>(e.resid + (size_t)m * e.ld_resid + n);
-                    } else if constexpr (RAW2) {
-                        R[it] = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(e.resid) + (size_t)m * e.ld_resid + n);
-                    } else if constexpr (RAW1) {
-                        R[it] = *reinterpret_cast<const unsigned*>(e.aux + (size_t)m * e.ld_aux + n);
-                    }
+                    R[it] = epi_fetch<EPI>(e, m, n0 + le * 4);
                 }
             };
-            auto cooked = [&](const raw_t& r) -> f32x4 {
-                if constexpr (RAW2) return bf4_to_f32<F16>(r);
-                else if constexpr (RAW1) return dg8_unpack4(r);
-                else return r;
+            // pers_store takes native vectors.  The skip flag is captured by value: captured by reference, the product kernels
+            // assemble differently (gemm_epilogue.h says why such forms are kept)
+            auto st = [abl_st](auto* ptr, auto w) {
+                if constexpr (std::is_same_v<decltype(w), uint2>) pers_store<NT>(ptr, epi_u32x2{w.x, w.y}, abl_st);
+                else pers_store<NT>(ptr, w, abl_st);
             };
             auto stage = [&](int q) {
                 const int mi = q >> 1, ih = q & 1;
@@ -399,25 +385,18 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
                     const int n = n0 + le * 4;
                     f32x4 x = *reinterpret_cast<const f32x4*>(slab + r * SF + le * 16);
                     if (m < M) {
-                        if constexpr (EPI == BSCLIP_EPI_F32) {
-                            pers_store<NT>(static_cast<float*>(C) + (size_t)m * ldc + n, x, abl_st);
-                        } else if constexpr (EPI == BSCLIP_EPI_RESID_F32) {
+                        if constexpr (epi_is_resid(EPI)) {
                             if (e.drop.thr16) x = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, x);
-                            x += cooked(R[it]);
-                            pers_store<NT>(static_cast<float*>(C) + (size_t)m * ldc + n, x, abl_st);
+                        }
+                        if constexpr (EPI == BSCLIP_EPI_F32) {   // no second operand: R was never fetched and must not be read
+                            epi_finish_store<EPI, F16>(x, f32x4{}, m, n, C, ldc, st);
                         } else if constexpr (EPI == BSCLIP_EPI_DGELU_BF16) {
-                            x *= cooked(R[it]);
-                            {
-                                const uint2 o = f32_to_bf4<F16>(x);
-                                pers_store<NT>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, pers_u32x2{o.x, o.y}, abl_st);
-                            }
-                        } else if constexpr (EPI == BSCLIP_EPI_RESID_BF16) {
-                            if (e.drop.thr16) x = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, x);
-                            x += cooked(R[it]);
-                            {
-                                const uint2 o = f32_to_bf4<F16>(x);
-                                pers_store<NT>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, pers_u32x2{o.x, o.y}, abl_st);
-                            }
+                            // written out: through epi_finish_store the phase-stamped build of this epilogue assembles differently
+                            x *= epi_cook<EPI, F16>(R[it]);
+                            const uint2 o = f32_to_bf4<F16>(x);
+                            pers_store<NT>(static_cast<bf16_t*>(C) + (size_t)m * ldc + n, epi_u32x2{o.x, o.y}, abl_st);
+                        } else {
+                            epi_finish_store<EPI, F16>(x, epi_cook<EPI, F16>(R[it]), m, n, C, ldc, st);
                         }
                     }
                 }
@@ -453,7 +432,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pers_kernel(const bf16_t* __restr
         n0 = dn0;
         dmaA(p ^ 1, 0, 2 * BK);
     }
-#undef PERS_BARRIER
     stamp(1);
     if constexpr (DIAG) {
         if (tid == 0) {

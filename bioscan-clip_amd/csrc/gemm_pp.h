@@ -1,0 +1,785 @@
+// 256x256 ping-pong GEMM kernel, with the two fused InfoNCE epilogues that run on its accumulator tile.
+//
+// Included by gemm.hip inside its anonymous namespace (shares EpiArgs, the GELU table, BK / ROW_BYTES and the epilogue helpers).
+//
+// LDS: 2 buffer sets x {A[256][64], B[256][64]} bf16 = 128 KiB; a "half" is 128 rows (16 KiB) = 16 wave-instructions of
+// LDS-DMA, two per wave.  Wave w: group g = w>>2 owns output rows [128g, 128g+128) (so it reads only A-half g),
+// wc = w&3 owns output columns [64wc, 64wc+64) (B-half wc>>1).  Per K-tile the wave holds ALL its fragments in
+// registers (A: 2 blocks of 64 rows, B: 2 blocks of 32 columns = 96 VGPRs), loaded in phases 0-2:
+//   phase 0: read A(m0), B(n0) -> MFMA (m0,n0)      DMA: A-half1 of tile t+1
+//   phase 1: read A(m1)        -> MFMA (m1,n0)      DMA: B-half0 of tile t+1
+//   phase 2: read B(n1)        -> MFMA (m1,n1)      DMA: B-half1 of tile t+1
+//   phase 3: (no reads)        -> MFMA (m0,n1)      DMA: A-half0 of tile t+2 ; s_waitcnt vmcnt(2)
+// Hazards (instants = barrier releases; group 1 runs one instant behind group 0):
+//   WAR  A[set] is last read in phase 1, B[set] in phase 2; their re-staging starts two phases later (phase 3 / phase 1
+//        of the next tile), i.e. >= 2 barrier instants after the slower group's reads have been waited for.
+//   RAW  every wave waits (vmcnt) for its own DMA pieces of tile t+1 BEFORE the first barrier of phase 3; the first
+//        reads of tile t+1 (phase 0) come after at least one more barrier for both groups.
+// ABL (diagnostic builds only): ablation mask for tools/gemm_ablate.py -- 1: no MFMA, 2: no LDS fragment reads, 4: no DMA,
+// 8: no barriers.  Results are garbage then; only the K-loop time is of interest.
+// OP: operand type of the main K loop.  0 = bf16 (v_mfma_f32_16x16x32_bf16).  1 / 2 = OCP fp8 e4m3 (BASELINE configs[4]): the
+// SAME LDS image, DMA schedule and ds_read_b128 fragment reads -- a 128-byte LDS row now holds 128 k-elements instead of 64, so
+// LDS-DMA and LDS-read bytes per FLOP halve (tools/gemm_ablate.py: the bf16 loop is limited as much by the DMA stream as by the
+// matrix pipe).  A lane's 16-byte fragment is 16 consecutive k of one row; any assignment of those bytes to MFMA k-slots is
+// valid as long as A and B use the same one, so
+//   OP 1: the two 8-byte halves feed two v_mfma_f32_16x16x32_fp8_fp8 (bf16 rate: gains the bytes only);
+//   OP 2: the fragments of both half-tiles (32 bytes) feed ONE v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales
+//         (E8M0 127): 2x the bf16 MFMA rate.
+// OP 3 = IEEE fp16 (bsclip_gemm_bf16 | BSCLIP_OPERANDS_FP16): OP 0's loop with v_mfma_f32_16x16x32_f16, and every 16-bit value the
+// epilogue reads or writes (C, RESID_BF16's stream) is fp16.
+// An optional LAST K-tile is bf16 (e.a_aug / e.b_aug, 64 columns): the LoRA branch t . B^T stays in bf16 and is added in the
+// accumulator's units (B_aug rows pre-divided by alpha[n]), then alpha[n] dequantises the sum in the epilogue.
+template <int EPI, bool HAS_BIAS, bool DIAG = false, int ABL = 0, int SCHED = 0, int OP = 0>
+__global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restrict__ A, int lda,
+                                                          const bf16_t* __restrict__ B, int ldb, void* __restrict__ C,
+                                                          int ldc, int M, int N, int K, int tiles_n, EpiArgs e) {
+    static_assert(OP == 0 || (SCHED == 0 && ABL == 0), "fp8 / fp16 operands: production schedule only");
+    constexpr bool FP8 = OP == 1 || OP == 2, F16 = OP == 3;
+    if constexpr (EPI == BSCLIP_EPI_F32 && !HAS_BIAS && OP == 0) {   // split-K slabs (gridDim.y == 1: no-op)
+        A += (size_t)blockIdx.y * K;
+        B += (size_t)blockIdx.y * K;
+        C = static_cast<float*>(C) + (size_t)blockIdx.y * e.split_stride;
+    }
+    if constexpr (epi_is_resid(EPI)) BSCLIP_DROP_RESOLVE(e.drop);
+    constexpr int ESZ = FP8 ? 1 : 2;   // bytes per element of the main operands
+    constexpr int SET = 65536, HALF = 16384, B_OFF = 32768;
+    // main loop 128 KiB; epilogue slabs 2x64x1040 (f32) or 4x64x528 (bf16 x2) = 132 KiB, + 16 KiB GELU table
+    __shared__ __attribute__((aligned(16))) char smem[4 * 64 * 528 + (EPI == BSCLIP_EPI_GELU_BF16 || EPI == BSCLIP_EPI_GELU_FP8 ? GELU_LUT_BYTES : 0)];
+
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_n = wg % tiles_n, tile_m = wg / tiles_n;
+    const int m0 = tile_m * 256, n0 = tile_n * 256;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = wave >> 2, wc = wave & 3;
+
+    // ---- LDS-DMA sources: for half h, this wave moves chunks (wave) and (wave+8): rows 128h + 8*chunk + (lane>>3) ----
+    // sources are byte pointers; K-tile t of the main operands starts t * 128 bytes into the row (64 bf16 / 128 fp8 elements)
+    const char* srcA[2][2];
+    const char* srcB[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int row = 128 * h + 8 * (wave + 8 * i) + (lane >> 3);
+            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            srcA[h][i] = reinterpret_cast<const char*>(A) + (size_t)min(m0 + row, M - 1) * lda * ESZ + c * 16;
+            srcB[h][i] = reinterpret_cast<const char*>(B) + (size_t)min(n0 + row, N - 1) * ldb * ESZ + c * 16;
+        }
+    const int nk_main = K / (BK * 2 / ESZ);
+    const bool aug = FP8 && e.a_aug != nullptr;   // wave-uniform
+    const int dma_off = wave * 1024;  // + i*8192 + half*HALF (+ B_OFF) + set*SET
+    // the bf16 K-augmentation tile: its per-lane sources are recomputed when it is staged (once per workgroup) instead of
+    // living in 16 more VGPRs through the whole loop
+    auto aug_src = [&](const bf16_t* base, int ld, int r0, int rmax, int h, int i) {
+        const int row = 128 * h + 8 * (wave + 8 * i) + (lane >> 3);
+        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        return reinterpret_cast<const char*>(base) + (size_t)min(r0 + row, rmax) * ld * 2 + c * 16;
+    };
+    auto dmaA = [&](int set, int h, int k0) {   // k0 = K-tile index * 128 (byte offset into the row)
+        if constexpr (ABL & 4) return;
+        char* d = smem + set * SET + h * HALF + dma_off;
+        if (FP8 && aug && k0 == nk_main * 128) {
+            glds16(aug_src(e.a_aug, e.ld_a_aug, m0, M - 1, h, 0), d);
+            glds16(aug_src(e.a_aug, e.ld_a_aug, m0, M - 1, h, 1), d + 8192);
+        } else {
+            glds16(srcA[h][0] + k0, d);
+            glds16(srcA[h][1] + k0, d + 8192);
+        }
+    };
+    auto dmaB = [&](int set, int h, int k0) {
+        if constexpr (ABL & 4) return;
+        char* d = smem + set * SET + B_OFF + h * HALF + dma_off;
+        if (FP8 && aug && k0 == nk_main * 128) {
+            glds16(aug_src(e.b_aug, e.ld_b_aug, n0, N - 1, h, 0), d);
+            glds16(aug_src(e.b_aug, e.ld_b_aug, n0, N - 1, h, 1), d + 8192);
+        } else {
+            glds16(srcB[h][0] + k0, d);
+            glds16(srcB[h][1] + k0, d + 8192);
+        }
+    };
+
+    // ---- fragment read offsets ----
+    const int fr = lane & 15, fq = lane >> 4;
+    const int sw = fr >> 1;
+    const int a_off = (128 * g + fr) * ROW_BYTES + ((fq ^ sw) << 4);
+    const int b_off = B_OFF + (64 * wc + fr) * ROW_BYTES + ((fq ^ sw) << 4);
+
+    f32x4 acc[2][2][4][2];  // [m block][n block][row tile][col tile]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    bf16x8 fa[2][2][4];  // [m block][ks][row tile]
+    bf16x8 fb[2][2][2];  // [n block][ks][col tile]
+    if constexpr (ABL & 2) {  // fragments must still hold something defined
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) fa[a][k][i] = bf16x8{1, 2, 3, 4, 5, 6, 7, 8};
+#pragma unroll
+                for (int j = 0; j < 2; ++j) fb[a][k][j] = bf16x8{8, 7, 6, 5, 4, 3, 2, 1};
+            }
+    }
+    // OP 2 keeps a tile's two 16-byte fragments in ONE 8-register vector (the operand of the block-scaled MFMA), so no
+    // register copies are needed to form it; the peeled bf16 tile takes its halves
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x8 __attribute__((ext_vector_type(8)));
+    i32x8 fa8[OP == 2 ? 2 : 1][OP == 2 ? 4 : 1];
+    i32x8 fb8[OP == 2 ? 2 : 1][OP == 2 ? 2 : 1];
+    auto readA = [&](const char* base, int mi) {
+        if constexpr (ABL & 2) return;
+        if constexpr (OP == 2) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(base + (a_off + (64 * mi + 16 * i) * ROW_BYTES));
+                const i32x4 hi = *reinterpret_cast<const i32x4*>(base + ((a_off ^ 64) + (64 * mi + 16 * i) * ROW_BYTES));
+                fa8[mi][i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    fa[mi][ks][i] = *reinterpret_cast<const bf16x8*>(base + ((a_off ^ (ks << 6)) + (64 * mi + 16 * i) * ROW_BYTES));
+        }
+    };
+    auto readB = [&](const char* base, int ni) {
+        if constexpr (ABL & 2) return;
+        if constexpr (OP == 2) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(base + (b_off + (32 * ni + 16 * j) * ROW_BYTES));
+                const i32x4 hi = *reinterpret_cast<const i32x4*>(base + ((b_off ^ 64) + (32 * ni + 16 * j) * ROW_BYTES));
+                fb8[ni][j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    fb[ni][ks][j] = *reinterpret_cast<const bf16x8*>(base + ((b_off ^ (ks << 6)) + (32 * ni + 16 * j) * ROW_BYTES));
+        }
+    };
+    // BF16TILE (compile-time tag): 16-bit MFMAs -- always for OP 0 / 3, for the peeled bf16 K-augmentation tile of the fp8 builds
+    auto mma = [&](int mi, int ni, auto bf16_tag = std::true_type{}) {
+        if constexpr (ABL & 1) return;
+        constexpr bool BF16TILE = !FP8 || decltype(bf16_tag)::value;
+        __builtin_amdgcn_s_setprio(1);
+        if constexpr (BF16TILE && OP == 2) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const i32x8 a = fa8[mi][i], b = fb8[ni][j];
+                    acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        __builtin_bit_cast(bf16x8, __builtin_shufflevector(b, b, 0, 1, 2, 3)),
+                        __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, a, 0, 1, 2, 3)), acc[mi][ni][i][j], 0, 0, 0);
+                    acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        __builtin_bit_cast(bf16x8, __builtin_shufflevector(b, b, 4, 5, 6, 7)),
+                        __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, a, 4, 5, 6, 7)), acc[mi][ni][i][j], 0, 0, 0);
+                }
+        } else if constexpr (BF16TILE) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[mi][ni][i][j] = mfma16x16x32<F16>(fb[ni][ks][j], fa[mi][ks][i], acc[mi][ni][i][j]);
+        } else if constexpr (OP == 1) {
+            typedef long i64x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const i64x2 a2 = __builtin_bit_cast(i64x2, fa[mi][ks][i]), b2 = __builtin_bit_cast(i64x2, fb[ni][ks][j]);
+                        acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[0], a2[0], acc[mi][ni][i][j], 0, 0, 0);
+                        acc[mi][ni][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[1], a2[1], acc[mi][ni][i][j], 0, 0, 0);
+                    }
+        } else if constexpr (OP == 2) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    // cbsz = blgp = 0: both operands OCP e4m3; block scales 2^(127-127) = 1 for every 32-element block
+                    acc[mi][ni][i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[ni][j], fa8[mi][i], acc[mi][ni][i][j], 0, 0,
+                                                                                         0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+        }
+        __builtin_amdgcn_s_setprio(0);
+    };
+    // GEMM_BARRIER (gemm.hip) with the ablation bit
+#define PP_BARRIER()                                           \
+    do {                                                       \
+        __builtin_amdgcn_sched_barrier(0);                     \
+        if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier(); \
+        __builtin_amdgcn_sched_barrier(0);                     \
+    } while (0)
+
+    auto stamp = [&](int i) {
+        if constexpr (DIAG) {
+            if (lane == 0 && wc == 0) e.diag[(size_t)blockIdx.x * 16 + g * 8 + i] = wall_clock64();
+        }
+    };
+    stamp(0);
+    const int nk = nk_main + (aug ? 1 : 0);
+#ifdef BSCLIP_DIAG
+    if constexpr (SCHED == 1) {
+        // Deep-prefetch variant, kept for comparison (bsclip_gemm_set_tile(6)); NOT the default.  tools/gemm_ablate.py shows the
+        // K loop bound as much by the LDS-DMA stream as by the matrix pipe (DMA + barriers alone 1.1 us per K-tile, MFMA +
+        // barriers alone 1.0, both 1.45).  If the DMA side were latency x bytes in flight, refilling a set with tile t+2 as
+        // soon as tile t has been read out of it -- A after phase 1, B after phase 2, ~100 KB per CU in flight instead of ~40 --
+        // would fix it.  It does not: DMA + barriers alone stay at 1.05 us per K-tile (a throughput limit of the L2 -> LDS path,
+        // ~61 GB/s per CU) and the full loop gets slower (1.56 us), so the one-tile-ahead schedule below remains in use.
+        // WAR: group 1 runs one barrier instant behind group 0.  A[set] is last read in phase 1; group 1's reads are waited for
+        //      before its mma(1,0), i.e. before global instant b4 (the barrier group 0 passes after its phase-2 reads), and A
+        //      DMAs are issued after that barrier (group 1: after its own, one instant later).  B[set] is last read in phase 2,
+        //      complete by b6; B DMAs are issued after the phase-3 barrier.
+        // RAW: before the phase-3 barrier every wave waits until only its 4 newest DMA instructions (A of tile t+2) are
+        //      outstanding: VMEM returns in order, so all its pieces of tile t+1 have landed; tile t+1 is first read after at
+        //      least one more barrier by either group.
+        dmaA(0, 0, 0);
+        dmaA(0, 1, 0);
+        dmaB(0, 0, 0);
+        dmaB(0, 1, 0);
+        if (nk > 1) {
+            dmaA(1, 0, 2 * BK);
+            dmaA(1, 1, 2 * BK);
+            dmaB(1, 0, 2 * BK);
+            dmaB(1, 1, 2 * BK);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        PP_BARRIER();
+        if (g == 1) PP_BARRIER();  // group 1 runs one barrier behind group 0 from here on
+        stamp(1);
+        for (int t = 0; t < nk; ++t) {
+            const int set = t & 1;
+            const char* base = smem + set * SET;
+            const bool has2 = t + 2 < nk;
+            const int k2 = (t + 2) * 2 * BK;
+            // ---- phase 0 ----
+            readA(base, 0);
+            readB(base, 0);
+            PP_BARRIER();
+            mma(0, 0, std::true_type{});
+            PP_BARRIER();
+            // ---- phase 1 ----
+            readA(base, 1);
+            PP_BARRIER();
+            mma(1, 0, std::true_type{});
+            PP_BARRIER();
+            // ---- phase 2 ----
+            readB(base, 1);
+            PP_BARRIER();
+            if (has2) {
+                dmaA(set, 0, k2);
+                dmaA(set, 1, k2);
+            }
+            mma(1, 1, std::true_type{});
+            PP_BARRIER();
+            // ---- phase 3 ----
+            if (has2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // tile t+1 complete; A of tile t+2 may fly
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            PP_BARRIER();
+            if (has2) {
+                dmaB(set, 0, k2);
+                dmaB(set, 1, k2);
+            }
+            mma(0, 1, std::true_type{});
+            PP_BARRIER();
+        }
+    } else if constexpr (SCHED == 2) {
+        // Four barriers per K-tile ("half-barrier ping-pong", experimental: bsclip_gemm_set_tile(7)).  One s_barrier per phase,
+        // call it b(t,p); group 0 runs   reads(p) | b(t,p) | mma(p)   and group 1 runs   b(t,p) | reads(p), mma(p),   so between
+        // two barriers group 0 does [mma(p), reads(p+1)] while group 1 does [reads(p), mma(p)]: matrix beside LDS in each half.
+        // Reads of tile t: A blocks in phases 0 and 1, B blocks in phases 0 and 2.  Group 0 issues reads(p) before b(t,p) and
+        // waits for them after it; group 1 issues and waits between b(t,p) and b(t,p+1).  Hence every read of A[set(t)] is
+        // complete before b(t,2) and every read of B[set(t)] before b(t,3).
+        // WAR: A[set(t)] may be refilled (tile t+2) after b(t,2), B[set(t)] after b(t,3).
+        // RAW: group 0 reads tile t+1 between b(t,3) and b(t+1,0), so every wave waits for its own pieces of tile t+1 BEFORE
+        //      it calls b(t,3).  Group 0's code before b(t,3) is its phase-3 slot (as in the classic schedule); group 1's is the
+        //      end of its phase 2, so group 1 issues its pieces one phase earlier than group 0:
+        //        group 0, tile t:  ph0 A-half1(t+1)  ph1 B-half0(t+1)  ph2 B-half1(t+1)  ph3 A-half0(t+2), wait vmcnt(2)
+        //        group 1, tile t:  ph0 B-half0(t+1)  ph1 B-half1(t+1)  ph2 wait vmcnt(0)  ph3 A-half0(t+2), A-half1(t+2)
+        //      (group 1's phase-3 code runs after b(t,3) > b(t,2): A[set(t)] is free; its B pieces go out after b(t,0), b(t,1),
+        //      both later than b(t-1,3)).
+        dmaA(0, 0, 0);
+        dmaA(0, 1, 0);
+        dmaB(0, 0, 0);
+        dmaB(0, 1, 0);
+        if (nk > 1) {
+            dmaA(1, 0, 2 * BK);
+            if (g == 1) {
+                dmaA(1, 1, 2 * BK);
+                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            }
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        PP_BARRIER();  // tile 0 published
+        stamp(1);
+        // one code body for both groups (two copies of the loop spilled: 308 B of scratch per lane); only the barrier position
+        // and the DMA piece of each phase depend on the group
+#define BAR_G0() do { if (g == 0) PP_BARRIER(); } while (0)
+#define BAR_G1() do { if (g == 1) PP_BARRIER(); } while (0)
+        for (int t = 0; t < nk; ++t) {
+            const int set = t & 1;
+            const char* base = smem + set * SET;
+            const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
+            const int k1 = (t + 1) * 2 * BK, k2 = (t + 2) * 2 * BK;
+            // ---- phase 0 ----
+            BAR_G1();
+            if (has1) {
+                if (g == 0) dmaA(set ^ 1, 1, k1);
+                else dmaB(set ^ 1, 0, k1);
+            }
+            readA(base, 0);
+            readB(base, 0);
+            BAR_G0();
+            mma(0, 0, std::true_type{});
+            // ---- phase 1 ----
+            BAR_G1();
+            if (has1) {
+                if (g == 0) dmaB(set ^ 1, 0, k1);
+                else dmaB(set ^ 1, 1, k1);
+            }
+            readA(base, 1);
+            BAR_G0();
+            mma(1, 0, std::true_type{});
+            // ---- phase 2 ----
+            BAR_G1();
+            if (has1 && g == 0) dmaB(set ^ 1, 1, k1);
+            readB(base, 1);
+            BAR_G0();
+            mma(1, 1, std::true_type{});
+            // ---- phase 3 ----
+            if (g == 0) {
+                if (has2) {
+                    dmaA(set, 0, k2);
+                    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // tile t+1 landed; A-half0(t+2) may fly
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tile t+1 have landed
+            }
+            PP_BARRIER();  // b(t,3): the one barrier both groups call at the same point of their code
+            if (g == 1 && has2) {
+                dmaA(set, 0, k2);
+                dmaA(set, 1, k2);
+            }
+            mma(0, 1, std::true_type{});
+        }
+#undef BAR_G0
+#undef BAR_G1
+    } else
+#endif
+    {
+        // ---- prologue: tile 0 complete, plus the first piece of tile 1 (the "phase 3 of tile -1" slot) ----
+        dmaA(0, 0, 0);
+        dmaA(0, 1, 0);
+        dmaB(0, 0, 0);
+        dmaB(0, 1, 0);
+        if (nk > 1) {
+            dmaA(1, 0, 2 * BK);
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        PP_BARRIER();
+        if (g == 1) PP_BARRIER();  // group 1 runs one barrier behind group 0 from here on
+        stamp(1);
+
+        auto k_tile = [&](int t, auto tag) {
+            const int set = t & 1;
+            const char* base = smem + set * SET;
+            const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
+            const int k1 = (t + 1) * 2 * BK, k2 = (t + 2) * 2 * BK;   // byte offsets of K-tiles t+1, t+2
+            // ---- phase 0 ----
+            if (has1) dmaA(set ^ 1, 1, k1);
+            readA(base, 0);
+            readB(base, 0);
+            PP_BARRIER();
+            mma(0, 0, tag);
+            PP_BARRIER();
+            // ---- phase 1 ----
+            if (has1) dmaB(set ^ 1, 0, k1);
+            readA(base, 1);
+            PP_BARRIER();
+            mma(1, 0, tag);
+            PP_BARRIER();
+            // ---- phase 2 ----
+            if (has1) dmaB(set ^ 1, 1, k1);
+            readB(base, 1);
+            PP_BARRIER();
+            mma(1, 1, tag);
+            PP_BARRIER();
+            // ---- phase 3 ----
+            if (has2) {
+                dmaA(set, 0, k2);
+                asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // everything of tile t+1 has landed; A-half0(t+2) may fly
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            PP_BARRIER();
+            mma(0, 1, tag);
+            PP_BARRIER();
+        };
+        if constexpr (!FP8) {
+            for (int t = 0; t < nk; ++t) k_tile(t, std::true_type{});
+        } else {  // fp8 tiles, then the peeled bf16 K-augmentation tile (same schedule, bf16 MFMAs)
+            for (int t = 0; t < nk_main; ++t) k_tile(t, std::false_type{});
+            if (aug) k_tile(nk_main, std::true_type{});
+        }
+    }
+    if constexpr (SCHED != 2) {
+        if (g == 0) PP_BARRIER();  // balance group 1's extra barrier
+    }
+#undef PP_BARRIER
+    stamp(2);
+
+    // ---- epilogue ----
+    f32x4 bias[2][2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            bias[ni][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (HAS_BIAS)
+                bias[ni][j] = *reinterpret_cast<const f32x4*>(e.bias + n0 + 64 * wc + 32 * ni + 16 * j + fq * 4);
+        }
+    if constexpr (FP8) {  // dequantise: alpha[n] = activation scale x weight-row scale
+        f32x4 al[2][2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                al[ni][j] = *reinterpret_cast<const f32x4*>(e.alpha + n0 + 64 * wc + 32 * ni + 16 * j + fq * 4);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[mi][ni][i][j] *= al[ni][j];
+    }
+    if constexpr (HAS_BIAS) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[mi][ni][i][j] += bias[ni][j];
+    }
+    // ---- fused InfoNCE, pass 1: the logits tile never leaves the accumulators --------------------------------------
+    // Per output row the tile's 256 columns live in 4 waves (wc) x 4 lanes (fq) x 16 registers: in-lane reduction, two xor
+    // shuffles (16, 32) across the lanes that share a row, LDS across the four waves.  Written per (row, column tile):
+    // (max, sum exp(x - max), sum over same-label columns of x); infonce_combine_kernel merges the column tiles.
+    if constexpr (EPI == EPI_LSE_PART) {
+        __syncthreads();  // every wave is past its last fragment read: the staging LDS is free
+        float* red = reinterpret_cast<float*>(smem);  // [256 rows][4 waves][4]
+        long lcol[2][2][4];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
+                    lcol[ni][j][c] = n < e.n_valid ? (long)e.labels[n] : (long)0x7fffffffffffffffLL;
+                }
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = 128 * g + 64 * mi + 16 * i + fr;
+                const int grow = e.row_base + min(m0 + r, M - 1);
+                const long li = (long)e.labels[min(grow, e.n_valid - 1)];
+                float x[16];
+                float mx = -INFINITY;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
+                            const float v = n < e.n_valid ? acc[mi][ni][i][j][c] * e.logit_scale : -INFINITY;
+                            x[(ni * 2 + j) * 4 + c] = v;
+                            mx = fmaxf(mx, v);
+                        }
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                float se = 0.f, dot = 0.f;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const float v = x[(ni * 2 + j) * 4 + c];
+                            se += mx == -INFINITY ? 0.f : __expf(v - mx);
+                            dot += lcol[ni][j][c] == li ? v : 0.f;
+                        }
+                se += __shfl_xor(se, 16, 64);
+                se += __shfl_xor(se, 32, 64);
+                dot += __shfl_xor(dot, 16, 64);
+                dot += __shfl_xor(dot, 32, 64);
+                if (fq == 0) *reinterpret_cast<f32x4*>(red + (r * 4 + wc) * 4) = f32x4{mx, se, dot, 0.f};
+            }
+        __syncthreads();
+        if (tid < 256 && m0 + tid < M) {
+            float mm = -INFINITY, ss = 0.f, dd = 0.f;
+            f32x4 p[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                p[w] = *reinterpret_cast<const f32x4*>(red + (tid * 4 + w) * 4);
+                mm = fmaxf(mm, p[w][0]);
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                ss += p[w][0] == -INFINITY ? 0.f : p[w][1] * __expf(p[w][0] - mm);
+                dd += p[w][2];
+            }
+            *reinterpret_cast<f32x4*>(e.part + ((size_t)(m0 + tid) * tiles_n + tile_n) * 4) = f32x4{mm, ss, dd, 0.f};
+        }
+        return;
+    }
+    // ---- fused InfoNCE, pass 2: dLoss/dG of the tile, straight from the accumulators, in split-bf16 form --------------
+    // w_ij = coef (cnt_i exp(x - lse_ab[i]) + cnt_j exp(x - lse_ba[j]) - 2 T_ij) for j < n_valid, else 0; written as the
+    // operand [hi | hi | lo] of the gradient GEMM (C bf16 [M, ldc = 3 * Np]) -- the logits themselves are never stored.
+    if constexpr (EPI == EPI_LOSS_W) {
+        constexpr int SBW = 528;
+        __syncthreads();
+        char* slab_hi = smem + g * (64 * SBW);
+        char* slab_lo = smem + 2 * 64 * SBW + g * (64 * SBW);
+        long lcol[2][2][4];
+        float ccol[2][2][4], lcolse[2][2][4];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
+                    const bool ok = n < e.n_valid;
+                    lcol[ni][j][c] = ok ? (long)e.labels[n] : (long)0x7fffffffffffffffLL;
+                    ccol[ni][j][c] = ok ? e.cnt[n] : 0.f;
+                    lcolse[ni][j][c] = ok ? e.lse_col[n] : 0.f;
+                }
+        const int np = ldc / 3;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = 128 * g + 64 * mi + 16 * i + fr;
+                const int grow = min(e.row_base + min(m0 + r, M - 1), e.n_valid - 1);
+                const long li = (long)e.labels[grow];
+                const float ci = e.cnt[grow], lr = e.lse_row[grow];
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        float wv[4], hi[4];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
+                            const float xv = acc[mi][ni][i][j][c] * e.logit_scale;
+                            const float t = lcol[ni][j][c] == li ? 2.0f : 0.0f;
+                            wv[c] = n < e.n_valid ? e.coef * (ci * __expf(xv - lr) + ccol[ni][j][c] * __expf(xv - lcolse[ni][j][c]) - t) : 0.f;
+                            hi[c] = bf2f(f2bf(wv[c]));
+                        }
+                        const int off = (16 * i + fr) * SBW + (64 * wc + 32 * ni + 16 * j + 4 * fq) * 2;
+                        *reinterpret_cast<uint2*>(slab_hi + off) = uint2{pack_bf2(wv[0], wv[1]), pack_bf2(wv[2], wv[3])};
+                        *reinterpret_cast<uint2*>(slab_lo + off) =
+                            uint2{pack_bf2(wv[0] - hi[0], wv[1] - hi[1]), pack_bf2(wv[2] - hi[2], wv[3] - hi[3])};
+                    }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < 8; ++it) {
+                const int r = it * 8 + (wave & 3) * 2 + (lane >> 5);
+                const int m = m0 + 128 * g + 64 * mi + r;
+                const uint4 vh = *reinterpret_cast<const uint4*>(slab_hi + r * SBW + (lane & 31) * 16);
+                const uint4 vl = *reinterpret_cast<const uint4*>(slab_lo + r * SBW + (lane & 31) * 16);
+                if (m < M) {
+                    bf16_t* dst = static_cast<bf16_t*>(C) + (size_t)m * ldc + n0 + (lane & 31) * 8;
+                    *reinterpret_cast<uint4*>(dst) = vh;
+                    *reinterpret_cast<uint4*>(dst + np) = vh;
+                    *reinterpret_cast<uint4*>(dst + 2 * np) = vl;
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    // ---- LDS-staged, row-coalesced stores --------------------------------------------------------------------
+    // In the accumulator layout a lane owns 4 consecutive columns of 16 different rows, so direct stores are 8-B
+    // (bf16) pieces of 32-B row segments: 64-128 store instructions per lane, store-ISSUE bound (the epilogue cost
+    // more than the 12-tile K loop of the K=768 GEMMs).  The main-loop LDS is free now: each group stages a 64-row
+    // slab of its output, then its 256 threads walk the slab row-wise with 16 B per lane, so every global access
+    // (C, residual, saved pre-activation) is a full 512-B / 1-KiB row segment.
+    constexpr int SB = 528;   // bf16 slab row stride (256*2 + 16)
+    constexpr int SF = 1040;  // f32 slab row stride (256*4 + 16)
+    char* slab = smem + g * (64 * SF);
+    const int wq = wave & 3;
+    __syncthreads();  // every wave is past its last fragment read
+    const char* lut = smem + 4 * 64 * SB;
+    constexpr bool GELU = EPI == BSCLIP_EPI_GELU_BF16 || EPI == BSCLIP_EPI_GELU_FP8;
+    if constexpr (GELU) {  // 16 KiB table, L2-resident, behind the slabs
+        for (int i = tid; i <= GELU_LUT_N; i += 512)
+            *reinterpret_cast<float2*>(smem + 4 * 64 * SB + i * 8) = g_gelu_lut[i];
+        BSCLIP_LDS_BARRIER();
+    }
+    constexpr int S8 = 272;   // 8-bit slab row stride (256 + 16)
+    char* slab2 = smem + 2 * 64 * SB + g * (64 * S8);  // second slab (GELU: gelu' side band, 8-bit codes)
+    auto stage_bf16 = [&](int mi) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const f32x4 v = acc[mi][ni][i][j];
+                    const int off = (16 * i + fr) * SB + (64 * wc + 32 * ni + 16 * j + 4 * fq) * 2;
+                    uint2 o;
+                    if constexpr (GELU) {
+                        f32x2 gl0, dg0, gl1, dg1;
+                        gelu_lut2(lut, f32x2{v[0], v[1]}, gl0, dg0);
+                        gelu_lut2(lut, f32x2{v[2], v[3]}, gl1, dg1);
+                        *reinterpret_cast<unsigned*>(slab2 + (16 * i + fr) * S8 + (64 * wc + 32 * ni + 16 * j + 4 * fq)) =
+                            dg8_pack4(dg0, dg1);
+                        if constexpr (EPI == BSCLIP_EPI_GELU_FP8) {  // the next GEMM's fp8 operand: e4m3, scale 1, saturated
+                            // The saturation is taken on the pre-activation x: gelu(x) <= x (x cdf, cdf <= 1), so x >= 448 -> 448 is the
+                            // upper bound, +inf included (whose table arithmetic is inf - inf); a NaN x fails the comparison and
+                            // keeps its NaN gelu, which converts to the NaN code.  No lower bound is needed: gelu >= -0.17 down to
+                            // x ~ -7e17, where x Phi(-8) itself passes -448 (and -inf is inf - inf = NaN: it shows as the NaN code).
+                            auto sat = [](float x, float gl) { return x >= 448.0f ? 448.0f : gl; };
+                            *reinterpret_cast<unsigned*>((g ? smem + 64 * SB : smem) + (16 * i + fr) * S8 +
+                                                         (64 * wc + 32 * ni + 16 * j + 4 * fq)) =
+                                cvt_fp8x4(sat(v[0], gl0[0]), sat(v[1], gl0[1]), sat(v[2], gl1[0]), sat(v[3], gl1[1]));
+                            continue;
+                        }
+                        o.x = pack_h2<F16>(gl0[0], gl0[1]);
+                        o.y = pack_h2<F16>(gl1[0], gl1[1]);
+                    } else {
+                        o.x = pack_h2<F16>(v[0], v[1]);
+                        o.y = pack_h2<F16>(v[2], v[3]);
+                    }
+                    *reinterpret_cast<uint2*>((g ? smem + 64 * SB : smem) + off) = o;
+                }
+    };
+    auto rows_bf16 = [&](int mi, const char* src, bf16_t* dst, int ld) {
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int r = it * 8 + wq * 2 + (lane >> 5);
+            const int m = m0 + 128 * g + 64 * mi + r;
+            const uint4 v = *reinterpret_cast<const uint4*>(src + r * SB + (lane & 31) * 16);
+            if (m < M) nt_store(dst + (size_t)m * ld + n0 + (lane & 31) * 8, v);
+        }
+    };
+    // 64 x 256 B slab of 8-bit codes: 16 lanes x 16 B per row, 16 rows per pass of the group's 256 threads
+    auto rows_u8 = [&](int mi, const char* src, unsigned char* dst, int ld) {
+        const int t = tid & 255;
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int r = it * 16 + (t >> 4);
+            const int m = m0 + 128 * g + 64 * mi + r;
+            const uint4 v = *reinterpret_cast<const uint4*>(src + r * S8 + (t & 15) * 16);
+            if (m < M) nt_store(dst + (size_t)m * ld + n0 + (t & 15) * 16, v);
+        }
+    };
+    auto stage_f32 = [&](int mi) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    *reinterpret_cast<f32x4*>(slab + (16 * i + fr) * SF + (64 * wc + 32 * ni + 16 * j + 4 * fq) * 4) =
+                        acc[mi][ni][i][j];
+    };
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        if constexpr (EPI == BSCLIP_EPI_BF16 || GELU) {
+            stage_bf16(mi);
+            BSCLIP_LDS_BARRIER();
+            stamp(4 + 2 * mi);
+            if constexpr (EPI == BSCLIP_EPI_GELU_FP8) rows_u8(mi, smem + g * (64 * SB), static_cast<unsigned char*>(C), ldc);
+            else rows_bf16(mi, smem + g * (64 * SB), static_cast<bf16_t*>(C), ldc);
+            if constexpr (GELU) {
+                if (e.aux) rows_u8(mi, slab2, e.aux, e.ld_aux);  // gelu'(pre-activation) for the backward pass
+            }
+            BSCLIP_LDS_BARRIER();
+            stamp(5 + 2 * mi);
+        }
+    }
+    if constexpr (!(EPI == BSCLIP_EPI_BF16 || GELU)) {
+        // f32-staged epilogues read a second operand (residual stream / saved gelu') row-wise.  Those loads do not
+        // depend on the accumulators, so they are issued one slab ahead -- before the staging barrier -- and have the
+        // whole LDS round trip to land (issued just-in-time they were 16 serial HBM round trips per wave: 26 us/tile).
+        f32x4 pre[2][16];
+        auto prefetch = [&](int mi, f32x4 (&R)[16]) {
+#pragma unroll
+            for (int it = 0; it < 16; ++it) {
+                const int m = min(m0 + 128 * g + 64 * mi + it * 4 + wq, M - 1);
+                R[it] = epi_cook<EPI, F16>(epi_fetch<EPI>(e, m, n0 + lane * 4));
+            }
+        };
+        auto st = [](auto* p, auto w) { nt_store(p, w); };
+        auto consume = [&](int mi, const f32x4 (&R)[16]) {
+#pragma unroll
+            for (int it = 0; it < 16; ++it) {
+                const int r = it * 4 + wq;  // one 1-KiB row per wave instruction
+                const int m = m0 + 128 * g + 64 * mi + r;
+                const int n = n0 + lane * 4;
+                f32x4 v = *reinterpret_cast<const f32x4*>(slab + r * SF + lane * 16);
+                if (m < M) {
+                    if constexpr (epi_is_resid(EPI)) {
+                        if (e.drop.thr16) v = drop4(e.drop, (unsigned)m * (unsigned)e.n_total + (unsigned)n, v);
+                    }
+                    epi_finish_store<EPI, F16, true>(v, R[it], m, n, C, ldc, st);
+                }
+            }
+        };
+        prefetch(0, pre[0]);
+        stage_f32(0);
+        BSCLIP_LDS_BARRIER();
+        stamp(4);
+        prefetch(1, pre[1]);
+        consume(0, pre[0]);
+        BSCLIP_LDS_BARRIER();
+        stamp(5);
+        stage_f32(1);
+        BSCLIP_LDS_BARRIER();
+        stamp(6);
+        consume(1, pre[1]);
+        stamp(7);
+    }
+    stamp(3);
+}
+
+// HB: the kernel adds e.bias.  F16 (fp16 operands, OP 3) has the production schedule only.
+template <int EPI, bool HB, bool F16, int SCHED = 0>
+void launch_pp(const bf16_t* A, int lda, const bf16_t* B, int ldb, void* C, int ldc, int M, int N, int K,
+               const EpiArgs& e, hipStream_t s) {
+    const int tiles_m = ceil_div(M, 256), tiles_n = N / 256;
+    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, HB, false, 0, F16 ? 0 : SCHED, F16 ? 3 : 0>), dim3(tiles_m * tiles_n), dim3(512), 0, s, A, lda, B,
+                       ldb, C, ldc, M, N, K, tiles_n, e);
+}
