@@ -68,12 +68,10 @@ extern "C" int bsclip_count_nonfinite(const void* x, int64_t n, int is_bf16, uin
                    "bsclip_count_nonfinite: bad arguments");
     long blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (is_bf16 & BSCLIP_OPERANDS_FP16)
-        hipLaunchKernelGGL(count_nonfinite_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long)n,
-                           1, counter_dev);
-    else
-        hipLaunchKernelGGL(count_nonfinite_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long)n,
-                           is_bf16, counter_dev);
+    pick_bool((is_bf16 & BSCLIP_OPERANDS_FP16) != 0, [&](auto fp) {
+        hipLaunchKernelGGL(count_nonfinite_kernel<decltype(fp)::value>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           x, (long)n, is_bf16 & 1, counter_dev);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -633,29 +633,24 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 2) void attn_bwd_kernel(const bf16_
 
 }  // namespace
 
-#define ATTN_FWD_LAUNCH(NBV, DR, TL, KBV)                                                                       \
-    hipLaunchKernelGGL((attn_fwd_kernel<NBV, DR, TL, false, KBV>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale, static_cast<bf16_t*>(ctx), ld_ctx, \
-                       lse, drop, nqb, static_cast<bf16_t*>(nullptr), static_cast<unsigned*>(keep_bits))
-#define ATTN_FWD_PICK(NBV, TL)                                                                                  \
-    do {                                                                                                        \
-        if (drop.thr16 && keep_bits) ATTN_FWD_LAUNCH(NBV, true, TL, true);                                      \
-        else if (drop.thr16) ATTN_FWD_LAUNCH(NBV, true, TL, false);                                             \
-        else ATTN_FWD_LAUNCH(NBV, false, TL, false);                                                            \
-    } while (0)
-#define ATTN_FWD_CASE(NBV)                                                                                      \
-    case NBV:                                                                                                   \
-        ATTN_FWD_PICK(NBV, 32);                                                                                 \
-        break;
-// fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the inference forms only -- no dropout, no keep bits (rejected on the host)
-#define ATTN_FWD16_LAUNCH(NBV, TL)                                                                              \
-    hipLaunchKernelGGL((attn_fwd_kernel<NBV, false, TL, false, false, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale, static_cast<bf16_t*>(ctx), ld_ctx, \
-                       lse, drop, nqb, static_cast<bf16_t*>(nullptr), static_cast<unsigned*>(nullptr))
-#define ATTN_FWD16_CASE(NBV)                                                                                    \
-    case NBV:                                                                                                   \
-        ATTN_FWD16_LAUNCH(NBV, 32);                                                                             \
-        break;
+// S -> (NB = key / query blocks of 32, TAIL = rows the instantiation knows its last tile to hold; 32 = any), shared by both directions.
+// The production sequence lengths get the instantiation that knows their last tile holds 5 rows (see tail_groups).  The backward takes
+// it at S = 133 only (TRIM197 = false): S = 133 gains 5 % from the trimmed last tile; at S = 197 the trimmed instantiation schedules
+// worse (268.6 vs 265.0 us).  f(NB tag, TAIL tag).
+template <bool TRIM197, class F>
+static void pick_attn_len(int S, F&& f) {
+    using five = std::integral_constant<int, 5>;
+    if constexpr (TRIM197)
+        if (S == 197) return f(std::integral_constant<int, 7>{}, five{});
+    if (S == 133) return f(five{}, five{});
+    pick_int<1, 2, 3, 4, 5, 6, 7>((S + 31) / 32, [&](auto nb) { f(nb, std::integral_constant<int, 32>{}); });
+}
+// the forward's forms.  fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the inference forms only -- no dropout, no keep bits (rejected
+// on the host)
+template <bool DR, bool KB, bool F16>
+struct AttnFwdForm {
+    static constexpr bool drop = DR, bits = KB, f16 = F16;
+};
 
 extern "C" int bsclip_attn_fwd(const void* qkv, int ld_qkv, int B, int S, int heads, const float* key_bias,
                                float scale, void* ctx, int ld_ctx, float* lse, int q_rows, void* keep_bits, float dropout_p,
@@ -664,7 +659,7 @@ extern "C" int bsclip_attn_fwd(const void* qkv, int ld_qkv, int B, int S, int he
     bool f16 = false;
     BSCLIP_REQUIRE(take_operands_flag(q_rows, f16), "bsclip_attn_fwd: unknown bits in q_rows=0x%x", q_rows);
     BSCLIP_REQUIRE(!f16 || (dropout_p == 0.f && !keep_bits), "bsclip_attn_fwd: fp16 operands take no dropout / keep_bits (inference only)");
-    BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(keep_bits) & 15) == 0, "bsclip_attn_fwd: keep_bits must be 16-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, keep_bits), "bsclip_attn_fwd: keep_bits must be 16-byte aligned");
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= 224, "bsclip_attn_fwd: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 8 == 0 && ld_ctx >= heads * 64 && ld_ctx % 4 == 0,
                    "bsclip_attn_fwd: ld_qkv=%d ld_ctx=%d", ld_qkv, ld_ctx);
@@ -673,43 +668,24 @@ extern "C" int bsclip_attn_fwd(const void* qkv, int ld_qkv, int B, int S, int he
     const int nqb = q_rows > 0 ? (q_rows + 31) / 32 : (S + 31) / 32;
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the production sequence lengths get the instantiation that knows their last tile holds 5 rows (see tail_groups)
-    if (f16) {
-        if (S == 197) {
-            ATTN_FWD16_LAUNCH(7, 5);
-        } else if (S == 133) {
-            ATTN_FWD16_LAUNCH(5, 5);
-        } else {
-            switch ((S + 31) / 32) {
-                ATTN_FWD16_CASE(1) ATTN_FWD16_CASE(2) ATTN_FWD16_CASE(3) ATTN_FWD16_CASE(4) ATTN_FWD16_CASE(5) ATTN_FWD16_CASE(6)
-                ATTN_FWD16_CASE(7)
-            }
-        }
-    } else if (S == 197) {
-        ATTN_FWD_PICK(7, 5);
-    } else if (S == 133) {
-        ATTN_FWD_PICK(5, 5);
-    } else {
-        switch ((S + 31) / 32) {
-            ATTN_FWD_CASE(1) ATTN_FWD_CASE(2) ATTN_FWD_CASE(3) ATTN_FWD_CASE(4) ATTN_FWD_CASE(5) ATTN_FWD_CASE(6)
-            ATTN_FWD_CASE(7)
-        }
-    }
+    auto pick_form = [&](auto&& f) {
+        if (f16) f(AttnFwdForm<false, false, true>{});
+        else if (drop.thr16 && keep_bits) f(AttnFwdForm<true, true, false>{});
+        else if (drop.thr16) f(AttnFwdForm<true, false, false>{});
+        else f(AttnFwdForm<false, false, false>{});
+    };
+    pick_form([&](auto form) { pick_attn_len<true>(S, [&](auto nb, auto tail) {
+        using Form = decltype(form);
+        hipLaunchKernelGGL((attn_fwd_kernel<decltype(nb)::value, Form::drop, decltype(tail)::value, false, Form::bits, Form::f16>),
+                           dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale,
+                           static_cast<bf16_t*>(ctx), ld_ctx, lse, drop, nqb, static_cast<bf16_t*>(nullptr),
+                           static_cast<unsigned*>(keep_bits));
+    }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
 
 #ifdef BSCLIP_DIAG   // experiment (round 4): only in libbsclip_hip_diag.so, like the backward it serves (attn_sweep.hip / attn_pers.hip)
-#define ATTN_FWD2_LAUNCH(NBV, DR, TL)                                                                           \
-    hipLaunchKernelGGL((attn_fwd_kernel<NBV, DR, TL, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s,       \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale, static_cast<bf16_t*>(ctx), ld_ctx, \
-                       stats, drop, nqb, static_cast<bf16_t*>(ctx_lo))
-#define ATTN_FWD2_CASE(NBV)                                                                                     \
-    case NBV:                                                                                                   \
-        if (drop.thr16) ATTN_FWD2_LAUNCH(NBV, true, 32);                                                        \
-        else ATTN_FWD2_LAUNCH(NBV, false, 32);                                                                  \
-        break;
-
 // Forward for the key-owner-sweep backward (bsclip_attn_bwd2): same attention, but instead of the log-sum-exp it leaves
 // stats[B, heads, S, 4] = (nm2, inv, rZ, 0) and the output to 16 mantissa bits (ctx = bf16(O), ctx_lo = bf16(O - ctx), both
 // with row stride ld_ctx) -- see attn_fwd_kernel's V2 note.
@@ -721,57 +697,30 @@ extern "C" int bsclip_attn_fwd2(const void* qkv, int ld_qkv, int B, int S, int h
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 8 == 0 && ld_ctx >= heads * 64 && ld_ctx % 4 == 0,
                    "bsclip_attn_fwd2: ld_qkv=%d ld_ctx=%d", ld_qkv, ld_ctx);
     BSCLIP_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "bsclip_attn_fwd2: dropout_p=%f", dropout_p);
-    BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 15) == 0, "bsclip_attn_fwd2: stats must be 16-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, stats), "bsclip_attn_fwd2: stats must be 16-byte aligned");
     const int nqb = (S + 31) / 32;
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (S == 197) {
-        if (drop.thr16) ATTN_FWD2_LAUNCH(7, true, 5);
-        else ATTN_FWD2_LAUNCH(7, false, 5);
-    } else if (S == 133) {
-        if (drop.thr16) ATTN_FWD2_LAUNCH(5, true, 5);
-        else ATTN_FWD2_LAUNCH(5, false, 5);
-    } else {
-        switch ((S + 31) / 32) {
-            ATTN_FWD2_CASE(1) ATTN_FWD2_CASE(2) ATTN_FWD2_CASE(3) ATTN_FWD2_CASE(4) ATTN_FWD2_CASE(5) ATTN_FWD2_CASE(6)
-            ATTN_FWD2_CASE(7)
-        }
-    }
+    pick_bool(drop.thr16 != 0, [&](auto dr) { pick_attn_len<true>(S, [&](auto nb, auto tail) {
+        hipLaunchKernelGGL((attn_fwd_kernel<decltype(nb)::value, decltype(dr)::value, decltype(tail)::value, true>), dim3(B * heads),
+                           dim3(ATT_WAVES * 64), 0, s, static_cast<const bf16_t*>(qkv), ld_qkv, S, heads, key_bias, scale,
+                           static_cast<bf16_t*>(ctx), ld_ctx, stats, drop, nqb, static_cast<bf16_t*>(ctx_lo));
+    }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
 #endif  // BSCLIP_DIAG
 
-#define ATTN_BWD_LAUNCH(NBV, DR, TL, BT, PR, LR)                                                                 \
-    hipLaunchKernelGGL((attn_bwd_kernel<NBV, DR, false, TL, BT, PR, LR>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_ctx, lse, S, heads, \
-                       key_bias, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, nqb, static_cast<unsigned long long*>(nullptr), \
-                       static_cast<const unsigned*>(keep_bits), lp)
-// dropout: from the forward's keep words when the caller has them, re-hashed otherwise; no dropout: delta preloaded (PRE).
-// The LoRA partial products ride on the two forms the engines run (keep words / preloaded delta).
-#define ATTN_BWD_PICK(NBV, TL)                                                                                   \
-    do {                                                                                                         \
-        if (lp.dtp && drop.thr16) ATTN_BWD_LAUNCH(NBV, true, TL, true, false, true);                             \
-        else if (lp.dtp) ATTN_BWD_LAUNCH(NBV, false, TL, false, true, true);                                     \
-        else if (drop.thr16 && keep_bits) ATTN_BWD_LAUNCH(NBV, true, TL, true, false, false);                    \
-        else if (drop.thr16) ATTN_BWD_LAUNCH(NBV, true, TL, false, false, false);                                \
-        else if (g_attn_preload) ATTN_BWD_LAUNCH(NBV, false, TL, false, true, false);                            \
-        else ATTN_BWD_LAUNCH(NBV, false, TL, false, false, false);                                               \
-    } while (0)
-#define ATTN_BWD_CASE(NBV)                                                                                       \
-    case NBV:                                                                                                    \
-        ATTN_BWD_PICK(NBV, 32);                                                                                  \
-        break;
+// The backward's forms.  Dropout: from the forward's keep words when the caller has them, re-hashed otherwise; no dropout: delta
+// preloaded (PRE).  The LoRA partial products ride on the two forms the engines run (keep words / preloaded delta).
+// fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the ViT's forms -- S = 197, no dropout, no keep bits (rejected on the host); the
+// key-owner phase with the preloaded delta, with or without the LoRA partial products.
+template <bool DR, bool BT, bool PR, bool LR>
+struct AttnBwdForm {
+    static constexpr bool drop = DR, bits = BT, pre = PR, lora = LR;
+};
 // A/B switch of the round-5 "row constant as the initial accumulator" form of the no-dropout key-owner phase (default on)
 static const bool g_attn_preload = !(getenv("BSCLIP_ATTN_PRELOAD") && atoi(getenv("BSCLIP_ATTN_PRELOAD")) == 0);
-
-// fp16 operands (q_rows | BSCLIP_OPERANDS_FP16): the ViT's forms -- S = 197, no dropout, no keep bits (rejected on the host); the key-owner
-// phase with the preloaded delta, with or without the LoRA partial products
-#define ATTN_BWD16_LAUNCH(PR, LR)                                                                                \
-    hipLaunchKernelGGL((attn_bwd_kernel<7, false, false, 32, false, PR, LR, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s, \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_ctx, lse, S, heads, \
-                       key_bias, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, nqb, static_cast<unsigned long long*>(nullptr), \
-                       static_cast<const unsigned*>(nullptr), lp)
 
 static int attn_bwd_launch(const void* qkv, int ld_qkv, const void* dctx, int ld_ctx, const float* lse, int B, int S, int heads,
                            const float* key_bias, float scale, void* dqkv, int ld_dqkv, int q_rows, const void* keep_bits,
@@ -781,7 +730,7 @@ static int attn_bwd_launch(const void* qkv, int ld_qkv, const void* dctx, int ld
     BSCLIP_REQUIRE(take_operands_flag(q_rows, f16), "bsclip_attn_bwd: unknown bits in q_rows=0x%x", q_rows);
     BSCLIP_REQUIRE(!f16 || (dropout_p == 0.f && !keep_bits), "bsclip_attn_bwd: fp16 operands take no dropout / keep_bits");
     BSCLIP_REQUIRE(!f16 || S == 197, "bsclip_attn_bwd: fp16 operands are built for S = 197 (the ViT), not S=%d", S);
-    BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(keep_bits) & 15) == 0, "bsclip_attn_bwd: keep_bits must be 16-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, keep_bits), "bsclip_attn_bwd: keep_bits must be 16-byte aligned");
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= 224, "bsclip_attn_bwd: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 8 == 0 && ld_dqkv >= 3 * heads * 64 && ld_dqkv % 4 == 0 &&
                        ld_ctx >= heads * 64 && ld_ctx % 8 == 0,
@@ -792,19 +741,24 @@ static int attn_bwd_launch(const void* qkv, int ld_qkv, const void* dctx, int ld
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     BSCLIP_REQUIRE(!lp.dtp || !drop.thr16 || keep_bits, "bsclip_attn_bwd_lora: with dropout the forward's keep_bits are required");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // S = 133 gains 5 % from the trimmed last tile; at S = 197 the trimmed instantiation schedules worse (268.6 vs 265.0 us)
-    if (f16) {
-        if (lp.dtp) ATTN_BWD16_LAUNCH(true, true);
-        else if (g_attn_preload) ATTN_BWD16_LAUNCH(true, false);
-        else ATTN_BWD16_LAUNCH(false, false);
-    } else if (S == 133) {
-        ATTN_BWD_PICK(5, 5);
-    } else {
-        switch ((S + 31) / 32) {
-            ATTN_BWD_CASE(1) ATTN_BWD_CASE(2) ATTN_BWD_CASE(3) ATTN_BWD_CASE(4) ATTN_BWD_CASE(5) ATTN_BWD_CASE(6)
-            ATTN_BWD_CASE(7)
-        }
-    }
+    auto pick_form = [&](auto&& f) {
+        if (lp.dtp && drop.thr16) f(AttnBwdForm<true, true, false, true>{});
+        else if (lp.dtp) f(AttnBwdForm<false, false, true, true>{});
+        else if (drop.thr16 && keep_bits) f(AttnBwdForm<true, true, false, false>{});
+        else if (drop.thr16) f(AttnBwdForm<true, false, false, false>{});
+        else if (g_attn_preload) f(AttnBwdForm<false, false, true, false>{});
+        else f(AttnBwdForm<false, false, false, false>{});
+    };
+    pick_bool(f16, [&](auto fp) { pick_form([&](auto form) { pick_attn_len<false>(S, [&](auto nb, auto tail) {
+        using Form = decltype(form);
+        constexpr int NB = decltype(nb)::value, TAIL = decltype(tail)::value;
+        constexpr bool F16 = decltype(fp)::value;
+        if constexpr (!F16 || (!Form::drop && NB == 7 && TAIL == 32))   // fp16: S = 197 without dropout, checked above
+            hipLaunchKernelGGL((attn_bwd_kernel<NB, Form::drop, false, TAIL, Form::bits, Form::pre, Form::lora, F16>), dim3(B * heads),
+                               dim3(ATT_WAVES * 64), 0, s, static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx),
+                               ld_ctx, lse, S, heads, key_bias, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, nqb,
+                               static_cast<unsigned long long*>(nullptr), static_cast<const unsigned*>(keep_bits), lp);
+    }); }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -823,8 +777,7 @@ extern "C" int bsclip_attn_bwd_lora(const void* qkv, int ld_qkv, const void* dct
                                     const void* keep_bits, const void* t_aug, int ld_t, const float* lora_b, float* dt_partial,
                                     float* db_partial, float dropout_p, uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(t_aug && lora_b && dt_partial && db_partial, "bsclip_attn_bwd_lora: null pointer");
-    BSCLIP_REQUIRE(ld_t >= 8 && ld_t % 8 == 0 && (reinterpret_cast<uintptr_t>(t_aug) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(dt_partial) & 15) == 0 && (reinterpret_cast<uintptr_t>(lora_b) & 3) == 0,
+    BSCLIP_REQUIRE(ld_t >= 8 && ld_t % 8 == 0 && aligned_to(16, t_aug, dt_partial) && aligned_to(4, lora_b),
                    "bsclip_attn_bwd_lora: t_aug / dt_partial must be 16-byte aligned, ld_t=%d a multiple of 8", ld_t);
     return attn_bwd_launch(qkv, ld_qkv, dctx, ld_ctx, lse, B, S, heads, key_bias, scale, dqkv, ld_dqkv, q_rows, keep_bits, dropout_p,
                            dropout_seed, LoraPart{static_cast<const bf16_t*>(t_aug), ld_t, lora_b, dt_partial, db_partial}, stream);
@@ -840,14 +793,12 @@ extern "C" int bsclip_attn_bwd_diag(const void* qkv, int ld_qkv, const void* dct
     BSCLIP_REQUIRE(S == 197 || S == 133, "bsclip_attn_bwd_diag: S=%d (197 or 133)", S);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const DropCfg drop = make_drop(0.f, 0);
-    if (S == 197)
-        hipLaunchKernelGGL((attn_bwd_kernel<7, false, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s,
+    pick_int<7, 5>((S + 31) / 32, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        hipLaunchKernelGGL((attn_bwd_kernel<NB, false, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s,
                            static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_ctx, lse, S, heads,
-                           (const float*)nullptr, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, 7, diag);
-    else
-        hipLaunchKernelGGL((attn_bwd_kernel<5, false, true>), dim3(B * heads), dim3(ATT_WAVES * 64), 0, s,
-                           static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_ctx, lse, S, heads,
-                           (const float*)nullptr, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, 5, diag);
+                           (const float*)nullptr, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop, NB, diag);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

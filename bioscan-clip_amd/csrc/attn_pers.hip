@@ -443,11 +443,11 @@ __global__ __launch_bounds__((NB + 1) * 64) void attn_bwd_pers_kernel(
 
 }  // namespace
 
-#define ATTN_PERS_LAUNCH(NBV, SV, DR, RG)                                                                                   \
-    hipLaunchKernelGGL((attn_bwd_pers_kernel<NBV, SV, DR, RG>), dim3(grid), dim3((NBV + 1) * 64), 0, s,                      \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,                   \
-                       static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, heads, B * heads,  \
-                       scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop)
+// the two sequence lengths the persistent kernel is built for: NB = blocks of 32, RG as the kernel's note explains
+template <int SV>
+struct PersLen {
+    static constexpr int S = SV, NB = (SV + 31) / 32, RG = SV == 197 ? 2 : 4;
+};
 
 // internal (attn_sweep.hip dispatches here for S = 197 / 133 without a key mask); returns false when the shape is not covered
 bool bsclip_attn_bwd_pers_launch(const void* qkv, int ld_qkv, const void* dctx, int ld_dctx, const void* ctx, const void* ctx_lo,
@@ -461,17 +461,16 @@ bool bsclip_attn_bwd_pers_launch(const void* qkv, int ld_qkv, const void* dctx, 
         if (cus <= 0) cus = 256;
     }
     const int grid = B * heads < cus ? B * heads : cus;
-    if (S == 197) {
-        if (drop.thr16) return false;   // a fourth statistics array does not fit beside the tiles at S = 197 (timm's ViT has no attention dropout)
-        ATTN_PERS_LAUNCH(7, 197, false, 2);
-        return true;
-    }
-    if (S == 133) {
-        if (drop.thr16) ATTN_PERS_LAUNCH(5, 133, true, 4);
-        else ATTN_PERS_LAUNCH(5, 133, false, 4);
-        return true;
-    }
-    return false;
+    if (S == 197 && drop.thr16) return false;   // a fourth statistics array does not fit beside the tiles at S = 197 (timm's ViT has no attention dropout)
+    return pick_int<197, 133>(S, [&](auto sv) { pick_bool(drop.thr16 != 0, [&](auto dr) {
+        using L = PersLen<decltype(sv)::value>;
+        constexpr bool DR = decltype(dr)::value;
+        if constexpr (L::S != 197 || !DR)
+            hipLaunchKernelGGL((attn_bwd_pers_kernel<L::NB, L::S, DR, L::RG>), dim3(grid), dim3((L::NB + 1) * 64), 0, s,
+                               static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,
+                               static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, heads, B * heads, scale,
+                               static_cast<bf16_t*>(dqkv), ld_dqkv, drop);
+    }); });
 }
 
 #ifdef BSCLIP_DIAG
@@ -485,16 +484,13 @@ extern "C" int bsclip_attn_bwd_pers_diag(const void* qkv, int ld_qkv, const void
     hipStream_t s = static_cast<hipStream_t>(stream);
     const DropCfg drop = make_drop(0.f, 0);
     const int grid = B * heads < 256 ? B * heads : 256;
-    if (S == 197)
-        hipLaunchKernelGGL((attn_bwd_pers_kernel<7, 197, false, 2, true>), dim3(grid), dim3(512), 0, s, static_cast<const bf16_t*>(qkv),
-                           ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx, static_cast<const bf16_t*>(ctx),
-                           static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, heads, B * heads, scale, static_cast<bf16_t*>(dqkv), ld_dqkv,
-                           drop, diag);
-    else
-        hipLaunchKernelGGL((attn_bwd_pers_kernel<5, 133, false, 4, true>), dim3(grid), dim3(384), 0, s, static_cast<const bf16_t*>(qkv),
-                           ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx, static_cast<const bf16_t*>(ctx),
-                           static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, heads, B * heads, scale, static_cast<bf16_t*>(dqkv), ld_dqkv,
-                           drop, diag);
+    pick_int<197, 133>(S, [&](auto sv) {
+        using L = PersLen<decltype(sv)::value>;
+        hipLaunchKernelGGL((attn_bwd_pers_kernel<L::NB, L::S, false, L::RG, true>), dim3(grid), dim3((L::NB + 1) * 64), 0, s,
+                           static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,
+                           static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, heads, B * heads, scale,
+                           static_cast<bf16_t*>(dqkv), ld_dqkv, drop, diag);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

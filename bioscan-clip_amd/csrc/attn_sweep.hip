@@ -320,17 +320,6 @@ bool bsclip_attn_bwd_pers_launch(const void* qkv, int ld_qkv, const void* dctx, 
                                  const DropCfg& drop, hipStream_t s);
 static const bool g_attn_pers = !(getenv("BSCLIP_ATTN_PERS") && atoi(getenv("BSCLIP_ATTN_PERS")) == 0);   // A/B switch
 
-#define ATTN_SWEEP_LAUNCH(NBV, DR)                                                                                      \
-    hipLaunchKernelGGL((attn_bwd_sweep_kernel<NBV, DR>), dim3(B * heads), dim3((NBV + 1) * 64), 0, s,                    \
-                       static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,               \
-                       static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, S, heads,     \
-                       key_bias, scale, static_cast<bf16_t*>(dqkv), ld_dqkv, drop)
-#define ATTN_SWEEP_CASE(NBV)                              \
-    case NBV:                                             \
-        if (drop.thr16) ATTN_SWEEP_LAUNCH(NBV, true);     \
-        else ATTN_SWEEP_LAUNCH(NBV, false);               \
-        break;
-
 // Backward of bsclip_attn_fwd2 (same qkv, key_bias, scale, dropout arguments; ctx / ctx_lo / stats as that call left them):
 // dqkv[B*S, 3*heads*64] = (dQ | dK | dV).  Every query row receives a gradient (no q_rows form: the last ViT block, whose
 // gradient enters through token 0 only, stays on bsclip_attn_fwd / bsclip_attn_bwd).
@@ -343,7 +332,7 @@ extern "C" int bsclip_attn_bwd2(const void* qkv, int ld_qkv, const void* dctx, i
                        ld_dctx >= heads * 64 && ld_dctx % 8 == 0 && ld_ctx >= heads * 64 && ld_ctx % 8 == 0,
                    "bsclip_attn_bwd2: ld_qkv=%d ld_dqkv=%d ld_dctx=%d ld_ctx=%d", ld_qkv, ld_dqkv, ld_dctx, ld_ctx);
     BSCLIP_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "bsclip_attn_bwd2: dropout_p=%f", dropout_p);
-    BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 15) == 0, "bsclip_attn_bwd2: stats must be 16-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, stats), "bsclip_attn_bwd2: stats must be 16-byte aligned");
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (g_attn_pers && !key_bias &&
@@ -351,10 +340,13 @@ extern "C" int bsclip_attn_bwd2(const void* qkv, int ld_qkv, const void* dctx, i
         BSCLIP_LAUNCH_CHECK();
         return BSCLIP_OK;
     }
-    switch ((S + 31) / 32) {
-        ATTN_SWEEP_CASE(1) ATTN_SWEEP_CASE(2) ATTN_SWEEP_CASE(3) ATTN_SWEEP_CASE(4) ATTN_SWEEP_CASE(5) ATTN_SWEEP_CASE(6)
-        ATTN_SWEEP_CASE(7)
-    }
+    pick_int<1, 2, 3, 4, 5, 6, 7>((S + 31) / 32, [&](auto nb) { pick_bool(drop.thr16 != 0, [&](auto dr) {
+        constexpr int NB = decltype(nb)::value;
+        hipLaunchKernelGGL((attn_bwd_sweep_kernel<NB, decltype(dr)::value>), dim3(B * heads), dim3((NB + 1) * 64), 0, s,
+                           static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,
+                           static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, S, heads, key_bias, scale,
+                           static_cast<bf16_t*>(dqkv), ld_dqkv, drop);
+    }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -370,16 +362,13 @@ extern "C" int bsclip_attn_bwd2_diag(const void* qkv, int ld_qkv, const void* dc
     hipStream_t s = static_cast<hipStream_t>(stream);
     const DropCfg drop = make_drop(0.f, 0);
     const float* key_bias = nullptr;
-    if (S == 197)
-        hipLaunchKernelGGL((attn_bwd_sweep_kernel<7, false, true>), dim3(B * heads), dim3(8 * 64), 0, s, static_cast<const bf16_t*>(qkv),
-                           ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx, static_cast<const bf16_t*>(ctx),
-                           static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, S, heads, key_bias, scale, static_cast<bf16_t*>(dqkv),
-                           ld_dqkv, drop, diag);
-    else
-        hipLaunchKernelGGL((attn_bwd_sweep_kernel<5, false, true>), dim3(B * heads), dim3(6 * 64), 0, s, static_cast<const bf16_t*>(qkv),
-                           ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx, static_cast<const bf16_t*>(ctx),
-                           static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, S, heads, key_bias, scale, static_cast<bf16_t*>(dqkv),
-                           ld_dqkv, drop, diag);
+    pick_int<7, 5>((S + 31) / 32, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        hipLaunchKernelGGL((attn_bwd_sweep_kernel<NB, false, true>), dim3(B * heads), dim3((NB + 1) * 64), 0, s,
+                           static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<const bf16_t*>(dctx), ld_dctx,
+                           static_cast<const bf16_t*>(ctx), static_cast<const bf16_t*>(ctx_lo), ld_ctx, stats, S, heads, key_bias, scale,
+                           static_cast<bf16_t*>(dqkv), ld_dqkv, drop, diag);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

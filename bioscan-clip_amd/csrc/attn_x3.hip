@@ -380,38 +380,20 @@ __global__ __launch_bounds__(X3_WAVES * 64, 2) void attn_bwd_x3_kernel(const flo
 
 }  // namespace
 
-#define X3_FWD_CASE(NBV)                                                                                                        \
-    case NBV:                                                                                                                   \
-        if (drop.thr16)                                                                                                         \
-            hipLaunchKernelGGL((attn_fwd_x3_kernel<NBV, true>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv, ld_qkv, S, heads, key_bias, \
-                               scale, ctx, ld_ctx, lse, drop, ctx3, ld_c3);                                                     \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((attn_fwd_x3_kernel<NBV, false>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv, ld_qkv, S, heads, key_bias, \
-                               scale, ctx, ld_ctx, lse, drop, ctx3, ld_c3);                                                     \
-        break;
-
 // internal (called by exact.hip's bsclip_attn_fwd_f32 / bsclip_attn_bwd_f32 after their argument checks)
 void bsclip_launch_attn_fwd_x3(const float* qkv, int ld_qkv, int B, int S, int heads, const float* key_bias, float scale, float* ctx,
                                int ld_ctx, float* lse, const DropCfg& drop, bf16_t* ctx3, int ld_c3, hipStream_t s) {
-    switch ((S + 31) / 32) {
-        X3_FWD_CASE(1) X3_FWD_CASE(2) X3_FWD_CASE(3) X3_FWD_CASE(4) X3_FWD_CASE(5) X3_FWD_CASE(6) X3_FWD_CASE(7)
-    }
+    pick_int<1, 2, 3, 4, 5, 6, 7>((S + 31) / 32, [&](auto nb) { pick_bool(drop.thr16 != 0, [&](auto dr) {
+        hipLaunchKernelGGL((attn_fwd_x3_kernel<decltype(nb)::value, decltype(dr)::value>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv,
+                           ld_qkv, S, heads, key_bias, scale, ctx, ld_ctx, lse, drop, ctx3, ld_c3);
+    }); });
 }
-
-#define X3_BWD_CASE(NBV)                                                                                                        \
-    case NBV:                                                                                                                   \
-        if (drop.thr16)                                                                                                         \
-            hipLaunchKernelGGL((attn_bwd_x3_kernel<NBV, true>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, \
-                               ld_ctx, lse, S, heads, key_bias, scale, dqkv, ld_dqkv, drop, dqkv3, ld_d3);                      \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((attn_bwd_x3_kernel<NBV, false>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, \
-                               ld_ctx, lse, S, heads, key_bias, scale, dqkv, ld_dqkv, drop, dqkv3, ld_d3);                      \
-        break;
 
 void bsclip_launch_attn_bwd_x3(const float* qkv, int ld_qkv, const float* dctx, int ld_dctx, const float* ctx, int ld_ctx, const float* lse,
                                int B, int S, int heads, const float* key_bias, float scale, float* dqkv, int ld_dqkv, const DropCfg& drop,
                                bf16_t* dqkv3, int ld_d3, hipStream_t s) {
-    switch ((S + 31) / 32) {
-        X3_BWD_CASE(1) X3_BWD_CASE(2) X3_BWD_CASE(3) X3_BWD_CASE(4) X3_BWD_CASE(5) X3_BWD_CASE(6) X3_BWD_CASE(7)
-    }
+    pick_int<1, 2, 3, 4, 5, 6, 7>((S + 31) / 32, [&](auto nb) { pick_bool(drop.thr16 != 0, [&](auto dr) {
+        hipLaunchKernelGGL((attn_bwd_x3_kernel<decltype(nb)::value, decltype(dr)::value>), dim3(B * heads), dim3(X3_WAVES * 64), 0, s, qkv,
+                           ld_qkv, dctx, ld_dctx, ctx, ld_ctx, lse, S, heads, key_bias, scale, dqkv, ld_dqkv, drop, dqkv3, ld_d3);
+    }); });
 }

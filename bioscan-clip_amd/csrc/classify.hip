@@ -123,8 +123,7 @@ extern "C" int bsclip_ce_fwd_bwd(const float* logits, int ldc, const int32_t* ta
     BSCLIP_REQUIRE(!dlogits || (ld_d >= C && ld_d % 4 == 0), "bsclip_ce_fwd_bwd: ld_d=%d (>= C=%d, a multiple of 4)", ld_d, C);
     BSCLIP_REQUIRE(!dlogits_split3 || (ld_d3 >= 3 * Cp && ld_d3 % 4 == 0),
                    "bsclip_ce_fwd_bwd: ld_d3=%d (>= 3 x %d = C rounded up to 64, three times; a multiple of 4)", ld_d3, Cp);
-    BSCLIP_REQUIRE(((((uintptr_t)logits) | ((uintptr_t)dlogits)) & 15) == 0 && (((uintptr_t)dlogits_split3) & 7) == 0 &&
-                       ((((uintptr_t)targets) | ((uintptr_t)loss_out) | ((uintptr_t)row_loss) | ((uintptr_t)flag)) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, logits, dlogits) && aligned_to(8, dlogits_split3) && aligned_to(4, targets, loss_out, row_loss, flag),
                    "bsclip_ce_fwd_bwd: logits / dlogits must be 16-byte, dlogits_split3 8-byte, the other buffers 4-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(ce_rows_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, s, logits, ldc, targets, B, C, Cp, row_loss, dlogits, ld_d,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/bsclip.h"
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits in HBM
@@ -294,6 +296,29 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---- host: a run-time switch becomes a template argument.  f is a generic lambda called with a std::true_type / std::false_type /
+// std::integral_constant tag; callers nest these, read the value with decltype(tag)::value and write the launch once.  Combinations
+// that have no kernel are fenced off with `if constexpr` inside the lambda, so that nothing extra is instantiated. ----
+template <class F>
+inline void pick_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int... Vs, class F>
+inline bool pick_int(int v, F&& f) {   // false: v is none of Vs, f was not called
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// true if every pointer is a multiple of `align` bytes (a power of two)
+template <class... P>
+inline bool aligned_to(uintptr_t align, const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & (align - 1)) == 0;
+}
+// grid of the elementwise kernels that take four elements per thread in blocks of 256: ceil(n / 4 / 256) clamped to [1, max_blocks]
+static inline int grid4x256(size_t n, size_t max_blocks) {
+    const size_t blocks = (n / 4 + 255) / 256;
+    return (int)(blocks < 1 ? 1 : blocks > max_blocks ? max_blocks : blocks);
+}
 
 // fullft.hip, internal: out0 / out1 [c] += sum_b partial[b][c] in a fixed order (columns < split go to out0, the rest to out1)
 void bsclip_launch_slab_reduce_add(const float* partial, int nblocks, int n, float* out0, float* out1, int split, hipStream_t s);

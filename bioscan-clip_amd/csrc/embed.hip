@@ -231,23 +231,15 @@ extern "C" int bsclip_im2col_patch16(const float* image, int B, void* cols_bf16,
     BSCLIP_REQUIRE(image && cols_bf16 && B > 0, "bsclip_im2col_patch16: bad args");
     bool f16 = false;
     BSCLIP_REQUIRE(take_operands_flag(split, f16), "bsclip_im2col_patch16: unknown bits in split=0x%x", split);
-    BSCLIP_REQUIRE(ld_cols % 8 == 0 && ld_cols >= (split ? 2304 : 768) && (((uintptr_t)cols_bf16) & 15) == 0,
+    BSCLIP_REQUIRE(ld_cols % 8 == 0 && ld_cols >= (split ? 2304 : 768) && aligned_to(16, cols_bf16),
                    "bsclip_im2col_patch16: ld_cols=%d (>= %d, multiple of 8, 16-byte aligned rows)", ld_cols, split ? 2304 : 768);
     const long total = (long)B * 196 * 96;
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (f16 && split)
-        hipLaunchKernelGGL((im2col_patch16_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
-    else if (f16)
-        hipLaunchKernelGGL((im2col_patch16_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
-    else if (split)
-        hipLaunchKernelGGL((im2col_patch16_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
-    else
-        hipLaunchKernelGGL((im2col_patch16_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
+    pick_bool(split != 0, [&](auto sp) { pick_bool(f16, [&](auto fp) {
+        hipLaunchKernelGGL((im2col_patch16_kernel<decltype(sp)::value, decltype(fp)::value>), dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), image, B, static_cast<bf16_t*>(cols_bf16), ld_cols);
+    }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -258,15 +250,12 @@ extern "C" int bsclip_vit_cls_rows(void* x, int x_bf16, const float* cls_token, 
     bool f16 = false;
     BSCLIP_REQUIRE(take_operands_flag(x_bf16, f16), "bsclip_vit_cls_rows: unknown bits in x_bf16=0x%x", x_bf16);
     BSCLIP_REQUIRE(!f16 || x_bf16, "bsclip_vit_cls_rows: fp16 operands need the 16-bit stream (x_bf16)");
-    if (f16)
-        hipLaunchKernelGGL((vit_cls_rows_kernel<true, true>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           x, cls_token, pos_embed, B, S, H);
-    else if (x_bf16)
-        hipLaunchKernelGGL((vit_cls_rows_kernel<true>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           x, cls_token, pos_embed, B, S, H);
-    else
-        hipLaunchKernelGGL((vit_cls_rows_kernel<false>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           x, cls_token, pos_embed, B, S, H);
+    pick_bool(x_bf16 != 0, [&](auto xb) { pick_bool(f16, [&](auto fp) {
+        constexpr bool XB = decltype(xb)::value, F16 = decltype(fp)::value;
+        if constexpr (XB || !F16)   // fp16 operands need the 16-bit stream (checked above)
+            hipLaunchKernelGGL((vit_cls_rows_kernel<XB, F16>), dim3(ceil_div(B * H, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                               cls_token, pos_embed, B, S, H);
+    }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -283,7 +272,7 @@ extern "C" int bsclip_bert_embed(const int64_t* ids, const int64_t* type_ids, in
 }
 
 static bool transpose_aligned(const void* in, int ld_in, const void* out, int ld_out) {
-    return ld_in % 8 == 0 && ld_out % 8 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0;
+    return ld_in % 8 == 0 && ld_out % 8 == 0 && aligned_to(16, in, out);
 }
 
 extern "C" int bsclip_transpose_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, void* stream) {
@@ -317,10 +306,7 @@ extern "C" int bsclip_transpose_colsum_bf16(const void* in, int ld_in, int R, in
 
 extern "C" int bsclip_cast_f32_bf16(const float* in, int64_t n, void* out, void* stream) {
     BSCLIP_REQUIRE(in && out && n > 0, "bsclip_cast_f32_bf16: bad args");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
+    hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3(grid4x256(n, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                        (long)n, static_cast<bf16_t*>(out));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -329,10 +315,7 @@ extern "C" int bsclip_cast_f32_bf16(const float* in, int64_t n, void* out, void*
 // the fp16 form (no integer argument can carry BSCLIP_OPERANDS_FP16 here: n is a 64-bit count)
 extern "C" int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* stream) {
     BSCLIP_REQUIRE(in && out && n > 0, "bsclip_cast_f32_f16: bad args");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in,
+    hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3(grid4x256(n, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                        (long)n, static_cast<bf16_t*>(out));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -342,12 +325,9 @@ extern "C" int bsclip_cast_f32_f16(const float* in, int64_t n, void* out, void* 
 extern "C" int bsclip_cast_f32_f16_scaled(const float* in, int64_t n, int scale_log2, void* out, void* stream) {
     BSCLIP_REQUIRE(in && out && n > 0, "bsclip_cast_f32_f16_scaled: bad args");
     BSCLIP_REQUIRE(scale_log2 >= -64 && scale_log2 <= 64, "bsclip_cast_f32_f16_scaled: scale_log2=%d (|k| <= 64)", scale_log2);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, in, out),
                    "bsclip_cast_f32_f16_scaled: in and out must be 16-byte aligned");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cast_f32_f16_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
+    hipLaunchKernelGGL(cast_f32_f16_scaled_kernel, dim3(grid4x256(n, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
                        ldexpf(1.f, scale_log2), static_cast<bf16_t*>(out));
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -358,12 +338,10 @@ extern "C" int bsclip_waug_set_lora_layers(const int64_t* table_dev, int layers,
     BSCLIP_REQUIRE(take_operands_flag(layers, f16), "bsclip_waug_set_lora_layers: unknown bits in layers=0x%x (count < 256)", layers);
     BSCLIP_REQUIRE(table_dev && layers > 0 && ld_w >= H + BSCLIP_KPAD && ld_w % 4 == 0 && H % 4 == 0,
                    "bsclip_waug_set_lora_layers: bad args");
-    if (f16)
-        hipLaunchKernelGGL(waug_set_lora_layers_kernel<true>, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0,
+    pick_bool(f16, [&](auto fp) {
+        hipLaunchKernelGGL(waug_set_lora_layers_kernel<decltype(fp)::value>, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0,
                            static_cast<hipStream_t>(stream), table_dev, ld_w, H);
-    else
-        hipLaunchKernelGGL(waug_set_lora_layers_kernel<false>, dim3(ceil_div(2 * H, 256), layers), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), table_dev, ld_w, H);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -686,7 +686,7 @@ extern "C" int bsclip_exact_attn_set_impl(int impl) {
 
 extern "C" int bsclip_split3_rows(const float* src, int ld_src, int M, int K, void* dst, int ld_dst, void* stream) {
     BSCLIP_REQUIRE(src && dst, "bsclip_split3_rows: null pointer");
-    BSCLIP_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, src) && aligned_to(8, dst),
                    "bsclip_split3_rows: src must be 16-byte, dst 8-byte aligned");
     BSCLIP_REQUIRE(M > 0 && K > 0 && K % 4 == 0 && ld_src >= K && ld_src % 4 == 0 && ld_dst >= 3 * K && ld_dst % 4 == 0,
                    "bsclip_split3_rows: M=%d K=%d ld_src=%d ld_dst=%d", M, K, ld_src, ld_dst);
@@ -703,8 +703,7 @@ extern "C" int bsclip_split3_weight(const float* w, int ld_w, int N, int K, cons
     BSCLIP_REQUIRE((lora_a == nullptr) == (lora_b == nullptr), "bsclip_split3_weight: lora_a and lora_b go together");
     // the kernel reads w, lora_a and lora_b as f32x4 and writes dst as 8-byte words: views into a flat parameter buffer are aligned
     // only while every parameter's numel is a multiple of 4 -- a misaligned view must be an error code, not a GPU fault
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(lora_a) | reinterpret_cast<uintptr_t>(lora_b)) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(dst) & 7) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, w, lora_a, lora_b) && aligned_to(8, dst),
                    "bsclip_split3_weight: w / lora_a / lora_b must be 16-byte, dst 8-byte aligned");
     BSCLIP_REQUIRE(N > 0 && K > 0 && K % 4 == 0 && ld_w >= K && ld_w % 4 == 0 && ld_dst >= 3 * K && ld_dst % 4 == 0 &&
                        (lora_a == nullptr || (N == 3 * H && K == H)),
@@ -719,8 +718,7 @@ extern "C" int bsclip_split3_weight(const float* w, int ld_w, int N, int K, cons
 extern "C" int bsclip_gelu_split3(const float* z, int ld_z, int M, int N, void* dst, int ld_dst, void* codes, int ld_codes, float* g32,
                                   int ld_g32, void* stream) {
     BSCLIP_REQUIRE(z && (dst || g32), "bsclip_gelu_split3: null pointer");
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(g32)) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0 &&
-                       (reinterpret_cast<uintptr_t>(codes) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, z, g32) && aligned_to(8, dst) && aligned_to(4, codes),
                    "bsclip_gelu_split3: z / g32 must be 16-byte, dst 8-byte, codes 4-byte aligned");
     BSCLIP_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && ld_z >= N && ld_z % 4 == 0 && (dst == nullptr || (ld_dst >= 3 * N && ld_dst % 4 == 0)) &&
                        (codes == nullptr || (ld_codes >= N && ld_codes % 4 == 0)) && (g32 == nullptr || (ld_g32 >= N && ld_g32 % 4 == 0)),
@@ -749,12 +747,12 @@ static void split3_after(const float* src, int ld_src, int M, int K, void* dst, 
 extern "C" int bsclip_attn_fwd_f32(const float* qkv, int ld_qkv, int B, int S, int heads, const float* key_bias, float scale, float* ctx,
                                    int ld_ctx, float* lse, void* ctx_split3, int ld_c3, float dropout_p, uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(qkv && ctx && lse, "bsclip_attn_fwd_f32: null pointer");
-    BSCLIP_REQUIRE(!ctx_split3 || (ld_c3 >= 3 * heads * 64 && ld_c3 % 4 == 0 && (reinterpret_cast<uintptr_t>(ctx_split3) & 7) == 0),
+    BSCLIP_REQUIRE(!ctx_split3 || (ld_c3 >= 3 * heads * 64 && ld_c3 % 4 == 0 && aligned_to(8, ctx_split3)),
                    "bsclip_attn_fwd_f32: ctx_split3 bf16 [B S, ld_c3 >= 3 heads 64], 8-byte aligned (ld_c3=%d)", ld_c3);
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= AF_SMAX, "bsclip_attn_fwd_f32: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 4 == 0 && ld_ctx >= heads * 64 && ld_ctx % 4 == 0,
                    "bsclip_attn_fwd_f32: ld_qkv=%d ld_ctx=%d", ld_qkv, ld_ctx);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, qkv, ctx),
                    "bsclip_attn_fwd_f32: qkv and ctx must be 16-byte aligned (vector loads / stores)");
     BSCLIP_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "bsclip_attn_fwd_f32: dropout_p=%f", dropout_p);
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
@@ -764,23 +762,16 @@ extern "C" int bsclip_attn_fwd_f32(const float* qkv, int ld_qkv, int B, int S, i
         BSCLIP_LAUNCH_CHECK();
         return BSCLIP_OK;
     }
-    if (g_exact_attn_impl == 2) {   // f32 operands on the matrix pipe (round 4); impl 1 = the one-row-per-thread vector-ALU kernel
-        if (drop.thr16)
-            hipLaunchKernelGGL((attn_fwd_mf32_kernel<true>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale,
+    // impl 2 = f32 operands on the matrix pipe (round 4); impl 1 = the one-row-per-thread vector-ALU kernel
+    pick_bool(drop.thr16 != 0, [&](auto dr) {
+        constexpr bool DR = decltype(dr)::value;
+        if (g_exact_attn_impl == 2)
+            hipLaunchKernelGGL((attn_fwd_mf32_kernel<DR>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale,
                                ctx, ld_ctx, lse, drop);
         else
-            hipLaunchKernelGGL((attn_fwd_mf32_kernel<false>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale,
+            hipLaunchKernelGGL((attn_fwd_f32_kernel<DR>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale,
                                ctx, ld_ctx, lse, drop);
-        if (ctx_split3) split3_after(ctx, ld_ctx, B * S, heads * 64, ctx_split3, ld_c3, s);
-        BSCLIP_LAUNCH_CHECK();
-        return BSCLIP_OK;
-    }
-    if (drop.thr16)
-        hipLaunchKernelGGL((attn_fwd_f32_kernel<true>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale, ctx,
-                           ld_ctx, lse, drop);
-    else
-        hipLaunchKernelGGL((attn_fwd_f32_kernel<false>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, S, heads, key_bias, scale, ctx,
-                           ld_ctx, lse, drop);
+    });
     if (ctx_split3) split3_after(ctx, ld_ctx, B * S, heads * 64, ctx_split3, ld_c3, s);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -789,8 +780,7 @@ extern "C" int bsclip_attn_fwd_f32(const float* qkv, int ld_qkv, int B, int S, i
 extern "C" int bsclip_dgelu_split3(const float* dact, int ld_dact, const float* z, int ld_z, int M, int N, void* dst, int ld_dst,
                                    float* out32, int ld_out32, void* stream) {
     BSCLIP_REQUIRE(dact && z && (dst || out32), "bsclip_dgelu_split3: null pointer");
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(dact) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(out32)) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(dst) & 7) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, dact, z, out32) && aligned_to(8, dst),
                    "bsclip_dgelu_split3: dact / z / out32 must be 16-byte, dst 8-byte aligned");
     BSCLIP_REQUIRE(M > 0 && N > 0 && N % 4 == 0 && ld_dact >= N && ld_dact % 4 == 0 && ld_z >= N && ld_z % 4 == 0 &&
                        (dst == nullptr || (ld_dst >= 3 * N && ld_dst % 4 == 0)) && (out32 == nullptr || (ld_out32 >= N && ld_out32 % 4 == 0)),
@@ -807,7 +797,7 @@ extern "C" int bsclip_split3_transpose(const float* src, int ld_src, int R, int 
     BSCLIP_REQUIRE(src && dst, "bsclip_split3_transpose: null pointer");
     BSCLIP_REQUIRE((lora_a == nullptr) == (lora_b == nullptr), "bsclip_split3_transpose: lora_a and lora_b go together");
     BSCLIP_REQUIRE(R > 0 && C > 0 && Rp >= R && Rp % 64 == 0 && ld_src >= C && ld_dst >= 3 * Rp && ld_dst % 8 == 0 && (order == 0 || order == 1) &&
-                       (lora_a == nullptr || (R == 3 * H && C == H)) && (reinterpret_cast<uintptr_t>(dst) & 15) == 0,
+                       (lora_a == nullptr || (R == 3 * H && C == H)) && aligned_to(16, dst),
                    "bsclip_split3_transpose: R=%d C=%d Rp=%d order=%d H=%d ld_src=%d ld_dst=%d", R, C, Rp, order, H, ld_src, ld_dst);
     hipLaunchKernelGGL(split3_transpose_kernel, dim3(Rp / 64, (C + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), src, ld_src, R,
                        C, Rp, order, lora_a, lora_b, H, static_cast<bf16_t*>(dst), ld_dst);
@@ -830,14 +820,13 @@ extern "C" int bsclip_attn_bwd_f32(const float* qkv, int ld_qkv, const float* dc
                                    const float* lse, int B, int S, int heads, const float* key_bias, float scale, float* dqkv, int ld_dqkv,
                                    void* dqkv_split3, int ld_d3, float dropout_p, uint32_t dropout_seed, void* stream) {
     BSCLIP_REQUIRE(qkv && dctx && ctx && lse && dqkv, "bsclip_attn_bwd_f32: null pointer");
-    BSCLIP_REQUIRE(!dqkv_split3 || (ld_d3 >= 9 * heads * 64 && ld_d3 % 4 == 0 && (reinterpret_cast<uintptr_t>(dqkv_split3) & 7) == 0),
+    BSCLIP_REQUIRE(!dqkv_split3 || (ld_d3 >= 9 * heads * 64 && ld_d3 % 4 == 0 && aligned_to(8, dqkv_split3)),
                    "bsclip_attn_bwd_f32: dqkv_split3 bf16 [B S, ld_d3 >= 9 heads 64], 8-byte aligned (ld_d3=%d)", ld_d3);
     BSCLIP_REQUIRE(B > 0 && heads > 0 && S > 0 && S <= AF_SMAX, "bsclip_attn_bwd_f32: B=%d heads=%d S=%d (S <= 224)", B, heads, S);
     BSCLIP_REQUIRE(ld_qkv >= 3 * heads * 64 && ld_qkv % 4 == 0 && ld_dqkv >= 3 * heads * 64 && ld_dqkv % 4 == 0 && ld_ctx >= heads * 64 &&
                        ld_ctx % 4 == 0 && ld_dctx >= heads * 64 && ld_dctx % 4 == 0,
                    "bsclip_attn_bwd_f32: ld_qkv=%d ld_dqkv=%d ld_ctx=%d ld_dctx=%d", ld_qkv, ld_dqkv, ld_ctx, ld_dctx);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(ctx) | reinterpret_cast<uintptr_t>(dctx) |
-                     reinterpret_cast<uintptr_t>(dqkv)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, qkv, ctx, dctx, dqkv),
                    "bsclip_attn_bwd_f32: qkv, ctx, dctx and dqkv must be 16-byte aligned (vector loads / stores)");
     BSCLIP_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "bsclip_attn_bwd_f32: dropout_p=%f", dropout_p);
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
@@ -848,23 +837,15 @@ extern "C" int bsclip_attn_bwd_f32(const float* qkv, int ld_qkv, const float* dc
         BSCLIP_LAUNCH_CHECK();
         return BSCLIP_OK;
     }
-    if (g_exact_attn_impl == 2) {
-        if (drop.thr16)
-            hipLaunchKernelGGL((attn_bwd_mf32_kernel<true>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx,
+    pick_bool(drop.thr16 != 0, [&](auto dr) {
+        constexpr bool DR = decltype(dr)::value;
+        if (g_exact_attn_impl == 2)
+            hipLaunchKernelGGL((attn_bwd_mf32_kernel<DR>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx,
                                lse, S, heads, key_bias, scale, dqkv, ld_dqkv, drop);
         else
-            hipLaunchKernelGGL((attn_bwd_mf32_kernel<false>), dim3(B * heads), dim3(MF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx,
+            hipLaunchKernelGGL((attn_bwd_f32_kernel<DR>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx,
                                lse, S, heads, key_bias, scale, dqkv, ld_dqkv, drop);
-        if (dqkv_split3) split3_after(dqkv, ld_dqkv, B * S, 3 * heads * 64, dqkv_split3, ld_d3, s);
-        BSCLIP_LAUNCH_CHECK();
-        return BSCLIP_OK;
-    }
-    if (drop.thr16)
-        hipLaunchKernelGGL((attn_bwd_f32_kernel<true>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx, lse,
-                           S, heads, key_bias, scale, dqkv, ld_dqkv, drop);
-    else
-        hipLaunchKernelGGL((attn_bwd_f32_kernel<false>), dim3(B * heads), dim3(AF_THREADS), 0, s, qkv, ld_qkv, dctx, ld_dctx, ctx, ld_ctx, lse,
-                           S, heads, key_bias, scale, dqkv, ld_dqkv, drop);
+    });
     if (dqkv_split3) split3_after(dqkv, ld_dqkv, B * S, 3 * heads * 64, dqkv_split3, ld_d3, s);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;

@@ -204,12 +204,10 @@ extern "C" int bsclip_ln_param_grad(const void* x, int ld_x, int x_bf16, const f
     if (blocks > PG_MAX_BLOCKS) blocks = PG_MAX_BLOCKS;
     const DropCfg drop = make_drop(in_dropout_p, in_dropout_seed);
     const bf16_t* gg = static_cast<const bf16_t*>(g_gemm);
-#define PG_LAUNCH(HH, XB)                                                                                                    \
-    hipLaunchKernelGGL((ln_pgrad_kernel<HH, XB>), dim3(blocks), dim3(PG_BLOCK), 0, s, x, ld_x, stats, M, g_resid, ld_gr, gg, ld_g, \
-                       dt, lora_a, mode, drop, workspace)
-    if (H == 768) { if (x_bf16) PG_LAUNCH(768, true); else PG_LAUNCH(768, false); }
-    else          { if (x_bf16) PG_LAUNCH(512, true); else PG_LAUNCH(512, false); }
-#undef PG_LAUNCH
+    pick_int<768, 512>(H, [&](auto h) { pick_bool(x_bf16 != 0, [&](auto xb) {
+        hipLaunchKernelGGL((ln_pgrad_kernel<decltype(h)::value, decltype(xb)::value>), dim3(blocks), dim3(PG_BLOCK), 0, s, x, ld_x, stats,
+                           M, g_resid, ld_gr, gg, ld_g, dt, lora_a, mode, drop, workspace);
+    }); });
     hipLaunchKernelGGL(slab_reduce_add_kernel, dim3(ceil_div(2 * H, 32)), dim3(256), 0, s, workspace, blocks, 2 * H, d_gamma,
                        d_beta, H);
     BSCLIP_LAUNCH_CHECK();

@@ -244,13 +244,13 @@ extern "C" int bsclip_gemm_bf16(const void* A, int lda, const void* B, int ldb, 
     BSCLIP_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0, "bsclip_gemm_bf16: lda=%d ldb=%d (K=%d)", lda,
                    ldb, K);
     BSCLIP_REQUIRE(ldc >= N && ldc % 4 == 0, "bsclip_gemm_bf16: ldc=%d (N=%d)", ldc, N);
-    BSCLIP_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "bsclip_gemm_bf16: 16-B alignment");
+    BSCLIP_REQUIRE(aligned_to(16, A, B, C), "bsclip_gemm_bf16: 16-B alignment");
     BSCLIP_REQUIRE(!args || args->struct_size == sizeof(bsclip_epi_args),
                    "bsclip_gemm_bf16: args->struct_size=%u, this library's bsclip_epi_args is %zu bytes (binding out of date?)",
                    args->struct_size, sizeof(bsclip_epi_args));
     EpiArgs e = epi_from_public(args, N);
     if (args) {
-        BSCLIP_REQUIRE(!e.aux || (e.ld_aux >= N && e.ld_aux % 16 == 0 && (((uintptr_t)e.aux) & 15) == 0),
+        BSCLIP_REQUIRE(!e.aux || (e.ld_aux >= N && e.ld_aux % 16 == 0 && aligned_to(16, e.aux)),
                        "bsclip_gemm_bf16: aux (8-bit gelu' band) needs ld_aux >= N, ld_aux %% 16 == 0, 16-B alignment (ld_aux=%d)",
                        args->ld_aux);
         BSCLIP_REQUIRE(args->dropout_p >= 0.f && args->dropout_p < 1.f, "bsclip_gemm_bf16: dropout_p=%f", args->dropout_p);
@@ -258,7 +258,7 @@ extern "C" int bsclip_gemm_bf16(const void* A, int lda, const void* B, int ldb, 
                        "bsclip_gemm_bf16: dropout is only defined for BSCLIP_EPI_RESID_F32 / _BF16");
         e.drop = make_drop(args->dropout_p, args->dropout_seed);
     }
-    BSCLIP_REQUIRE(!e.bias || (((uintptr_t)e.bias) & 15) == 0, "bsclip_gemm_bf16: bias must be 16-B aligned");
+    BSCLIP_REQUIRE(!e.bias || aligned_to(16, e.bias), "bsclip_gemm_bf16: bias must be 16-B aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
@@ -279,7 +279,7 @@ extern "C" int bsclip_gemm_bf16(const void* A, int lda, const void* B, int ldb, 
             launch_bias<BSCLIP_EPI_PATCH_F32>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
         case BSCLIP_EPI_RESID_BF16:
-            BSCLIP_REQUIRE(e.resid && e.ld_resid >= N && e.ld_resid % 4 == 0 && (((uintptr_t)e.resid) & 7) == 0,
+            BSCLIP_REQUIRE(e.resid && e.ld_resid >= N && e.ld_resid % 4 == 0 && aligned_to(8, e.resid),
                            "bsclip_gemm_bf16: RESID_BF16 needs resid (bf16, 8-byte aligned rows) / ld_resid");
             launch_bias<BSCLIP_EPI_RESID_BF16>(a, lda, b, ldb, C, ldc, M, N, K, e, s, f16);
             break;
@@ -319,7 +319,7 @@ extern "C" int bsclip_gemm_splitk_f32(const void* A, int lda, const void* B, int
                    "bsclip_gemm_splitk_f32: M=%d N=%d (multiple of 256) K=%d (multiple of 64 * splits=%d)", M, N, K, splits);
     BSCLIP_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && ldc >= N && ldc % 4 == 0,
                    "bsclip_gemm_splitk_f32: lda=%d ldb=%d ldc=%d", lda, ldb, ldc);
-    BSCLIP_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)partial) & 15) == 0, "bsclip_gemm_splitk_f32: 16-B alignment");
+    BSCLIP_REQUIRE(aligned_to(16, A, B, C, partial), "bsclip_gemm_splitk_f32: 16-B alignment");
     EpiArgs e = epi_from_public(nullptr, N);
     e.split_stride = (long)M * N;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -387,7 +387,7 @@ int bsclip_gemm_bf16_batched(const bsclip_gemm_batch& t, int nb, int lda, int ld
     BSCLIP_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && ldc >= N && ldc % 4 == 0,
                    "bsclip_gemm_bf16_batched: lda=%d ldb=%d ldc=%d", lda, ldb, ldc);
     for (int i = 0; i < nb; ++i)
-        BSCLIP_REQUIRE(t.A[i] && t.B[i] && t.C[i] && (((uintptr_t)t.A[i] | (uintptr_t)t.B[i] | (uintptr_t)t.C[i]) & 15) == 0,
+        BSCLIP_REQUIRE(t.A[i] && t.B[i] && t.C[i] && aligned_to(16, t.A[i], t.B[i], t.C[i]),
                        "bsclip_gemm_bf16_batched: operand %d null or not 16-B aligned", i);
     const EpiArgs e = epi_from_public(nullptr, N);
     const int tiles_m = ceil_div(M, 128), tiles_n = N / 128;
@@ -416,16 +416,16 @@ extern "C" int bsclip_gemm_fp8(const void* A8, int lda, const void* B8, int ldb,
                    M, N, K);
     BSCLIP_REQUIRE(lda >= K && ldb >= K && lda % 16 == 0 && ldb % 16 == 0, "bsclip_gemm_fp8: lda=%d ldb=%d (K=%d)", lda, ldb, K);
     BSCLIP_REQUIRE(ldc >= N && ldc % 4 == 0 && (epilogue != BSCLIP_EPI_GELU_FP8 || ldc % 16 == 0), "bsclip_gemm_fp8: ldc=%d", ldc);
-    BSCLIP_REQUIRE((((uintptr_t)A8 | (uintptr_t)B8 | (uintptr_t)C) & 15) == 0, "bsclip_gemm_fp8: 16-B alignment");
-    BSCLIP_REQUIRE(args->bias && f8->alpha && ((((uintptr_t)args->bias | (uintptr_t)f8->alpha)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, A8, B8, C), "bsclip_gemm_fp8: 16-B alignment");
+    BSCLIP_REQUIRE(args->bias && f8->alpha && aligned_to(16, args->bias, f8->alpha),
                    "bsclip_gemm_fp8: bias and alpha are required, 16-B aligned");
     BSCLIP_REQUIRE((f8->a_aug == nullptr) == (f8->b_aug == nullptr), "bsclip_gemm_fp8: a_aug and b_aug go together");
     BSCLIP_REQUIRE(!f8->a_aug || (f8->ld_a_aug >= 64 && f8->ld_b_aug >= 64 && f8->ld_a_aug % 8 == 0 && f8->ld_b_aug % 8 == 0 &&
-                                  (((uintptr_t)f8->a_aug | (uintptr_t)f8->b_aug) & 15) == 0),
+                                  aligned_to(16, f8->a_aug, f8->b_aug)),
                    "bsclip_gemm_fp8: K-augmentation block needs ld >= 64, ld %% 8 == 0, 16-B alignment");
     BSCLIP_REQUIRE(f8->form == 1 || f8->form == 2, "bsclip_gemm_fp8: form %d (1 or 2)", f8->form);
     EpiArgs e = epi_from_public(args, N);
-    BSCLIP_REQUIRE(!e.aux || (e.ld_aux >= N && e.ld_aux % 16 == 0 && (((uintptr_t)e.aux) & 15) == 0), "bsclip_gemm_fp8: aux band");
+    BSCLIP_REQUIRE(!e.aux || (e.ld_aux >= N && e.ld_aux % 16 == 0 && aligned_to(16, e.aux)), "bsclip_gemm_fp8: aux band");
     BSCLIP_REQUIRE(args->dropout_p >= 0.f && args->dropout_p < 1.f && (args->dropout_p == 0.f || epilogue == BSCLIP_EPI_RESID_F32),
                    "bsclip_gemm_fp8: dropout_p=%f", args->dropout_p);
     e.drop = make_drop(args->dropout_p, args->dropout_seed);
@@ -435,23 +435,13 @@ extern "C" int bsclip_gemm_fp8(const void* A8, int lda, const void* B8, int ldb,
     e.ld_a_aug = f8->ld_a_aug;
     e.ld_b_aug = f8->ld_b_aug;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define F8_CASE(EPI)                                                                   \
-    case EPI:                                                                          \
-        if (f8->form == 1) launch_f8<EPI, 1>(A8, lda, B8, ldb, C, ldc, M, N, K, e, s); \
-        else launch_f8<EPI, 2>(A8, lda, B8, ldb, C, ldc, M, N, K, e, s);               \
-        break;
-    switch (epilogue) {
-        F8_CASE(BSCLIP_EPI_BF16)
-        F8_CASE(BSCLIP_EPI_F32)
-        F8_CASE(BSCLIP_EPI_GELU_FP8)
-        case BSCLIP_EPI_RESID_F32:
-            BSCLIP_REQUIRE(e.resid && e.ld_resid >= N, "bsclip_gemm_fp8: RESID needs resid/ld_resid");
-            if (f8->form == 1) launch_f8<BSCLIP_EPI_RESID_F32, 1>(A8, lda, B8, ldb, C, ldc, M, N, K, e, s);
-            else launch_f8<BSCLIP_EPI_RESID_F32, 2>(A8, lda, B8, ldb, C, ldc, M, N, K, e, s);
-            break;
-        default: BSCLIP_REQUIRE(false, "bsclip_gemm_fp8: epilogue %d not available with fp8 operands", epilogue);
-    }
-#undef F8_CASE
+    BSCLIP_REQUIRE(epilogue != BSCLIP_EPI_RESID_F32 || (e.resid && e.ld_resid >= N), "bsclip_gemm_fp8: RESID needs resid/ld_resid");
+    const bool available = pick_int<BSCLIP_EPI_BF16, BSCLIP_EPI_F32, BSCLIP_EPI_GELU_FP8, BSCLIP_EPI_RESID_F32>(epilogue, [&](auto epi) {
+        pick_int<1, 2>(f8->form, [&](auto form) {
+            launch_f8<decltype(epi)::value, decltype(form)::value>(A8, lda, B8, ldb, C, ldc, M, N, K, e, s);
+        });
+    });
+    BSCLIP_REQUIRE(available, "bsclip_gemm_fp8: epilogue %d not available with fp8 operands", epilogue);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -492,7 +482,7 @@ __global__ void lora_baug_set_kernel(bf16_t* __restrict__ b_aug, int ld, int H, 
 extern "C" int bsclip_quantize_rows_fp8(const float* src, int R, int C, void* dst, int ld_dst, float* scale, void* stream) {
     BSCLIP_REQUIRE(src && dst && scale && R > 0 && C > 0 && C % 4 == 0 && ld_dst >= C && ld_dst % 4 == 0,
                    "bsclip_quantize_rows_fp8: R=%d C=%d ld_dst=%d", R, C, ld_dst);
-    BSCLIP_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "bsclip_quantize_rows_fp8: 16-B alignment");
+    BSCLIP_REQUIRE(aligned_to(16, src, dst), "bsclip_quantize_rows_fp8: 16-B alignment");
     hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), src, R, C,
                        static_cast<unsigned char*>(dst), ld_dst, scale);
     BSCLIP_LAUNCH_CHECK();

@@ -2,6 +2,8 @@
 // and the K-loop ablation mask of the ping-pong kernel.  Included by gemm.hip after its anonymous namespace; on no product path.
 
 static int g_diag_ablate = 0;  // tools/gemm_ablate.py: which parts of the K loop the diagnostic EPI_BF16 build leaves out
+// HAS_BIAS of the diagnostic build of each epilogue
+constexpr bool diag_has_bias(int epi) { return epi == BSCLIP_EPI_GELU_BF16 || epi == BSCLIP_EPI_RESID_F32 || epi == BSCLIP_EPI_RESID_BF16; }
 
 // Diagnostic: the ping-pong kernel with four phase stamps per workgroup and wave group (start, prologue done, K loop
 // done, end) written to diag[grid*16] (8 per wave group: start, prologue, K loop, end, 4 epilogue sections) (100 MHz ticks).  Used by tools/gemm_phases.py; not on any product path.
@@ -16,29 +18,19 @@ extern "C" int bsclip_gemm_diag(const void* A, int lda, const void* B, int ldb, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
-    switch (epilogue) {
-        case BSCLIP_EPI_BF16:
-#define DIAG_ABL(mask)                                                                                                      \
-    case mask:                                                                                                             \
-        hipLaunchKernelGGL((gemm_nt_pp_kernel<BSCLIP_EPI_BF16, false, true, mask>), grid, block, 0, s, a, lda, b, ldb, C, ldc, \
-                           M, N, K, tiles_n, e);                                                                           \
-        break;
-            switch (g_diag_ablate) {
-                DIAG_ABL(0) DIAG_ABL(1) DIAG_ABL(2) DIAG_ABL(4) DIAG_ABL(8) DIAG_ABL(6) DIAG_ABL(3) DIAG_ABL(5) DIAG_ABL(9)
-                default: BSCLIP_REQUIRE(false, "bsclip_gemm_diag: ablation mask %d not instantiated", g_diag_ablate);
-            }
-#undef DIAG_ABL
-            break;
-        case BSCLIP_EPI_GELU_BF16:
-            hipLaunchKernelGGL((gemm_nt_pp_kernel<BSCLIP_EPI_GELU_BF16, true, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        case BSCLIP_EPI_RESID_F32:
-            hipLaunchKernelGGL((gemm_nt_pp_kernel<BSCLIP_EPI_RESID_F32, true, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        case BSCLIP_EPI_DGELU_BF16:
-            hipLaunchKernelGGL((gemm_nt_pp_kernel<BSCLIP_EPI_DGELU_BF16, false, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        default: BSCLIP_REQUIRE(false, "bsclip_gemm_diag: epilogue %d has no diagnostic build", epilogue);
+    auto launch = [&](auto epi, auto abl) {
+        constexpr int EPI = decltype(epi)::value;
+        hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, diag_has_bias(EPI), true, decltype(abl)::value>), grid, block, 0, s, a, lda, b, ldb, C,
+                           ldc, M, N, K, tiles_n, e);
+    };
+    if (epilogue == BSCLIP_EPI_BF16) {   // the only epilogue with ablated builds
+        const bool built = pick_int<0, 1, 2, 4, 8, 6, 3, 5, 9>(
+            g_diag_ablate, [&](auto abl) { launch(std::integral_constant<int, BSCLIP_EPI_BF16>{}, abl); });
+        BSCLIP_REQUIRE(built, "bsclip_gemm_diag: ablation mask %d not instantiated", g_diag_ablate);
+    } else {
+        const bool built = pick_int<BSCLIP_EPI_GELU_BF16, BSCLIP_EPI_RESID_F32, BSCLIP_EPI_DGELU_BF16>(
+            epilogue, [&](auto epi) { launch(epi, std::integral_constant<int, 0>{}); });
+        BSCLIP_REQUIRE(built, "bsclip_gemm_diag: epilogue %d has no diagnostic build", epilogue);
     }
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -57,21 +49,11 @@ extern "C" int bsclip_gemm_duo_diag(const void* A, int lda, const void* B, int l
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
-    switch (epilogue) {
-        case BSCLIP_EPI_BF16:
-            hipLaunchKernelGGL((gemm_nt_duo_kernel<BSCLIP_EPI_BF16, false, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        case BSCLIP_EPI_GELU_BF16:
-            hipLaunchKernelGGL((gemm_nt_duo_kernel<BSCLIP_EPI_GELU_BF16, true, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        case BSCLIP_EPI_RESID_F32:
-            hipLaunchKernelGGL((gemm_nt_duo_kernel<BSCLIP_EPI_RESID_F32, true, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        case BSCLIP_EPI_DGELU_BF16:
-            hipLaunchKernelGGL((gemm_nt_duo_kernel<BSCLIP_EPI_DGELU_BF16, false, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
-            break;
-        default: BSCLIP_REQUIRE(false, "bsclip_gemm_duo_diag: epilogue %d has no diagnostic build", epilogue);
-    }
+    const bool built = pick_int<BSCLIP_EPI_BF16, BSCLIP_EPI_GELU_BF16, BSCLIP_EPI_RESID_F32, BSCLIP_EPI_DGELU_BF16>(epilogue, [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        hipLaunchKernelGGL((gemm_nt_duo_kernel<EPI, diag_has_bias(EPI), true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, e);
+    });
+    BSCLIP_REQUIRE(built, "bsclip_gemm_duo_diag: epilogue %d has no diagnostic build", epilogue);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -90,19 +72,13 @@ extern "C" int bsclip_gemm_pers_diag(const void* A, int lda, const void* B, int 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
-#define PERS_DIAG(EPI, HB)                                                                                                  \
-    case EPI:                                                                                                               \
-        hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, HB, true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K, tiles_n, nt, e); \
-        break;
-    switch (epilogue) {
-        PERS_DIAG(BSCLIP_EPI_BF16, false)
-        PERS_DIAG(BSCLIP_EPI_GELU_BF16, true)
-        PERS_DIAG(BSCLIP_EPI_RESID_F32, true)
-        PERS_DIAG(BSCLIP_EPI_RESID_BF16, true)
-        PERS_DIAG(BSCLIP_EPI_DGELU_BF16, false)
-        default: BSCLIP_REQUIRE(false, "bsclip_gemm_pers_diag: epilogue %d has no diagnostic build", epilogue);
-    }
-#undef PERS_DIAG
+    const bool built = pick_int<BSCLIP_EPI_BF16, BSCLIP_EPI_GELU_BF16, BSCLIP_EPI_RESID_F32, BSCLIP_EPI_RESID_BF16, BSCLIP_EPI_DGELU_BF16>(
+        epilogue, [&](auto epi) {
+            constexpr int EPI = decltype(epi)::value;
+            hipLaunchKernelGGL((gemm_nt_pers_kernel<EPI, diag_has_bias(EPI), true>), grid, block, 0, s, a, lda, b, ldb, C, ldc, M, N, K,
+                               tiles_n, nt, e);
+        });
+    BSCLIP_REQUIRE(built, "bsclip_gemm_pers_diag: epilogue %d has no diagnostic build", epilogue);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

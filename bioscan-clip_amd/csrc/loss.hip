@@ -326,7 +326,7 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     BSCLIP_REQUIRE(D == 768, "bsclip_infonce_fwd_bwd: D=%d (supported: 768)", D);
     BSCLIP_REQUIRE(N > 0 && N <= 16384 && row0 >= 0 && n_local >= 0 && row0 + n_local <= N,
                    "bsclip_infonce_fwd_bwd: N=%d row0=%d n_local=%d", N, row0, n_local);
-    BSCLIP_REQUIRE((((uintptr_t)workspace) & 15) == 0, "bsclip_infonce_fwd_bwd: workspace must be 16-B aligned");
+    BSCLIP_REQUIRE(aligned_to(16, workspace), "bsclip_infonce_fwd_bwd: workspace must be 16-B aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Layout L = make_layout(N, nmod, D);
     const int Np = L.Np;

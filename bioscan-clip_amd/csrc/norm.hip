@@ -395,20 +395,6 @@ int ln_grid(int M, int resident_per_cu = 8) {
 
 }  // namespace
 
-#define LN_FWD_LAUNCH(HH, XB, LO)                                                                              \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, M, \
-                       gamma, beta, eps, static_cast<bf16_t*>(y_bf16), ld_y, y_f32, lora_a, stats, drop,               \
-                       static_cast<bf16_t*>(nullptr), 0, static_cast<bf16_t*>(y_split3), ld_y3)
-#define LN_FWD16_LAUNCH(HH, XB, LO)                                                                            \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO, false, true>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, \
-                       M, gamma, beta, eps, static_cast<bf16_t*>(y_bf16), ld_y, y_f32, lora_a, stats, drop,            \
-                       static_cast<bf16_t*>(nullptr), 0, static_cast<bf16_t*>(nullptr), 0)
-#define LN_FWD16_PICK(HH)                                                                                      \
-    do {                                                                                                       \
-        if (x_bf16) { if (lo) LN_FWD16_LAUNCH(HH, true, true); else LN_FWD16_LAUNCH(HH, true, false); }        \
-        else        { if (lo) LN_FWD16_LAUNCH(HH, false, true); else LN_FWD16_LAUNCH(HH, false, false); }      \
-    } while (0)
-
 extern "C" int bsclip_layernorm_fwd(const void* x, int ld_x, int x_bf16, int M, int H, const float* gamma,
                                     const float* beta, float eps, void* y_bf16, int ld_y, float* y_f32, void* y_split3, int ld_y3,
                                     const float* lora_a, float* stats, float dropout_p, uint32_t dropout_seed, void* stream) {
@@ -422,29 +408,23 @@ extern "C" int bsclip_layernorm_fwd(const void* x, int ld_x, int x_bf16, int M, 
     BSCLIP_REQUIRE(!y_bf16 || (ld_y % 4 == 0 && ld_y >= H + (lora_a ? BSCLIP_KPAD : 0)),
                    "bsclip_layernorm_fwd: ld_y=%d too small for H=%d%s", ld_y, H, lora_a ? "+KPAD" : "");
     BSCLIP_REQUIRE(!lora_a || y_bf16, "bsclip_layernorm_fwd: lora_a needs y_bf16");
-    BSCLIP_REQUIRE(!y_split3 || (ld_y3 >= 3 * H && ld_y3 % 4 == 0 && (reinterpret_cast<uintptr_t>(y_split3) & 7) == 0),
+    BSCLIP_REQUIRE(!y_split3 || (ld_y3 >= 3 * H && ld_y3 % 4 == 0 && aligned_to(8, y_split3)),
                    "bsclip_layernorm_fwd: y_split3 bf16 [M, ld_y3 >= 3H], 8-byte aligned (ld_y3=%d)", ld_y3);
     BSCLIP_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "bsclip_layernorm_fwd: dropout_p=%f", dropout_p);
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lo = lora_a != nullptr;
-    if (f16) {
-        if (H == 768) LN_FWD16_PICK(768);
-        else LN_FWD16_PICK(512);
-    } else if (H == 768) {
-        if (x_bf16) { if (lo) LN_FWD_LAUNCH(768, true, true); else LN_FWD_LAUNCH(768, true, false); }
-        else        { if (lo) LN_FWD_LAUNCH(768, false, true); else LN_FWD_LAUNCH(768, false, false); }
-    } else {
-        if (x_bf16) { if (lo) LN_FWD_LAUNCH(512, true, true); else LN_FWD_LAUNCH(512, true, false); }
-        else        { if (lo) LN_FWD_LAUNCH(512, false, true); else LN_FWD_LAUNCH(512, false, false); }
-    }
+    // fp16 operands have no split3 output (checked above); the fp8 output form is bsclip_layernorm_fwd_fp8's
+    pick_int<768, 512>(H, [&](auto h) { pick_bool(x_bf16, [&](auto xb) { pick_bool(lo, [&](auto lr) { pick_bool(f16, [&](auto fp) {
+        constexpr int HH = decltype(h)::value;
+        constexpr bool XB = decltype(xb)::value, LO = decltype(lr)::value, F16 = decltype(fp)::value;
+        hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO, false, F16>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, M,
+                           gamma, beta, eps, static_cast<bf16_t*>(y_bf16), ld_y, y_f32, lora_a, stats, drop,
+                           static_cast<bf16_t*>(nullptr), 0, static_cast<bf16_t*>(F16 ? nullptr : y_split3), F16 ? 0 : ld_y3);
+    }); }); }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
-
-#define LN_FWD8_LAUNCH(HH, XB, LO)                                                                                   \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO, true>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, M, gamma, \
-                       beta, eps, static_cast<bf16_t*>(y_fp8), ld_y, y_f32, lora_a, stats, drop, static_cast<bf16_t*>(t_aug), ld_t)
 
 extern "C" int bsclip_layernorm_fwd_fp8(const void* x, int ld_x, int x_bf16, int M, int H, const float* gamma,
                                         const float* beta, float eps, void* y_fp8, int ld_y, void* t_aug, int ld_t,
@@ -460,25 +440,15 @@ extern "C" int bsclip_layernorm_fwd_fp8(const void* x, int ld_x, int x_bf16, int
     const DropCfg drop = make_drop(dropout_p, dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lo = lora_a != nullptr;
-    if (H == 768) {
-        if (x_bf16) { if (lo) LN_FWD8_LAUNCH(768, true, true); else LN_FWD8_LAUNCH(768, true, false); }
-        else        { if (lo) LN_FWD8_LAUNCH(768, false, true); else LN_FWD8_LAUNCH(768, false, false); }
-    } else {
-        if (x_bf16) { if (lo) LN_FWD8_LAUNCH(512, true, true); else LN_FWD8_LAUNCH(512, true, false); }
-        else        { if (lo) LN_FWD8_LAUNCH(512, false, true); else LN_FWD8_LAUNCH(512, false, false); }
-    }
+    pick_int<768, 512>(H, [&](auto h) { pick_bool(x_bf16, [&](auto xb) { pick_bool(lo, [&](auto lr) {
+        constexpr int HH = decltype(h)::value;
+        constexpr bool XB = decltype(xb)::value, LO = decltype(lr)::value;
+        hipLaunchKernelGGL((layernorm_fwd_kernel<HH, XB, LO, true>), dim3(ln_grid(M, LO ? 5 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, M, gamma,
+                           beta, eps, static_cast<bf16_t*>(y_fp8), ld_y, y_f32, lora_a, stats, drop, static_cast<bf16_t*>(t_aug), ld_t);
+    }); }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
-
-#define LN_BWD_LAUNCH(HH, XB, LO)                                                                                \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<HH, XB, LO>), dim3(ln_grid(M, LO ? 4 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, stats, \
-                       gamma, M, g_resid, ld_gr, g_gemm, ld_g, dt, lora_a, mode, dx_f32, \
-                       ld_dx, dx_bf16, ld_dxb, drop, in_drop, resid_flags)
-#define LN_BWD16_LAUNCH(LO)                                                                                      \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<768, true, LO, true>), dim3(ln_grid(M, LO ? 4 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, \
-                       stats, gamma, M, g_resid, ld_gr, g_gemm, ld_g, dt, lora_a, mode, dx_f32, ld_dx, dx_bf16, ld_dxb, drop, in_drop, \
-                       resid_flags)
 
 extern "C" int bsclip_layernorm_bwd(const void* x, int ld_x, int x_bf16, const float* stats, const float* gamma, int M,
                                     int H, const void* g_resid, int ld_gr, const void* g_gemm, int ld_g,
@@ -509,16 +479,14 @@ extern "C" int bsclip_layernorm_bwd(const void* x, int ld_x, int x_bf16, const f
     const DropCfg in_drop = make_drop(in_dropout_p, in_dropout_seed);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lo = lora_a != nullptr;
-    if (f16) {
-        if (lo) LN_BWD16_LAUNCH(true);
-        else LN_BWD16_LAUNCH(false);
-    } else if (H == 768) {
-        if (x_bf16) { if (lo) LN_BWD_LAUNCH(768, true, true); else LN_BWD_LAUNCH(768, true, false); }
-        else        { if (lo) LN_BWD_LAUNCH(768, false, true); else LN_BWD_LAUNCH(768, false, false); }
-    } else {
-        if (x_bf16) { if (lo) LN_BWD_LAUNCH(512, true, true); else LN_BWD_LAUNCH(512, true, false); }
-        else        { if (lo) LN_BWD_LAUNCH(512, false, true); else LN_BWD_LAUNCH(512, false, false); }
-    }
+    pick_int<768, 512>(H, [&](auto h) { pick_bool(x_bf16, [&](auto xb) { pick_bool(lo, [&](auto lr) { pick_bool(f16, [&](auto fp) {
+        constexpr int HH = decltype(h)::value;
+        constexpr bool XB = decltype(xb)::value, LO = decltype(lr)::value, F16 = decltype(fp)::value;
+        if constexpr (!F16 || (HH == 768 && XB))   // the fp16 backward is the ViT's: H = 768 on a 16-bit x (checked above)
+            hipLaunchKernelGGL((layernorm_bwd_kernel<HH, XB, LO, F16>), dim3(ln_grid(M, LO ? 4 : 8)), dim3(LN_BLOCK), 0, s, x, ld_x, stats,
+                               gamma, M, g_resid, ld_gr, g_gemm, ld_g, dt, lora_a, mode, dx_f32, ld_dx, dx_bf16, ld_dxb, drop, in_drop,
+                               resid_flags);
+    }); }); }); });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -543,7 +543,14 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, c
 
 constexpr int LG_MAX_BLOCKS = 768;   // three 4-wave workgroups per CU
 
-extern "C" int64_t bsclip_lora_grad_workspace_floats(int H) { return (int64_t)LG_MAX_BLOCKS * 16 * H; }
+static int lora_blocks(int M) {   // >= 8 rows per wave, clamped to [1, LG_MAX_BLOCKS]
+    const int blocks = ceil_div(M, 4 * 8);
+    return blocks > LG_MAX_BLOCKS ? LG_MAX_BLOCKS : blocks < 1 ? 1 : blocks;
+}
+// the workspace's two slabs of per-block partial sums, each [LG_MAX_BLOCKS][8 H] floats: pa (dB) at the base, pb (dA) behind it
+static size_t lora_slab_floats(int H) { return (size_t)LG_MAX_BLOCKS * 8 * H; }
+
+extern "C" int64_t bsclip_lora_grad_workspace_floats(int H) { return (int64_t)(2 * lora_slab_floats(H)); }
 
 extern "C" int bsclip_lora_grad(const void* dqkv, int ld_dqkv, const void* h, int ld_h, int M, int H,
                                 const float* lora_b, float* dt, float* dA, float* dBq, float* dBv, float* workspace,
@@ -554,26 +561,17 @@ extern "C" int bsclip_lora_grad(const void* dqkv, int ld_dqkv, const void* h, in
     BSCLIP_REQUIRE(ld_dqkv >= 3 * H && ld_dqkv % 4 == 0 && ld_h >= H + 8 && ld_h % 8 == 0,
                    "bsclip_lora_grad: ld_dqkv=%d ld_h=%d", ld_dqkv, ld_h);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int blocks = ceil_div(M, 4 * 8);  // >= 8 rows per wave
-    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+    const int blocks = lora_blocks(M);
     const bf16_t* g = static_cast<const bf16_t*>(dqkv);
     const bf16_t* hh = static_cast<const bf16_t*>(h);
     float* pa = workspace;
-    float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
-    if (H == 768) {
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, hh, ld_h, M,
-                           lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<768>), dim3(16 * 768 / 32), dim3(256), 0, s, pa, pb,
-                           blocks, dA, dBq, dBv);
-    } else {
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<512>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, hh, ld_h, M,
-                           lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<512>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<512>), dim3(16 * 512 / 32), dim3(256), 0, s, pa, pb,
-                           blocks, dA, dBq, dBv);
-    }
+    float* pb = workspace + lora_slab_floats(H);
+    pick_int<768, 512>(H, [&](auto h_) {
+        constexpr int HH = decltype(h_)::value;
+        hipLaunchKernelGGL((lora_grad_dt_db_kernel<HH>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, hh, ld_h, M, lora_b, dt, pa);
+        hipLaunchKernelGGL((lora_grad_da_kernel<HH>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
+        hipLaunchKernelGGL((lora_grad_reduce_kernel<HH>), dim3(16 * HH / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -587,27 +585,22 @@ extern "C" int bsclip_lora_grad_heads(const void* h, int ld_h, int M, int H, int
                    "bsclip_lora_grad_heads: null/empty input (M=%d B=%d)", M, B);
     BSCLIP_REQUIRE(H == 768 || H == 512, "bsclip_lora_grad_heads: H=%d (supported: 768, 512)", H);
     BSCLIP_REQUIRE(ld_h >= H && ld_h % 8 == 0, "bsclip_lora_grad_heads: ld_h=%d", ld_h);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(dt_partial) | reinterpret_cast<uintptr_t>(dt)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, dt_partial, dt),
                    "bsclip_lora_grad_heads: dt_partial and dt must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int heads = H / 64;
-    int blocks = ceil_div(M, 4 * 8);
-    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+    const int blocks = lora_blocks(M);
     const bf16_t* hh = static_cast<const bf16_t*>(h);
-    float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
+    float* pb = workspace + lora_slab_floats(H);
     const int nA = ceil_div(2 * M, 256);
     hipLaunchKernelGGL(lora_heads_reduce_kernel<false>, dim3(nA + heads * 512 / 32), dim3(256), 0, s, dt_partial, db_partial, M, heads, B, nA,
                        dt, dBq, dBv);
-    if (H == 768) {
-        hipLaunchKernelGGL((lora_grad_da_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<768>), dim3(8 * 768 / 32), dim3(256), 0, s, (const float*)nullptr, pb, blocks, dA,
-                           dBq, dBv, 8 * 768 / 32);
-    } else {
-        hipLaunchKernelGGL((lora_grad_da_kernel<512>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<512>), dim3(8 * 512 / 32), dim3(256), 0, s, (const float*)nullptr, pb, blocks, dA,
-                           dBq, dBv, 8 * 512 / 32);
-    }
+    pick_int<768, 512>(H, [&](auto h_) {
+        constexpr int HH = decltype(h_)::value;
+        hipLaunchKernelGGL((lora_grad_da_kernel<HH>), dim3(blocks), dim3(LG_BLOCK), 0, s, hh, ld_h, M, dt, pb);
+        hipLaunchKernelGGL((lora_grad_reduce_kernel<HH>), dim3(8 * HH / 32), dim3(256), 0, s, (const float*)nullptr, pb, blocks, dA, dBq,
+                           dBv, 8 * HH / 32);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -626,17 +619,14 @@ extern "C" int bsclip_lora_grad_heads_f16(const void* h, int ld_h, int M, int H,
                    "bsclip_lora_grad_heads_f16: null/empty input (M=%d B=%d)", M, B);
     BSCLIP_REQUIRE(H == 768, "bsclip_lora_grad_heads_f16: H=%d (the ViT's 768)", H);
     BSCLIP_REQUIRE(ld_h >= H && ld_h % 8 == 0, "bsclip_lora_grad_heads_f16: ld_h=%d", ld_h);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(dt_partial) | reinterpret_cast<uintptr_t>(dt) | reinterpret_cast<uintptr_t>(workspace) |
-                     reinterpret_cast<uintptr_t>(h)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, dt_partial, dt, workspace, h),
                    "bsclip_lora_grad_heads_f16: h, dt_partial, dt and workspace must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float unscale = ldexpf(1.f, -operands);
     const int heads = H / 64;
-    int blocks = ceil_div(M, 4 * 8);
-    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+    const int blocks = lora_blocks(M);
     const bf16_t* hh = static_cast<const bf16_t*>(h);
-    float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
+    float* pb = workspace + lora_slab_floats(H);
     const int nA = ceil_div(2 * M, 256);
     hipLaunchKernelGGL(lora_heads_reduce_kernel<true>, dim3(nA + heads * 512 / 32), dim3(256), 0, s, dt_partial, db_partial, M, heads, B,
                        nA, dt, dBq, dBv, unscale);
@@ -666,12 +656,9 @@ __global__ __launch_bounds__(256) void add_scaled_f32_kernel(const float* __rest
 extern "C" int bsclip_add_scaled_f32(const float* in, int64_t n, int scale_log2, float* out, void* stream) {
     BSCLIP_REQUIRE(in && out && n > 0, "bsclip_add_scaled_f32: bad args");
     BSCLIP_REQUIRE(scale_log2 >= -64 && scale_log2 <= 64, "bsclip_add_scaled_f32: scale_log2=%d (|k| <= 64)", scale_log2);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, in, out),
                    "bsclip_add_scaled_f32: in and out must be 16-byte aligned");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(add_scaled_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
+    hipLaunchKernelGGL(add_scaled_f32_kernel, dim3(grid4x256(n, 1024)), dim3(256), 0, static_cast<hipStream_t>(stream), in, (long)n,
                        ldexpf(1.f, scale_log2), out);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -682,7 +669,7 @@ extern "C" int bsclip_add_scaled_f32(const float* in, int64_t n, int scale_log2,
 // Reference lora_layer.py:16-39 / image_encoder.py:44-47 / dna_encoder.py:47-49:
 //   u_q = B_q^T dq, u_v = B_v^T dv;  dA_q += u_q y^T, dA_v += u_v y^T, dB_q += dq t_q^T, dB_v += dv t_v^T
 extern "C" int64_t bsclip_lora_grad_f32_workspace_floats(int M, int H) {
-    return M > 0 && H > 0 ? 16 * (int64_t)((M + 3) / 4 * 4) + (int64_t)LG_MAX_BLOCKS * 16 * H : -1;
+    return M > 0 && H > 0 ? 16 * (int64_t)((M + 3) / 4 * 4) + (int64_t)(2 * lora_slab_floats(H)) : -1;
 }
 
 extern "C" int bsclip_lora_grad_f32(const float* dqkv, int ld_dqkv, const float* y, int ld_y, int M, int H, const float* lora_a,
@@ -690,31 +677,24 @@ extern "C" int bsclip_lora_grad_f32(const float* dqkv, int ld_dqkv, const float*
     BSCLIP_REQUIRE(dqkv && y && lora_a && lora_b && dA && dB && workspace, "bsclip_lora_grad_f32: null pointer");
     BSCLIP_REQUIRE(M > 0 && (H == 768 || H == 512) && ld_dqkv >= 3 * H && ld_dqkv % 4 == 0 && ld_y >= H && ld_y % 4 == 0,
                    "bsclip_lora_grad_f32: M=%d H=%d ld_dqkv=%d ld_y=%d", M, H, ld_dqkv, ld_y);
-    BSCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(dqkv) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(lora_a) |
-                     reinterpret_cast<uintptr_t>(lora_b) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, dqkv, y, lora_a, lora_b, workspace),
                    "bsclip_lora_grad_f32: dqkv, y, lora_a, lora_b and workspace must be 16-byte aligned (vector loads)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int blocks = ceil_div(M, 4 * 8);
-    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+    const int blocks = lora_blocks(M);
     const size_t Mp = (size_t)(M + 3) / 4 * 4;
     float* t = workspace;
     float* dt = workspace + 8 * Mp;
     float* pa = workspace + 16 * Mp;
-    float* pb = pa + (size_t)LG_MAX_BLOCKS * 8 * H;
+    float* pb = pa + lora_slab_floats(H);
     float* dBq = dB;
     float* dBv = dB + (size_t)H * 4;
-    if (H == 768) {
-        hipLaunchKernelGGL((lora_t_f32_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, lora_a, t);
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<768, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, dqkv, ld_dqkv, t, 8, M, lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<768, false, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<768>), dim3(16 * 768 / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
-    } else {
-        hipLaunchKernelGGL((lora_t_f32_kernel<512>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, lora_a, t);
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<512, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, dqkv, ld_dqkv, t, 8, M, lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<512, false, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<512>), dim3(16 * 512 / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
-    }
+    pick_int<768, 512>(H, [&](auto h_) {
+        constexpr int HH = decltype(h_)::value;
+        hipLaunchKernelGGL((lora_t_f32_kernel<HH>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, lora_a, t);
+        hipLaunchKernelGGL((lora_grad_dt_db_kernel<HH, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, dqkv, ld_dqkv, t, 8, M, lora_b, dt, pa);
+        hipLaunchKernelGGL((lora_grad_da_kernel<HH, false, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, y, ld_y, M, dt, pb);
+        hipLaunchKernelGGL((lora_grad_reduce_kernel<HH>), dim3(16 * HH / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -729,23 +709,18 @@ extern "C" int bsclip_lora_grad_fp8(const void* dqkv, int ld_dqkv, const void* y
     BSCLIP_REQUIRE(ld_dqkv >= 3 * H && ld_dqkv % 4 == 0 && ld_y >= H && ld_y % 4 == 0 && ld_t >= 8 && ld_t % 8 == 0,
                    "bsclip_lora_grad_fp8: ld_dqkv=%d ld_y=%d ld_t=%d", ld_dqkv, ld_y, ld_t);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int blocks = ceil_div(M, 4 * 8);
-    if (blocks > LG_MAX_BLOCKS) blocks = LG_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+    const int blocks = lora_blocks(M);
     const bf16_t* g = static_cast<const bf16_t*>(dqkv);
     const bf16_t* tt = static_cast<const bf16_t*>(t_aug) - H;   // the kernel reads t at column H of its "haug" row
     const bf16_t* yy = static_cast<const bf16_t*>(y_fp8);
     float* pa = workspace;
-    float* pb = workspace + (size_t)LG_MAX_BLOCKS * 8 * H;
-    if (H == 768) {
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<768>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, tt, ld_t, M, lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<768, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, yy, ld_y, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<768>), dim3(16 * 768 / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
-    } else {
-        hipLaunchKernelGGL((lora_grad_dt_db_kernel<512>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, tt, ld_t, M, lora_b, dt, pa);
-        hipLaunchKernelGGL((lora_grad_da_kernel<512, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, yy, ld_y, M, dt, pb);
-        hipLaunchKernelGGL((lora_grad_reduce_kernel<512>), dim3(16 * 512 / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
-    }
+    float* pb = workspace + lora_slab_floats(H);
+    pick_int<768, 512>(H, [&](auto h_) {
+        constexpr int HH = decltype(h_)::value;
+        hipLaunchKernelGGL((lora_grad_dt_db_kernel<HH>), dim3(blocks), dim3(LG_BLOCK), 0, s, g, ld_dqkv, tt, ld_t, M, lora_b, dt, pa);
+        hipLaunchKernelGGL((lora_grad_da_kernel<HH, true>), dim3(blocks), dim3(LG_BLOCK), 0, s, yy, ld_y, M, dt, pb);
+        hipLaunchKernelGGL((lora_grad_reduce_kernel<HH>), dim3(16 * HH / 32), dim3(256), 0, s, pa, pb, blocks, dA, dBq, dBv);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
@@ -753,15 +728,12 @@ extern "C" int bsclip_lora_grad_fp8(const void* dqkv, int ld_dqkv, const void* y
 extern "C" int bsclip_colsum(const void* g, int ld_g, int g_is_bf16, int M, int N, float* out, void* stream) {
     BSCLIP_REQUIRE(g && out && M > 0 && N > 0 && ld_g >= N, "bsclip_colsum: bad args");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool wide = N % 8 == 0 && ld_g % 8 == 0 && (((uintptr_t)g) & 15) == 0;
-    if (wide) {
-        if (g_is_bf16) hipLaunchKernelGGL((colsum8_kernel<true>), dim3(N / 8), dim3(256), 0, s, g, ld_g, M, N, out);
-        else hipLaunchKernelGGL((colsum8_kernel<false>), dim3(N / 8), dim3(256), 0, s, g, ld_g, M, N, out);
-    } else {
-        const dim3 grid(ceil_div(N, 32));
-        if (g_is_bf16) hipLaunchKernelGGL((colsum_kernel<true>), grid, dim3(256), 0, s, g, ld_g, M, N, out);
-        else hipLaunchKernelGGL((colsum_kernel<false>), grid, dim3(256), 0, s, g, ld_g, M, N, out);
-    }
+    const bool wide = N % 8 == 0 && ld_g % 8 == 0 && aligned_to(16, g);
+    pick_bool(g_is_bf16 != 0, [&](auto bf) {
+        constexpr bool BF = decltype(bf)::value;
+        if (wide) hipLaunchKernelGGL((colsum8_kernel<BF>), dim3(N / 8), dim3(256), 0, s, g, ld_g, M, N, out);
+        else hipLaunchKernelGGL((colsum_kernel<BF>), dim3(ceil_div(N, 32)), dim3(256), 0, s, g, ld_g, M, N, out);
+    });
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -226,10 +226,10 @@ inline int pad_keys(int n) { return (n + 255) / 256 * 256; }  // multiple of 256
 // top-k over the rows of a matrix the caller owns: the register lists hold 8 entries up to k = 8, 16 above
 template <bool SOFTMAX>
 static void launch_topk_rows(const float* m, int ld, int nrows, int K, int k, float* out_s, int64_t* out_i, hipStream_t s) {
-    if (k <= 8)
-        hipLaunchKernelGGL((topk_rows_kernel<8, SOFTMAX>), dim3(ceil_div(nrows, 4)), dim3(256), 0, s, m, ld, nrows, K, k, out_s, out_i, k);
-    else
-        hipLaunchKernelGGL((topk_rows_kernel<16, SOFTMAX>), dim3(ceil_div(nrows, 4)), dim3(256), 0, s, m, ld, nrows, K, k, out_s, out_i, k);
+    pick_bool(k <= 8, [&](auto small) {
+        hipLaunchKernelGGL((topk_rows_kernel<decltype(small)::value ? 8 : 16, SOFTMAX>), dim3(ceil_div(nrows, 4)), dim3(256), 0, s, m, ld,
+                           nrows, K, k, out_s, out_i, k);
+    });
 }
 
 extern "C" int64_t bsclip_topk_ip_workspace_floats(int Q, int K, int D) {
@@ -267,7 +267,7 @@ static int topk_check(const char* fn, const float* queries, const float* keys, i
     BSCLIP_REQUIRE(queries && keys && scores_out && idx_out && workspace, "%s: null pointer", fn);
     BSCLIP_REQUIRE(Q > 0 && K > 0 && D > 0 && D % 64 == 0, "%s: Q=%d K=%d D=%d (D %% 64 == 0)", fn, Q, K, D);
     BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= K, "%s: k=%d (1..16, <= K)", fn, k);
-    BSCLIP_REQUIRE(((((uintptr_t)workspace) | (indexed ? (uintptr_t)keys : 0)) & 15) == 0, "%s: %sworkspace must be 16-B aligned", fn,
+    BSCLIP_REQUIRE(aligned_to(16, workspace, indexed ? keys : nullptr), "%s: %sworkspace must be 16-B aligned", fn,
                    indexed ? "index and " : "");
     return BSCLIP_OK;
 }
@@ -297,7 +297,7 @@ extern "C" int64_t bsclip_retrieval_index_floats(int K, int D) {
 extern "C" int bsclip_retrieval_index_build(const float* keys, int K, int D, float* index, void* stream) {
     BSCLIP_REQUIRE(keys && index, "bsclip_retrieval_index_build: null pointer");
     BSCLIP_REQUIRE(K > 0 && D > 0 && D % 64 == 0, "bsclip_retrieval_index_build: K=%d D=%d (D %% 64 == 0)", K, D);
-    BSCLIP_REQUIRE((((uintptr_t)keys) & 15) == 0 && (((uintptr_t)index) & 15) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, keys, index),
                    "bsclip_retrieval_index_build: keys and index must be 16-B aligned");
     build_key_operand(keys, K, D, reinterpret_cast<bf16_t*>(index), stream);
     BSCLIP_LAUNCH_CHECK();
@@ -328,7 +328,7 @@ static int class_topk_checked(const char* fn, const float* logits, int ldc, int 
     BSCLIP_REQUIRE(B >= 1 && C >= 1, "%s: B=%d C=%d (both >= 1)", fn, B, C);
     BSCLIP_REQUIRE(k >= 1 && k <= 16 && k <= C, "%s: k=%d (1..16, <= C=%d)", fn, k, C);
     BSCLIP_REQUIRE(ldc >= C && ldc % 4 == 0, "%s: ldc=%d (>= C=%d, a multiple of 4)", fn, ldc, C);
-    BSCLIP_REQUIRE((((uintptr_t)logits) & 15) == 0 && (((uintptr_t)out_s) & 3) == 0 && (((uintptr_t)idx_out) & 7) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, logits) && aligned_to(4, out_s) && aligned_to(8, idx_out),
                    "%s: logits must be 16-byte, %s 4-byte, idx_out 8-byte aligned", fn, out_name);
     launch_topk_rows<SOFTMAX>(logits, ldc, B, C, k, out_s, idx_out, static_cast<hipStream_t>(stream));
     BSCLIP_LAUNCH_CHECK();
@@ -533,8 +533,7 @@ extern "C" int bsclip_retrieval_hit_ranks(const int64_t* idx, int Q, int k, cons
     BSCLIP_REQUIRE(Q > 0 && K > 0, "bsclip_retrieval_hit_ranks: Q=%d K=%d", Q, K);
     EVAL_REQUIRE_K("bsclip_retrieval_hit_ranks");
     EVAL_REQUIRE_L("bsclip_retrieval_hit_ranks");
-    BSCLIP_REQUIRE((((uintptr_t)idx) & 7) == 0 && ((((uintptr_t)key_labels) | ((uintptr_t)query_labels) | ((uintptr_t)hit_rank) |
-                                                    ((uintptr_t)flag)) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(8, idx) && aligned_to(4, key_labels, query_labels, hit_rank, flag),
                    "bsclip_retrieval_hit_ranks: idx must be 8-B aligned, the int32 buffers 4-B aligned");
     hipLaunchKernelGGL(hit_ranks_kernel, dim3(ceil_div(Q, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), idx, Q, k,
                        key_labels, K, query_labels, L, hit_rank, flag);
@@ -550,8 +549,8 @@ extern "C" int bsclip_retrieval_class_counts(const int32_t* hit_rank, const int3
     BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_class_counts: Q=%d", Q);
     EVAL_REQUIRE_L("bsclip_retrieval_class_counts");
     BSCLIP_REQUIRE(nk >= 1 && nk <= EVAL_MAX_K, "bsclip_retrieval_class_counts: nk=%d (1..%d)", nk, EVAL_MAX_K);
-    BSCLIP_REQUIRE(((((uintptr_t)hit_rank) | ((uintptr_t)query_labels) | ((uintptr_t)seen) | ((uintptr_t)right) | ((uintptr_t)flag)) &
-                    3) == 0, "bsclip_retrieval_class_counts: the int32 buffers must be 4-B aligned");
+    BSCLIP_REQUIRE(aligned_to(4, hit_rank, query_labels, seen, right, flag),
+                   "bsclip_retrieval_class_counts: the int32 buffers must be 4-B aligned");
     CountCfg cfg = {};
     BSCLIP_REQUIRE(level_offsets[0] == 0, "bsclip_retrieval_class_counts: level_offsets[0] must be 0");
     for (int l = 0; l <= L; ++l) {
@@ -587,8 +586,7 @@ extern "C" int bsclip_retrieval_match_bits(const int64_t* idx, int Q, int k, con
         BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_match_bits: level=%d (0 <= level < L=%d)", level, L);
         BSCLIP_REQUIRE(C > 0, "bsclip_retrieval_match_bits: C=%d member entries", C);
     }
-    BSCLIP_REQUIRE((((uintptr_t)idx) & 7) == 0 && ((((uintptr_t)key_labels) | ((uintptr_t)query_labels) | ((uintptr_t)member) |
-                                                    ((uintptr_t)bits) | ((uintptr_t)flag)) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(8, idx) && aligned_to(4, key_labels, query_labels, member, bits, flag),
                    "bsclip_retrieval_match_bits: idx must be 8-B aligned, the int32 buffers 4-B aligned");
     hipLaunchKernelGGL(match_bits_kernel, dim3(ceil_div(Q, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), idx, Q, k,
                        key_labels, K, query_labels, L, member, C, level, bits, flag);
@@ -602,7 +600,7 @@ extern "C" int bsclip_retrieval_merge_hit_ranks(const float* sim, int Q, int k, 
     BSCLIP_REQUIRE(Q > 0, "bsclip_retrieval_merge_hit_ranks: Q=%d", Q);
     EVAL_REQUIRE_K("bsclip_retrieval_merge_hit_ranks");
     EVAL_REQUIRE_L("bsclip_retrieval_merge_hit_ranks");
-    BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)hit_rank)) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(4, sim, A, B, hit_rank),
                    "bsclip_retrieval_merge_hit_ranks: sim and the int32 buffers must be 4-B aligned");
     hipLaunchKernelGGL(merge_hit_ranks_kernel, dim3(ceil_div(Q, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), sim, Q, k, A,
                        B, L, threshold, hit_rank);
@@ -618,8 +616,7 @@ extern "C" int bsclip_retrieval_threshold_sweep(const float* sim, int Q, int k, 
     EVAL_REQUIRE_L("bsclip_retrieval_threshold_sweep");
     BSCLIP_REQUIRE(level >= 0 && level < L, "bsclip_retrieval_threshold_sweep: level=%d (0 <= level < L=%d)", level, L);
     BSCLIP_REQUIRE(k_prime >= 1, "bsclip_retrieval_threshold_sweep: k_prime=%d (>= 1)", k_prime);
-    BSCLIP_REQUIRE(((((uintptr_t)sim) | ((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)counts)) & 3) == 0 &&
-                       (((uintptr_t)thresholds) & 7) == 0,
+    BSCLIP_REQUIRE(aligned_to(4, sim, A, B, counts) && aligned_to(8, thresholds),
                    "bsclip_retrieval_threshold_sweep: thresholds must be 8-B aligned, sim and the int32 buffers 4-B aligned");
     const int kk = k_prime < k ? k_prime : k;  // the contract is hit_rank < k_prime: above k it holds for every query
     hipLaunchKernelGGL(threshold_sweep_kernel, dim3(ceil_div(Q, 256), ceil_div(T, EVAL_SWEEP_CHUNK)), dim3(256), 0,

@@ -200,8 +200,7 @@ extern "C" int bsclip_silhouette_samples(const float* x_sorted, int ld, int N, i
     BSCLIP_REQUIRE(C >= 2 && C <= N - 1, "bsclip_silhouette_samples: C=%d (2 .. N - 1 = %d)", C, N - 1);
     BSCLIP_REQUIRE(D >= 1, "bsclip_silhouette_samples: D=%d (>= 1)", D);
     BSCLIP_REQUIRE(ld >= D && ld % 4 == 0, "bsclip_silhouette_samples: ld=%d (>= D=%d, a multiple of 4)", ld, D);
-    BSCLIP_REQUIRE((((uintptr_t)x_sorted) & 15) == 0 &&
-                       ((((uintptr_t)seg_start) | ((uintptr_t)out_sorted) | ((uintptr_t)flag)) & 3) == 0,
+    BSCLIP_REQUIRE(aligned_to(16, x_sorted) && aligned_to(4, seg_start, out_sorted, flag),
                    "bsclip_silhouette_samples: x_sorted must be 16-byte, seg_start, out_sorted and flag 4-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int check_blocks = ceil_div(C + 1, 256) < 64 ? ceil_div(C + 1, 256) : 64;

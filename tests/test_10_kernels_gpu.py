@@ -511,7 +511,11 @@ def test_lora_grad(ops, H):
 
 
 @pytest.mark.parametrize("B,S,heads,p,q_rows", [(3, 197, 12, 0.0, 0), (3, 133, 12, 0.1, 0), (2, 197, 12, 0.0, 1), (5, 20, 8, 0.1, 0),
-                                                (2, 64, 8, 0.0, 0), (9, 1, 12, 0.0, 0), (2, 224, 12, 0.1, 0), (2, 100, 8, 0.0, 40)])
+                                                (2, 64, 8, 0.0, 0), (9, 1, 12, 0.0, 0), (2, 224, 12, 0.1, 0), (2, 100, 8, 0.0, 40),
+                                                # the LoRA forms at the remaining block counts: keep words at NB = 2 .. 6 (5 = the
+                                                # generic form, not S = 133's), preloaded delta at NB = 3, 5, 6
+                                                (2, 40, 8, 0.1, 0), (1, 70, 8, 0.1, 0), (2, 70, 8, 0.0, 0), (1, 100, 8, 0.1, 0),
+                                                (1, 150, 8, 0.1, 0), (2, 150, 8, 0.0, 0), (1, 170, 8, 0.1, 0), (1, 170, 8, 0.0, 0)])
 def test_lora_grad_from_attention_partials(ops, B, S, heads, p, q_rows):
     """bsclip_attn_bwd_lora + bsclip_lora_grad_heads (round 5: dt and dB as MFMA products of dq / dv while they sit in the attention
     backward's accumulators, per head and per sequence, reduced in a fixed order) against bsclip_attn_bwd + bsclip_lora_grad, which read
@@ -580,6 +584,10 @@ def test_small_ops(ops):
     out = torch.zeros(36, device="cuda")
     ops.colsum(g3, 333, 36, out)
     assert rel_err(out, g3.sum(0)) < 1e-5
+    g3b = dev(rnd(333, 40, seed=5).bfloat16())[:, :36]   # the fallback on bf16
+    out = torch.zeros(36, device="cuda")
+    ops.colsum(g3b, 333, 36, out)
+    assert rel_err(out, g3b.float().sum(0)) < 1e-5
     big = dev(rnd(34048, 768, seed=6).bfloat16())
     o1, o2 = torch.zeros(768, device="cuda"), torch.zeros(768, device="cuda")
     ops.colsum(big, 34048, 768, o1)
@@ -685,12 +693,15 @@ def test_embed_grad_matches_autograd_and_is_ordered(ops, H, vocab, B, S, types):
     assert all(torch.equal(a, b) for a, b in zip(outs[0], outs[1]))
 
 
-@pytest.mark.parametrize("H", [768, 512])
-def test_ln_param_grad(ops, H):
+@pytest.mark.parametrize("H,xbf16", [pytest.param(768, False, id="768"), pytest.param(512, False, id="512"),
+                                     pytest.param(512, True, id="512-x16")])
+def test_ln_param_grad(ops, H, xbf16):
     """d_gamma / d_beta of a LayerNorm whose upstream gradient is assembled like layernorm_bwd assembles it (bf16 GEMM output +
     f32 residual gradient + the LoRA term dt . A)."""
     M = 777
     x = dev(rnd(M, H, seed=1) * 2 + 0.3)
+    if xbf16:   # the 16-bit stream: the kernel and the reference below see the same rounded x
+        x = x.bfloat16()
     gamma, beta = dev(rnd(H, seed=2) * 0.2 + 1), dev(rnd(H, seed=3) * 0.1)
     y, stats = torch.empty(M, H + 64, device="cuda", dtype=torch.bfloat16), torch.empty(M, 2, device="cuda")
     ops.layernorm_fwd(x, gamma, beta, 1e-6, y_bf16=y, stats=stats)
@@ -698,7 +709,8 @@ def test_ln_param_grad(ops, H):
     g_resid = dev(rnd(M, H, seed=5))
     dt, la = dev(rnd(M, 8, seed=6)), dev(rnd(8, H, seed=7) * 0.1)
     dy = g_gemm.float() + g_resid + dt @ la
-    xhat = (x - x.mean(1, keepdim=True)) / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + 1e-6)
+    xf = x.float()
+    xhat = (xf - xf.mean(1, keepdim=True)) / torch.sqrt(xf.var(1, unbiased=False, keepdim=True) + 1e-6)
     dg, db = dev(rnd(H, seed=8)), dev(rnd(H, seed=9))
     dg0, db0 = dg.clone(), db.clone()
     ops.ln_param_grad(x, stats, 1, dg, db, g_resid=g_resid, g_gemm=g_gemm, dt=dt, lora_a=la)
@@ -891,7 +903,10 @@ def test_exact_layernorm_bwd_f32_operands(ops):
 
 
 @pytest.mark.parametrize("B,S,heads,masked,drop", [(3, 197, 12, False, None), (2, 133, 12, False, (0.1, 99)), (5, 20, 8, True, (0.1, 7)),
-                                                   (2, 224, 2, True, None), (3, 1, 2, False, None)])
+                                                   (2, 224, 2, True, None), (3, 1, 2, False, None),
+                                                   # dropout at the block counts 2, 3, 4, 6, 7 (1 and 5 are above)
+                                                   (2, 40, 2, False, (0.1, 5)), (1, 70, 2, True, (0.1, 6)), (2, 100, 2, False, (0.1, 8)),
+                                                   (1, 170, 2, True, (0.1, 9)), (1, 200, 2, False, (0.1, 10))])
 def test_exact_attention_two_implementations_agree(ops, B, S, heads, masked, drop):
     """The exact-mode attention exists three times -- split-bf16 operands on the bf16 matrix cores (impl 0, the default since round 5),
     f32 operands on the matrix pipe (impl 2: v_mfma_f32_32x32x2_f32, transposed tiles) and one-row-per-thread vector-ALU kernels

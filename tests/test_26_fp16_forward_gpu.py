@@ -55,7 +55,8 @@ def _attn_ref(qkv, B, S, heads, scale, key_bias=None):
 
 
 @pytest.mark.parametrize("S,heads,q_rows,masked", [(197, 12, 0, False), (197, 12, 1, False), (133, 12, 0, False), (20, 8, 0, True),
-                                                   (100, 3, 0, True), (161, 2, 0, False)])   # 4 and 6 key blocks (generic forms)
+                                                   (100, 3, 0, True), (161, 2, 0, False),    # 4 and 6 key blocks (generic forms)
+                                                   (40, 2, 0, False), (70, 2, 0, True), (150, 2, 0, False), (200, 2, 0, True)])   # 2, 3, 5, 7
 def test_attention_forward_fp16(S, heads, q_rows, masked):
     from bioscanclip.hip import ops
     B, scale = 3, 0.125

@@ -111,7 +111,8 @@ def test_layernorm_fwd_dropout(ops):
 
 
 @pytest.mark.parametrize("B,S,heads,masked", [(2, 64, 2, False), (3, 20, 8, True), (2, 197, 3, False),
-                                              (2, 100, 2, False), (2, 161, 2, True)])   # 4 and 6 key blocks (generic forms)
+                                              (2, 100, 2, False), (2, 161, 2, True),    # 4 and 6 key blocks (generic forms)
+                                              (2, 70, 2, False), (2, 150, 2, False)])   # 3, and 5 in the generic form (not S = 133's)
 def test_attention_dropout_fwd_bwd(ops, B, S, heads, masked):
     H = heads * 64
     scale = 0.125
@@ -168,7 +169,7 @@ def test_attention_dropout_fwd_bwd(ops, B, S, heads, masked):
 
 @pytest.mark.parametrize("B,S,heads,masked", [(2, 64, 2, False), (3, 20, 8, True), (2, 133, 12, False), (2, 197, 3, False),
                                               (1, 224, 2, True), (3, 1, 2, False), (30, 133, 12, False),
-                                              (2, 100, 2, False), (2, 161, 2, True)])
+                                              (2, 100, 2, False), (2, 161, 2, True), (2, 70, 2, False), (1, 150, 2, True)])
 def test_attention_keep_bits_reproduce_the_hashed_masks(ops, B, S, heads, masked):
     """Round 5: the forward leaves its dropout decisions as bit words (64 B per query row) and the backward reads them instead of
     re-hashing every element.  Same decisions, same arithmetic: the forward output does not change, the gradients are bit for bit
