@@ -284,6 +284,10 @@ class NativeComm:
         """(event recorded now on the current stream = the payload's producer, event the collective records when done)."""
         ready, done = torch.cuda.Event(), torch.cuda.Event()
         ready.record(torch.cuda.current_stream(self.device))
+        # a torch event has no HIP event behind it until its first record (``cuda_event`` is 0): handed over like that, the library
+        # saw a null done_event, recorded nothing, and the consumer's ``wait_event(done)`` ordered nothing behind the collective.
+        # The record here creates it (on the communicator's stream, ahead of the collective); the library records it again after.
+        done.record(self.stream)
         return ready, done
 
     def _ev(self, e):

@@ -38,6 +38,14 @@ class Fp8Args(Structure):
         self.struct_size = ctypes.sizeof(Fp8Args)
 
 
+class JpegInfo(Structure):
+    """``bsclip_jpeg_info`` (include/bsclip.h)."""
+    _fields_ = [("width", c_int), ("height", c_int), ("components", c_int), ("h_samp", c_int), ("v_samp", c_int),
+                ("restart_interval", c_int), ("coef_count", c_int64), ("pixel_bytes", c_int64)]
+
+
+JPEG_REC = 16   # int32 per image record of bsclip_jpeg_entropy_decode / bsclip_jpeg_pixels
+
 P, I, F, L, U = c_void_p, c_int, c_float, c_int64, c_uint32
 
 # name -> (restype, argtypes); mirrors include/bsclip.h one to one (tests/test_00_abi.py checks both directions)
@@ -108,6 +116,10 @@ SIGNATURES = {
     "bsclip_allreduce_grads": (I, [P, P, L, P, P, P]),
     "bsclip_kmer_tokenize": (I, [P, P, I, I, I, P, P]),
     "bsclip_augment_images": (I, [P, P, I, L, P, I, P, P]),
+    "bsclip_jpeg_probe": (I, [P, L, P]),
+    "bsclip_jpeg_entropy_decode": (I, [P, L, P, L, P, P]),
+    "bsclip_jpeg_pixels_workspace_bytes": (L, [L]),
+    "bsclip_jpeg_pixels": (I, [P, L, P, I, P, P, I, P, L, P, L, P]),
     "bsclip_lora_grad_workspace_floats": (L, [I]),
     "bsclip_lora_grad": (I, [P, I, P, I, I, I, P, P, P, P, P, P, P]),
     "bsclip_lora_grad_heads": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P]),

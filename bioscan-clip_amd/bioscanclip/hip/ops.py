@@ -6,6 +6,7 @@ hand-written kernel can take the whole GPU down.  Nothing in this module compute
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import lib as _l
@@ -1081,6 +1082,63 @@ def augment_images(src, records, B, mid_capacity, mid, out_size, out):
     _req(mid.dtype == F32 and mid.is_cuda and mid.numel() >= 3 * B * mid_capacity, "augment_images: mid f32 [B,3,cap]")
     _req(out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (B, 3, out_size, out_size), "augment_images: out")
     check(_l.load().bsclip_augment_images(_p(src), _p(records), B, mid_capacity, _p(mid), out_size, _p(out), _stream()))
+
+
+# ------------------------------------------------------------------------------------------- JPEG shards
+class JpegRefused(ValueError):
+    """A stream the decoder does not take; ``code`` is the library's return code (include/bsclip.h BSCLIP_JPEG_ERR_*)."""
+
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+def _host_bytes(data):
+    """(address, length, keep-alive) of ``bytes`` / a C-contiguous uint8 NumPy array (a memory-mapped slice included)."""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(data, dtype=np.uint8)
+    _req(data.dtype.itemsize == 1 and data.flags["C_CONTIGUOUS"], "JPEG bytes: bytes or a contiguous uint8 array")
+    return ctypes.c_void_p(data.ctypes.data), data.size, data
+
+
+def jpeg_probe(data):
+    """Header of one JPEG stream (host only): a ``lib.JpegInfo``.  Raises ``JpegRefused`` naming the reason otherwise."""
+    ptr, n, _keep = _host_bytes(data)
+    info = _l.JpegInfo()
+    rc = _l.load().bsclip_jpeg_probe(ptr, n, ctypes.byref(info))
+    if rc != 0:
+        raise JpegRefused(_l.last_error(), rc)
+    return info
+
+
+def jpeg_entropy_decode(src_addr, n, coef_addr, coef_capacity, qtab_addr, record_addr):
+    """Huffman-decode one stream (host only, the GIL is released: loader threads call this side by side).  Plain addresses:
+    coefficients int16 [coef_capacity], tables uint16 [3, 64], record int32 [16].  Raises ``JpegRefused`` on a refused, truncated or
+    corrupt stream."""
+    rc = _l.load().bsclip_jpeg_entropy_decode(src_addr, n, coef_addr, coef_capacity, qtab_addr, record_addr)
+    if rc != 0:
+        raise JpegRefused(_l.last_error(), rc)
+
+
+def jpeg_pixels_workspace_bytes(coef_count):
+    return int(_l.load().bsclip_jpeg_pixels_workspace_bytes(int(coef_count)))
+
+
+def jpeg_pixels(coef, coef_count, qtab, records_host, records_dev, B, scratch, out):
+    """B entropy-decoded images -> uint8 HWC pixels at their records' offsets in ``out``.  ``records_host`` (CPU int32 [B, 16], pinned
+    for a copy that does not stall, unchanged until the stream has passed the call) is validated by the library, which then copies it
+    into ``records_dev`` (GPU int32 [B, 16], scratch) in stream order: the kernels read what was checked."""
+    _req(coef.dtype == torch.int16 and coef.is_cuda and coef.is_contiguous() and coef.numel() >= coef_count, "jpeg_pixels: coef int16")
+    _req(qtab.dtype == torch.int16 and qtab.is_cuda and qtab.is_contiguous() and qtab.numel() % 64 == 0,
+         "jpeg_pixels: qtab uint16 bits [slots, 64] held as int16")
+    _req(records_host.dtype == torch.int32 and not records_host.is_cuda and records_host.is_contiguous()
+         and records_host.numel() == _l.JPEG_REC * B, "jpeg_pixels: records_host CPU int32 [B,16]")
+    _req(records_dev.dtype == torch.int32 and records_dev.is_cuda and records_dev.is_contiguous()
+         and records_dev.numel() == _l.JPEG_REC * B, "jpeg_pixels: records_dev int32 [B,16]")
+    _req(scratch.dtype == torch.uint8 and scratch.is_cuda and scratch.is_contiguous(), "jpeg_pixels: scratch uint8")
+    _req(out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous(), "jpeg_pixels: out uint8")
+    check(_l.load().bsclip_jpeg_pixels(_p(coef), coef_count, _p(qtab), qtab.numel() // 64, _p(records_host), _p(records_dev), B,
+                                       _p(scratch), scratch.numel(), _p(out), out.numel(), _stream()))
 
 
 # ------------------------------------------------------------------------------------------- full fine-tuning (8f-4)

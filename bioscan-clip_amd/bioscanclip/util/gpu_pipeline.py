@@ -6,7 +6,7 @@
   171-200) for a batch of DECODED uint8 images (H x W x 3, sizes may differ): ToTensor, Resize(256, antialias),
   RandomResizedCrop(224, antialias) | CenterCrop(224), random flips, RandomRotation(+-45 deg) -> f32 [B, 3, 224, 224]
   (``bsclip_augment_images``).  The random draws are made here on the host from a seeded ``torch.Generator`` (a few scalars
-  per image), the arithmetic runs on the device.  JPEG decoding and the HDF5 reader stay outside.
+  per image), the arithmetic runs on the device.  JPEG decoding is the shard loader's (``util/shards.py``); the HDF5 reader stays outside.
 """
 import math
 import struct

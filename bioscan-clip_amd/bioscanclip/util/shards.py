@@ -5,8 +5,13 @@ worker.  h5py and a JPEG decoder are absent from this image, and at >= 6 k image
 starves the step, so the stored form here is what the GPU pipeline consumes directly -- one directory per split:
 
     meta.json                       {"format": "bsclip-shard", "version": 1, "n", "split", "dataset", "text_len"}
+                                    (+ "image_codec": "jpeg" in a JPEG shard; absent = raw)
     images.bin                      decoded uint8 H x W x 3 pixels of every sample, back to back
+                                    (JPEG shard: the samples' JPEG streams, back to back)
     image_index.npy                 int64 [n, 3]: byte offset into images.bin, H, W
+    image_bytes.npy                 int64 [n]: length of each stream (JPEG shards only)
+    image_coefs.npy                 int64 [n]: quantised coefficients each stream decodes to (JPEG shards only; lays a batch out
+                                    without parsing the streams first)
     barcodes.bin                    the nucleotide strings (ASCII), back to back      (HDF5 "barcode")
     barcode_offsets.npy             int64 [n + 1]
     language_tokens_input_ids.npy   int64 [n, text_len]                               (HDF5 datasets of the same names)
@@ -16,7 +21,13 @@ starves the step, so the stored form here is what the GPU pipeline consumes dire
     order.npy, family.npy, genus.npy, species.npy   bytes [n]  (get_array_of_label_dicts, dataset.py:51-62: evaluation labels)
 
 Every array is memory-mapped; nothing is loaded whole.  ``convert_hdf5_split`` writes this layout from the reference's HDF5 file
-wherever h5py and PIL exist (not in this image: documented, exercised by nothing here).
+wherever h5py exists (not in this image: documented, exercised by nothing here).
+
+A JPEG shard (``image_codec="jpeg"``) keeps the dataset's own bytes -- several times smaller than decoded pixels -- and
+the loader decodes them without a CPU pixel path: loader threads Huffman-decode each stream into quantised coefficients
+(``bsclip_jpeg_entropy_decode``, host only, the GIL released), the device does the arithmetic (``bsclip_jpeg_pixels``) straight
+into the uint8 staging buffer the augmentation kernels read.  Only streams the decoder takes are ever written: baseline, 8-bit,
+grey or YCbCr 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, one scan.
 
 ``ShardLoader`` yields the reference's 7-tuple ``(processid, image, dna, input_ids, token_type_ids, attention_mask, label)``
 (dataset.py:267-275) with ``image`` f32 [B, 3, 224, 224] and ``dna`` int64 [B, 133] already on the device:
@@ -38,30 +49,56 @@ import numpy as np
 import torch
 
 FORMAT, VERSION = "bsclip-shard", 1
+CODECS = ("raw", "jpeg")
+MAX_DECODE_THREADS = 16
 _TAXA = ("order", "family", "genus", "species")
 _TEXT = ("language_tokens_input_ids", "language_tokens_token_type_ids", "language_tokens_attention_mask")
 
 
 def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mask, processid, labels=None, taxonomy=None,
-                split="train", dataset="bioscan_1m"):
+                split="train", dataset="bioscan_1m", image_codec="raw"):
     """images: sequence of uint8 [H, W, 3] arrays (sizes may differ); barcodes: sequence of str; the three text arrays
     int [n, text_len]; processid: sequence of str; labels: int [n] (default: the sample index, dataset.py:139);
-    taxonomy: dict order/family/genus/species -> sequence of str (default: empty strings)."""
+    taxonomy: dict order/family/genus/species -> sequence of str (default: empty strings).
+    ``image_codec="jpeg"``: images is a sequence of ``bytes``, each a JPEG stream, stored as it is.  Every stream is probed AND
+    entropy-decoded here (host only), so a shard never holds one the loader's decoder refuses or finds damaged: every stream is
+    looked at, then ValueError names the first ten offenders and their reasons."""
+    if image_codec not in CODECS:
+        raise ValueError(f"image_codec must be one of {CODECS}, got {image_codec!r}")
     os.makedirs(path, exist_ok=True)
     n = len(barcodes)
     assert len(processid) == n and len(input_ids) == n
     index = np.zeros((n, 3), dtype=np.int64)
+    nbytes, ncoefs, refused = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), []
     off, seen = 0, 0
     with open(os.path.join(path, "images.bin"), "wb") as f:
         for i, im in enumerate(images):                       # any iterable: images are streamed to disk one at a time
+            if image_codec == "jpeg":
+                seen += 1
+                try:
+                    h, w, ncoefs[i] = _check_jpeg(im, i)
+                except ValueError as exc:
+                    refused.append(str(exc))
+                    continue
+                if not refused:               # after a refusal the rest is only checked, to name more than the first offender
+                    index[i] = (off, h, w)
+                    nbytes[i] = len(im)
+                    f.write(im)
+                    off += len(im)
+                continue
             im = np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
             assert im.ndim == 3 and im.shape[2] == 3, "images must be decoded uint8 H x W x 3"
             index[i] = (off, im.shape[0], im.shape[1])
             f.write(im.tobytes())
             off += im.size
             seen += 1
+    if refused:
+        raise ValueError(f"{len(refused)} of {seen} streams cannot go into a JPEG shard: " + "; ".join(refused[:10]))
     assert seen == n, f"{seen} images for {n} barcodes"
     np.save(os.path.join(path, "image_index.npy"), index)
+    if image_codec == "jpeg":
+        np.save(os.path.join(path, "image_bytes.npy"), nbytes)
+        np.save(os.path.join(path, "image_coefs.npy"), ncoefs)
     offs = np.zeros(n + 1, dtype=np.int64)
     with open(os.path.join(path, "barcodes.bin"), "wb") as f:
         for i, s in enumerate(barcodes):
@@ -76,9 +113,28 @@ def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mas
     for t in _TAXA:
         vals = [""] * n if taxonomy is None else list(taxonomy[t])
         np.save(os.path.join(path, t + ".npy"), np.asarray([str(v).encode() for v in vals], dtype=np.bytes_))
+    meta = {"format": FORMAT, "version": VERSION, "n": n, "split": split, "dataset": dataset,
+            "text_len": int(np.asarray(input_ids).reshape(n, -1).shape[1])}
+    if image_codec != "raw":       # absent = raw: shards written before the codec existed, and raw ones since, read the same
+        meta["image_codec"] = image_codec
     with open(os.path.join(path, "meta.json"), "w") as f:
-        json.dump({"format": FORMAT, "version": VERSION, "n": n, "split": split, "dataset": dataset,
-                   "text_len": int(np.asarray(input_ids).reshape(n, -1).shape[1])}, f)
+        json.dump(meta, f)
+
+
+def _check_jpeg(data, i):
+    """(H, W, coefficient count) of one JPEG stream that the loader will be able to decode; ValueError otherwise."""
+    from bioscanclip.hip import ops
+    if not isinstance(data, (bytes, bytearray)):
+        raise ValueError(f"image {i}: image_codec='jpeg' takes the JPEG stream as bytes, got {type(data).__name__}")
+    try:
+        info = ops.jpeg_probe(data)
+        coef = np.empty(int(info.coef_count), dtype=np.int16)
+        qtab, rec = np.empty(192, dtype=np.uint16), np.empty(16, dtype=np.int32)
+        src = np.frombuffer(data, dtype=np.uint8)
+        ops.jpeg_entropy_decode(src.ctypes.data, src.size, coef.ctypes.data, coef.size, qtab.ctypes.data, rec.ctypes.data)
+    except ops.JpegRefused as exc:
+        raise ValueError(f"image {i}: {exc} (code {exc.code}); re-encode it as baseline JPEG or write a raw shard") from exc
+    return int(info.height), int(info.width), int(info.coef_count)
 
 
 def is_shard(path):
@@ -94,6 +150,9 @@ class Shard:
         if self.meta.get("format") != FORMAT or self.meta.get("version") != VERSION:
             raise ValueError(f"{path}: not a {FORMAT} v{VERSION} directory (meta.json says {self.meta})")
         self.path, self.n = path, int(self.meta["n"])
+        self.image_codec = self.meta.get("image_codec", "raw")
+        if self.image_codec not in CODECS:
+            raise ValueError(f"{path}: unknown image_codec {self.image_codec!r}")
         ld = lambda name: np.load(os.path.join(path, name + ".npy"), mmap_mode="r")
         self.image_index = ld("image_index")
         self.images = np.memmap(os.path.join(path, "images.bin"), dtype=np.uint8, mode="r")
@@ -102,6 +161,10 @@ class Shard:
         self.input_ids, self.token_type_ids, self.attention_mask = (ld(t) for t in _TEXT)
         self.processid, self.labels = ld("processid"), ld("labels")
         self.taxonomy = {t: ld(t) for t in _TAXA}
+        self.image_nbytes = ld("image_bytes") if self.image_codec == "jpeg" else None
+        self.image_ncoefs = ld("image_coefs") if self.image_codec == "jpeg" else None
+        if self.image_nbytes is not None and len(self.image_nbytes) != self.n:
+            raise ValueError(f"{path}: image_bytes.npy has {len(self.image_nbytes)} rows for n={self.n}")
         if not (len(self.image_index) == len(self.labels) == len(self.processid) == self.n and len(self.barcode_offsets) == self.n + 1):
             raise ValueError(f"{path}: array lengths disagree with meta.json n={self.n}")
 
@@ -109,8 +172,18 @@ class Shard:
         return self.n
 
     def image(self, i):
+        if self.image_codec != "raw":
+            raise RuntimeError(f"{self.path}: a {self.image_codec} shard has no CPU decode path; read it through ShardLoader (the GPU "
+                               "decodes), or take the stored stream with image_bytes(i)")
         off, h, w = (int(v) for v in self.image_index[i])
         return self.images[off:off + h * w * 3].reshape(h, w, 3)
+
+    def image_bytes(self, i):
+        """The stored JPEG stream of sample i (JPEG shards only)."""
+        if self.image_codec != "jpeg":
+            raise RuntimeError(f"{self.path}: a raw shard stores decoded pixels, not streams; use image(i)")
+        off = int(self.image_index[i][0])
+        return bytes(self.images[off:off + int(self.image_nbytes[i])])
 
     def barcode(self, i):
         return bytes(self.barcodes[int(self.barcode_offsets[i]):int(self.barcode_offsets[i + 1])]).decode("ascii")
@@ -147,9 +220,17 @@ class ShardLoader:
     SLOTS = 3
 
     def __init__(self, shard, batch_size, rank=0, world_size=1, shuffle=False, seed=0, for_training=True, with_text=True,
-                 device="cuda", augment_seed=None):
+                 device="cuda", augment_seed=None, decode_threads=4):
+        """``decode_threads`` (1..16, JPEG shards only): loader threads that entropy-decode a batch side by side."""
         from bioscanclip.util.gpu_pipeline import GpuAugment
         self.shard = Shard(shard) if isinstance(shard, str) else shard
+        self.decode_threads = int(decode_threads)
+        if not 1 <= self.decode_threads <= MAX_DECODE_THREADS:   # a fixed bound, never the machine's CPU count: the box is shared
+            raise ValueError(f"decode_threads must be in 1..{MAX_DECODE_THREADS}, got {decode_threads}")
+        self._pool = None
+        if self.shard.image_codec == "jpeg" and self.decode_threads > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix="bsclip-jpeg")
         self.batch_size, self.rank, self.world_size = int(batch_size), rank, world_size
         self.shuffle, self.seed, self.epoch = shuffle, seed, 0
         self.for_training, self.with_text, self.device = for_training, with_text, torch.device(device)
@@ -181,10 +262,12 @@ class ShardLoader:
         rows = sh.image_index[np.asarray(idx)]
         nbytes = int((rows[:, 1] * rows[:, 2]).sum()) * 3
         dna_len = int(sum(int(sh.barcode_offsets[i + 1] - sh.barcode_offsets[i]) for i in idx))
+        jpeg = sh.image_codec == "jpeg"
         if slot["cap_img"] < nbytes:
             slot["cap_img"] = int(nbytes * 1.25) + 4096
-            slot["img_host"] = torch.empty(slot["cap_img"], dtype=torch.uint8).pin_memory()
-            with torch.cuda.stream(self.stream):    # the staging buffer belongs to the stream that writes and reads it: a block
+            if not jpeg:                            # a JPEG batch reaches the device as coefficients (_stage_jpeg), not as pixels
+                slot["img_host"] = torch.empty(slot["cap_img"], dtype=torch.uint8).pin_memory()
+            with torch.cuda.stream(self.stream):   # the staging buffer belongs to the stream that writes and reads it: a block
                 # of the default stream's pool could still be in use by queued kernels of the training step
                 slot["img_dev"] = torch.empty(slot["cap_img"], dtype=torch.uint8, device=self.device)
         if slot["cap_dna"] < dna_len + 1:
@@ -192,11 +275,13 @@ class ShardLoader:
             slot["dna_host"] = torch.empty(slot["cap_dna"], dtype=torch.uint8).pin_memory()
             with torch.cuda.stream(self.stream):
                 slot["dna_dev"] = torch.empty(slot["cap_dna"], dtype=torch.uint8, device=self.device)
-        img_np, dna_np = slot["img_host"].numpy(), slot["dna_host"].numpy()
+        dna_np = slot["dna_host"].numpy()
+        img_np = None if jpeg else slot["img_host"].numpy()
         sizes, off, doffs = [], 0, [0]
         for (o, h, w), i in zip(rows, idx):
             nb = int(h) * int(w) * 3
-            img_np[off:off + nb] = sh.images[int(o):int(o) + nb]
+            if not jpeg:
+                img_np[off:off + nb] = sh.images[int(o):int(o) + nb]
             off += nb
             sizes.append((int(h), int(w)))
             b0, b1 = int(sh.barcode_offsets[i]), int(sh.barcode_offsets[i + 1])
@@ -227,14 +312,64 @@ class ShardLoader:
                 t = mh[base + k * self.batch_size * T:base + k * self.batch_size * T + B * T].view(B, T)
                 t.copy_(torch.from_numpy(np.ascontiguousarray(a[sel])))
                 host["text"].append(t)
+        if jpeg:
+            host["ncoef"] = self._stage_jpeg(slot, idx, rows)
         return host
+
+    def _stage_jpeg(self, slot, idx, rows):
+        """Entropy-decode the batch's streams into the slot's pinned coefficient buffer, tables and records (the serial part of a
+        JPEG decode, ``decode_threads`` streams at a time; the GIL is released inside the library).  Returns the coefficient count."""
+        from bioscanclip.hip import ops
+        sh, B = self.shard, len(idx)
+        spans = [(int(rows[k][0]), int(sh.image_nbytes[i])) for k, i in enumerate(idx)]
+        chunks = [range(t, B, self.decode_threads) for t in range(min(self.decode_threads, B))]
+        run = (lambda fn: list(self._pool.map(fn, chunks))) if self._pool is not None else (lambda fn: [fn(c) for c in chunks])
+        counts = np.asarray(sh.image_ncoefs[np.asarray(idx)], dtype=np.int64)    # written with the shard: no parse before the decode
+        coef_off = np.concatenate([[0], np.cumsum(counts)])       # every count is a multiple of 64: so is every offset
+        ncoef = int(coef_off[-1])
+        if slot.get("cap_coef", 0) < ncoef:
+            slot["cap_coef"] = int(ncoef * 1.25) + 4096
+            slot["coef_host"] = torch.empty(slot["cap_coef"], dtype=torch.int16).pin_memory()
+            with torch.cuda.stream(self.stream):
+                slot["coef_dev"] = torch.empty(slot["cap_coef"], dtype=torch.int16, device=self.device)
+                slot["planes_dev"] = torch.empty(ops.jpeg_pixels_workspace_bytes(slot["cap_coef"]), dtype=torch.uint8, device=self.device)
+        if "rec_host" not in slot:     # allocated once per slot, like meta_host
+            slot["rec_host"] = torch.empty((self.batch_size, 16), dtype=torch.int32).pin_memory()
+            slot["qtab_host"] = torch.empty((self.batch_size * 3, 64), dtype=torch.int16).pin_memory()
+        base = sh.images.ctypes.data
+        coef_p, rec_p, qtab_p = slot["coef_host"].data_ptr(), slot["rec_host"].data_ptr(), slot["qtab_host"].data_ptr()
+
+        def decode(chunk):   # pass 2: each image into its own range of the pinned buffers
+            for k in chunk:
+                o, n = spans[k]
+                try:
+                    ops.jpeg_entropy_decode(base + o, n, coef_p + 2 * int(coef_off[k]), int(counts[k]), qtab_p + 384 * k, rec_p + 64 * k)
+                except ops.JpegRefused as exc:
+                    raise RuntimeError(f"{sh.path}: sample {idx[k]}: {exc}") from exc
+        run(decode)
+        rec = slot["rec_host"].numpy()[:B]
+        if not (np.array_equal(rec[:, 5], rows[:, 1]) and np.array_equal(rec[:, 4], rows[:, 2])):
+            raise RuntimeError(f"{sh.path}: image_index.npy disagrees with the streams' own sizes (samples {list(idx)})")
+        pix_off = np.concatenate([[0], np.cumsum(rows[:, 1] * rows[:, 2] * 3)])[:B]
+        for col, v in ((0, coef_off[:B]), (2, pix_off)):          # the batch fields of the records: 64-bit offsets as two int32
+            rec[:, col] = (v & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+            rec[:, col + 1] = (v >> 32).astype(np.int32)
+        rec[:, 9:12] += 3 * np.arange(B, dtype=np.int32)[:, None]   # image k's tables are slots 3k .. 3k + 2
+        return ncoef
 
     def _enqueue(self, slot, host):
         """Device half, on the loader's side stream: H2D copies + the two transforms; records the slot's ready event."""
         from bioscanclip.hip import ops
         B = len(host["sizes"])
         with torch.cuda.stream(self.stream):
-            slot["img_dev"][:host["nbytes"]].copy_(slot["img_host"][:host["nbytes"]], non_blocking=True)
+            if "ncoef" in host:      # JPEG shard: coefficients, tables and records go up, the pixels are made in img_dev
+                n = host["ncoef"]
+                slot["coef_dev"][:n].copy_(slot["coef_host"][:n], non_blocking=True)
+                qtab_dev = slot["qtab_host"][:3 * B].to(self.device, non_blocking=True)
+                rec_dev = torch.empty((B, 16), dtype=torch.int32, device=self.device)    # filled by the library from rec_host
+                ops.jpeg_pixels(slot["coef_dev"], n, qtab_dev, slot["rec_host"][:B], rec_dev, B, slot["planes_dev"], slot["img_dev"])
+            else:
+                slot["img_dev"][:host["nbytes"]].copy_(slot["img_host"][:host["nbytes"]], non_blocking=True)
             n_dna = host["n_dna"]
             slot["dna_dev"][:max(n_dna, 1)].copy_(slot["dna_host"][:max(n_dna, 1)], non_blocking=True)
             off_dev = host["dna_offsets"].to(self.device, non_blocking=True)
@@ -292,26 +427,57 @@ class ShardLoader:
             yield (out["processid"], out["image"], out["dna"], out["text"][0], out["text"][1], out["text"][2], out["label"])
         th.join()
 
+    def __del__(self):
+        pool = getattr(self, "_pool", None)
+        if pool is not None:
+            pool.shutdown(wait=False)
 
-def convert_hdf5_split(hdf5_path, split, out_dir, dataset="bioscan_1m", labels=None):
+
+def convert_hdf5_split(hdf5_path, split, out_dir, dataset="bioscan_1m", labels=None, image_codec="raw", reencode=False):
     """Write one split of the reference's HDF5 file (DATA.md:23-35; datasets image / image_mask / barcode /
     language_tokens_* / processid | image_file / order / family / genus / species, read as ``Dataset_for_CL`` reads them,
-    dataset.py:219-265) as a shard directory.  Needs h5py and PIL, which this image does not have: run it where the data lives."""
+    dataset.py:219-265) as a shard directory.  Needs h5py, which this image does not have: run it where the data lives.
+    ``image_codec="raw"`` decodes every image with Pillow; ``"jpeg"`` copies the stored streams (no Pillow) after checking that the
+    loader's decoder takes each one.  Streams it does not take raise (``write_shard`` names the first ten) -- or, with ``reencode=True``, are
+    re-encoded through Pillow as baseline 4:4:4 quality 95 and counted in meta.json ("reencoded")."""
     try:
         import io
         import h5py
-        from PIL import Image
-    except ImportError as exc:   # pragma: no cover - neither package exists in this image
-        raise ImportError("convert_hdf5_split needs h5py and Pillow (absent from the build image); run it on the data host") from exc
+    except ImportError as exc:   # pragma: no cover - the package does not exist in this image
+        raise ImportError("convert_hdf5_split needs h5py (absent from the build image); run it on the data host") from exc
     g = h5py.File(hdf5_path, "r", libver="latest")[split]                     # pragma: no cover
     n = len(g["barcode"])                                                     # pragma: no cover
     pid_key = "processid" if dataset == "bioscan_5m" else "image_file"        # pragma: no cover
+    stream = lambda i: g["image"][i].astype(np.uint8)[:g["image_mask"][i]].tobytes()   # pragma: no cover
+    extra = {"reencoded": 0}                                                                # pragma: no cover
 
-    def images():                                                             # pragma: no cover
+    def pixels():                                                             # pragma: no cover
+        from PIL import Image
         for i in range(n):
-            enc = g["image"][i].astype(np.uint8)[:g["image_mask"][i]]
-            yield np.asarray(Image.open(io.BytesIO(enc.tobytes())).convert("RGB"), dtype=np.uint8)
-    write_shard(out_dir, images(), [b.decode("utf-8") for b in g["barcode"][:]],                         # pragma: no cover
+            yield np.asarray(Image.open(io.BytesIO(stream(i))).convert("RGB"), dtype=np.uint8)
+
+    def streams():                                                            # pragma: no cover
+        for i in range(n):
+            data = stream(i)
+            try:
+                _check_jpeg(data, i)
+            except ValueError:
+                from PIL import Image
+                buf = io.BytesIO()
+                Image.open(io.BytesIO(data)).convert("RGB").save(buf, format="JPEG", quality=95, subsampling="4:4:4")
+                data = buf.getvalue()
+                extra["reencoded"] += 1
+            yield data
+
+    images = pixels() if image_codec == "raw" else (stream(i) for i in range(n)) if not reencode else streams()   # pragma: no cover
+    write_shard(out_dir, images, [b.decode("utf-8") for b in g["barcode"][:]],                           # pragma: no cover
                 g["language_tokens_input_ids"][:], g["language_tokens_token_type_ids"][:], g["language_tokens_attention_mask"][:],
                 [p.decode("utf-8") for p in g[pid_key][:]], labels=labels,
-                taxonomy={t: [v.decode("utf-8") for v in g[t][:]] for t in _TAXA}, split=split, dataset=dataset)
+                taxonomy={t: [v.decode("utf-8") for v in g[t][:]] for t in _TAXA}, split=split, dataset=dataset,
+                image_codec=image_codec)
+    if image_codec == "jpeg" and reencode:                                    # pragma: no cover
+        with open(os.path.join(out_dir, "meta.json")) as f:
+            meta = json.load(f)
+        meta.update(extra)
+        with open(os.path.join(out_dir, "meta.json"), "w") as f:
+            json.dump(meta, f)

@@ -537,6 +537,49 @@ int bsclip_kmer_tokenize(const void* seqs, const int64_t* offsets, int B, int ma
 int bsclip_augment_images(const void* src_u8, const int32_t* records, int B, int64_t mid_capacity, float* mid, int out_size,
                           float* out, void* stream);
 
+/* ---- JPEG shards: entropy decode on the host, pixels on the GPU -----------------------------------------
+ * The reference stores JPEG bytes in its HDF5 file and decodes one per __getitem__ (bioscanclip/util/dataset.py:220-223,
+ * Image.open(io.BytesIO(...)).convert("RGB")).  Here the serial part (markers + Huffman decoding) runs on loader threads and the
+ * arithmetic (dequantise, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB; libjpeg's integer defaults) runs on the device.
+ * Decoded: baseline SOF0, 8-bit, grey or YCbCr with luma sampling 1 or 2 per axis and chroma 1x1, one scan, restart intervals,
+ * up to 4096 x 4096.  Anything else is refused with one of the codes below (never decoded in part); a truncated or corrupt
+ * entropy stream is an error too (nothing is zero-filled).
+ * jpeg_probe and jpeg_entropy_decode are HOST functions (host pointers, no device call, no allocation, no globals: callable
+ *   from any number of threads at once; the error text is the calling thread's, like every bsclip_last_error).
+ *   entropy_decode writes coef_out (int16, natural order, 64 per block; per component a block raster padded to whole MCUs:
+ *   info.coef_count elements), qtab_out (uint16 [3][64], one table per component) and record_out (int32 [16]):
+ *     {coef offset lo, hi (int16 elements, a multiple of 64), out offset lo, hi (bytes), W, H, components, luma h, luma v,
+ *      table slot of component 0, 1, 2, blocks (= coefficients / 64), restart interval, 0, 0}
+ *   with both offsets zero and slots 0, 1, 2: the caller places the image in its batch by setting them.
+ * jpeg_pixels: B images in one launch sequence.  coef_dev int16 [coef_count], qtab_dev uint16 [qtab_slots][64], scratch
+ *   >= bsclip_jpeg_pixels_workspace_bytes(coef_count) bytes, out_u8 [out_capacity]: image b's H x W x 3 bytes at its out offset.
+ *   records_host: the B records in HOST memory (pinned for a copy that does not stall; they must stay unchanged until the stream
+ *   has passed this call).  They are validated before anything is launched (sizes against the block count, every range against
+ *   coef_count / out_capacity / qtab_slots); then the library copies them to records_dev (device int32 [B][16], the caller's
+ *   scratch) on `stream` itself, so the kernels read exactly what was checked -- the one entry point that reads host memory.
+ *   coef_dev, qtab_dev, scratch, out_u8 16-byte aligned.  Images must not overlap (not checked). */
+#define BSCLIP_JPEG_ERR_TRUNCATED (-10)
+#define BSCLIP_JPEG_ERR_CORRUPT (-11)
+#define BSCLIP_JPEG_ERR_SOF (-12)           /* extended / progressive / lossless / arithmetic / 12-bit */
+#define BSCLIP_JPEG_ERR_COMPONENTS (-13)    /* not 1 or 3 */
+#define BSCLIP_JPEG_ERR_SAMPLING (-14)
+#define BSCLIP_JPEG_ERR_MULTISCAN (-15)
+#define BSCLIP_JPEG_ERR_MISSING_TABLE (-16)
+#define BSCLIP_JPEG_ERR_SIZE (-17)
+#define BSCLIP_JPEG_ERR_COLORSPACE (-18)    /* three components that are RGB */
+typedef struct bsclip_jpeg_info {
+    int32_t width, height, components, h_samp, v_samp, restart_interval;
+    int64_t coef_count;   /* int16 coefficients = bytes of scratch */
+    int64_t pixel_bytes;  /* width * height * 3 */
+} bsclip_jpeg_info;
+int bsclip_jpeg_probe(const void* host_bytes, int64_t n, bsclip_jpeg_info* info_out);
+int bsclip_jpeg_entropy_decode(const void* host_bytes, int64_t n, int16_t* host_coef_out, int64_t coef_capacity,
+                               uint16_t* host_qtab_out, int32_t* host_record_out);
+int64_t bsclip_jpeg_pixels_workspace_bytes(int64_t coef_count);
+int bsclip_jpeg_pixels(const int16_t* coef_dev, int64_t coef_count, const uint16_t* qtab_dev, int qtab_slots,
+                       const int32_t* records_host, int32_t* records_dev, int B, void* scratch, int64_t scratch_bytes,
+                       void* out_u8, int64_t out_capacity, void* stream);
+
 /* ---- LoRA / head gradients -------------------------------------------------------------------------------------
  * lora_grad: for one layer, from dqkv (bf16 [M, ld_dqkv], q cols [0,H), v cols [2H,3H)) and the augmented LN
  *   output h (bf16 [M, ld_h]: cols [0,H) = y, [H,H+4) = t_q, [H+4,H+8) = t_v):
