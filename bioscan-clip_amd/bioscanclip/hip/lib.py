@@ -45,6 +45,9 @@ class JpegInfo(Structure):
 
 
 JPEG_REC = 16   # int32 per image record of bsclip_jpeg_entropy_decode / bsclip_jpeg_pixels
+JPEG_SEG_REC = 8          # int32 per image of bsclip_jpeg_entropy_device's segments_host
+JPEG_SYNC_ENTRY = 4       # int32 per sync-index entry
+JPEG_HUFF_BYTES = 1420    # BSCLIP_JPEG_HUFF_BYTES: one device-ready Huffman table; an image has four
 
 P, I, F, L, U = c_void_p, c_int, c_float, c_int64, c_uint32
 
@@ -120,6 +123,9 @@ SIGNATURES = {
     "bsclip_jpeg_entropy_decode": (I, [P, L, P, L, P, P]),
     "bsclip_jpeg_pixels_workspace_bytes": (L, [L]),
     "bsclip_jpeg_pixels": (I, [P, L, P, I, P, P, I, P, L, P, L, P]),
+    "bsclip_jpeg_sync_index": (L, [P, L, I, P, L]),
+    "bsclip_jpeg_device_tables": (I, [P, L, P, P, P]),
+    "bsclip_jpeg_entropy_device": (I, [P, L, P, L, P, I, P, P, P, P, I, P, L, P, P]),
     "bsclip_lora_grad_workspace_floats": (L, [I]),
     "bsclip_lora_grad": (I, [P, I, P, I, I, I, P, P, P, P, P, P, P]),
     "bsclip_lora_grad_heads": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P]),

@@ -1141,6 +1141,49 @@ def jpeg_pixels(coef, coef_count, qtab, records_host, records_dev, B, scratch, o
                                        _p(scratch), scratch.numel(), _p(out), out.numel(), _stream()))
 
 
+def jpeg_sync_index(data, sync_mcus):
+    """The sync index of one stream (host only): int32 [entries, 4] = bit position, first MCU, Y predictor, Cb | Cr << 16 (see
+    include/bsclip.h).  Raises ``JpegRefused`` on whatever the entropy decoder refuses, and on ``sync_mcus < 1``."""
+    ptr, n, _keep = _host_bytes(data)
+    h = _l.load()
+    count = h.bsclip_jpeg_sync_index(ptr, n, int(sync_mcus), None, 0)
+    if count < 0:
+        raise JpegRefused(_l.last_error(), int(count))
+    out = np.empty((int(count), _l.JPEG_SYNC_ENTRY), dtype=np.int32)
+    rc = h.bsclip_jpeg_sync_index(ptr, n, int(sync_mcus), out.ctypes.data, int(count))
+    if rc != count:
+        raise JpegRefused(_l.last_error(), int(rc))
+    return out
+
+
+def jpeg_device_tables(src_addr, n, huff_addr, qtab_addr, record_addr):
+    """Parse one stream's headers (host only; plain addresses, like ``jpeg_entropy_decode``): four device-ready Huffman tables
+    (``lib.JPEG_HUFF_BYTES`` each), quantisation tables uint16 [3, 64], record int32 [16].  Raises ``JpegRefused``."""
+    rc = _l.load().bsclip_jpeg_device_tables(src_addr, n, huff_addr, qtab_addr, record_addr)
+    if rc != 0:
+        raise JpegRefused(_l.last_error(), rc)
+
+
+def jpeg_entropy_device(stream_bytes, sync, huff, records_host, segments_host, records_dev, segments_dev, B, coef, coef_count, status):
+    """Huffman-decode B stored streams on the device, one lane per index segment, into the coefficient raster ``jpeg_pixels`` reads.
+    ``records_host`` / ``segments_host`` (CPU int32 [B, 16] / [B, 8], unchanged until the stream has passed the call) are validated by
+    the library, which then copies them into ``records_dev`` / ``segments_dev`` and zeroes ``status`` (int32 [B]) in stream order;
+    afterwards ``status[b] != 0`` means image b's bytes or index are damaged."""
+    _req(stream_bytes.dtype == torch.uint8 and stream_bytes.is_cuda and stream_bytes.is_contiguous(), "jpeg_entropy_device: bytes uint8")
+    _req(sync.dtype == torch.int32 and sync.is_cuda and sync.is_contiguous() and sync.numel() % _l.JPEG_SYNC_ENTRY == 0,
+         "jpeg_entropy_device: sync int32 [entries, 4]")
+    _req(huff.dtype == torch.uint8 and huff.is_cuda and huff.is_contiguous() and huff.numel() % (4 * _l.JPEG_HUFF_BYTES) == 0,
+         "jpeg_entropy_device: huff uint8 [slots, 4 * JPEG_HUFF_BYTES]")
+    for t, w, nm in ((records_host, _l.JPEG_REC, "records"), (segments_host, _l.JPEG_SEG_REC, "segments")):
+        _req(t.dtype == torch.int32 and not t.is_cuda and t.is_contiguous() and t.numel() == w * B, f"jpeg_entropy_device: {nm}_host CPU int32 [B,{w}]")
+    for t, w, nm in ((records_dev, _l.JPEG_REC, "records"), (segments_dev, _l.JPEG_SEG_REC, "segments"), (status, 1, "status")):
+        _req(t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == w * B, f"jpeg_entropy_device: {nm} GPU int32 [B,{w}]")
+    _req(coef.dtype == torch.int16 and coef.is_cuda and coef.is_contiguous() and coef.numel() >= coef_count, "jpeg_entropy_device: coef int16")
+    check(_l.load().bsclip_jpeg_entropy_device(_p(stream_bytes), stream_bytes.numel(), _p(sync), sync.numel() // _l.JPEG_SYNC_ENTRY, _p(huff),
+                                               huff.numel() // (4 * _l.JPEG_HUFF_BYTES), _p(records_host), _p(segments_host), _p(records_dev),
+                                               _p(segments_dev), B, _p(coef), coef_count, _p(status), _stream()))
+
+
 # ------------------------------------------------------------------------------------------- full fine-tuning (8f-4)
 def ln_param_grad(x, stats, mode, d_gamma, d_beta, g_resid=None, g_gemm=None, dt=None, lora_a=None, M=None, in_dropout=None):
     """d_gamma / d_beta += LayerNorm parameter gradients, dy assembled as layernorm_bwd does."""

@@ -12,6 +12,9 @@ starves the step, so the stored form here is what the GPU pipeline consumes dire
     image_bytes.npy                 int64 [n]: length of each stream (JPEG shards only)
     image_coefs.npy                 int64 [n]: quantised coefficients each stream decodes to (JPEG shards only; lays a batch out
                                     without parsing the streams first)
+    image_sync.npy                  int32 [entries, 4]: the streams' sync-index entries, back to back (optional: JPEG shards written
+                                    with ``jpeg_sync_mcus`` or indexed later by ``add_jpeg_sync_index``; meta "jpeg_sync_mcus")
+    image_sync_offsets.npy          int64 [n + 1]: first entry of each stream in image_sync.npy (with it)
     barcodes.bin                    the nucleotide strings (ASCII), back to back      (HDF5 "barcode")
     barcode_offsets.npy             int64 [n + 1]
     language_tokens_input_ids.npy   int64 [n, text_len]                               (HDF5 datasets of the same names)
@@ -29,6 +32,11 @@ the loader decodes them without a CPU pixel path: loader threads Huffman-decode 
 into the uint8 staging buffer the augmentation kernels read.  Only streams the decoder takes are ever written: baseline, 8-bit,
 grey or YCbCr 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0, one scan.
 
+``ShardLoader(..., entropy="gpu")`` moves the Huffman decoding to the device as well (``bsclip_jpeg_entropy_device``): the loader only
+copies the stored bytes, their sync-index entries and the tables parsed from their headers, about a twelfth of the coefficients'
+bytes.  It needs the shard's sync index, which records every ``jpeg_sync_mcus`` MCUs where a code starts and what the DC predictors
+are, so that the segments between entries decode side by side, one lane each.  The default stays ``"host"``.
+
 ``ShardLoader`` yields the reference's 7-tuple ``(processid, image, dna, input_ids, token_type_ids, attention_mask, label)``
 (dataset.py:267-275) with ``image`` f32 [B, 3, 224, 224] and ``dna`` int64 [B, 133] already on the device:
   * sample order: ``prepare()`` (dataset.py:41-48) = ``DistributedSampler(num_replicas, rank, shuffle, drop_last=True)`` -- the
@@ -44,6 +52,7 @@ import json
 import os
 import queue
 import threading
+import time
 
 import numpy as np
 import torch
@@ -51,20 +60,29 @@ import torch
 FORMAT, VERSION = "bsclip-shard", 1
 CODECS = ("raw", "jpeg")
 MAX_DECODE_THREADS = 16
+ENTROPY_MODES = ("host", "gpu")
+DEFAULT_JPEG_SYNC_MCUS = 4     # the sweep over {2, 4, 8, 16, 32} on the bench pictures
 _TAXA = ("order", "family", "genus", "species")
 _TEXT = ("language_tokens_input_ids", "language_tokens_token_type_ids", "language_tokens_attention_mask")
 
 
 def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mask, processid, labels=None, taxonomy=None,
-                split="train", dataset="bioscan_1m", image_codec="raw"):
+                split="train", dataset="bioscan_1m", image_codec="raw", jpeg_sync_mcus=None):
     """images: sequence of uint8 [H, W, 3] arrays (sizes may differ); barcodes: sequence of str; the three text arrays
     int [n, text_len]; processid: sequence of str; labels: int [n] (default: the sample index, dataset.py:139);
     taxonomy: dict order/family/genus/species -> sequence of str (default: empty strings).
     ``image_codec="jpeg"``: images is a sequence of ``bytes``, each a JPEG stream, stored as it is.  Every stream is probed AND
     entropy-decoded here (host only), so a shard never holds one the loader's decoder refuses or finds damaged: every stream is
-    looked at, then ValueError names the first ten offenders and their reasons."""
+    looked at, then ValueError names the first ten offenders and their reasons.
+    ``jpeg_sync_mcus`` (an int >= 1, JPEG shards only): also write the sync index that ``ShardLoader(entropy="gpu")`` needs, one entry
+    every that many MCUs (``DEFAULT_JPEG_SYNC_MCUS`` is the measured choice); ``None`` writes exactly the files a shard had before."""
     if image_codec not in CODECS:
         raise ValueError(f"image_codec must be one of {CODECS}, got {image_codec!r}")
+    if jpeg_sync_mcus is not None:
+        if image_codec != "jpeg":
+            raise ValueError("jpeg_sync_mcus belongs to image_codec='jpeg'")
+        jpeg_sync_mcus = _check_sync_mcus(jpeg_sync_mcus)
+    sync = []
     os.makedirs(path, exist_ok=True)
     n = len(barcodes)
     assert len(processid) == n and len(input_ids) == n
@@ -85,6 +103,8 @@ def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mas
                     nbytes[i] = len(im)
                     f.write(im)
                     off += len(im)
+                    if jpeg_sync_mcus is not None:
+                        sync.append(_sync_index(im, i, jpeg_sync_mcus))
                 continue
             im = np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
             assert im.ndim == 3 and im.shape[2] == 3, "images must be decoded uint8 H x W x 3"
@@ -99,6 +119,8 @@ def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mas
     if image_codec == "jpeg":
         np.save(os.path.join(path, "image_bytes.npy"), nbytes)
         np.save(os.path.join(path, "image_coefs.npy"), ncoefs)
+    if jpeg_sync_mcus is not None:
+        _save_sync(path, sync, np.save)
     offs = np.zeros(n + 1, dtype=np.int64)
     with open(os.path.join(path, "barcodes.bin"), "wb") as f:
         for i, s in enumerate(barcodes):
@@ -117,6 +139,8 @@ def write_shard(path, images, barcodes, input_ids, token_type_ids, attention_mas
             "text_len": int(np.asarray(input_ids).reshape(n, -1).shape[1])}
     if image_codec != "raw":       # absent = raw: shards written before the codec existed, and raw ones since, read the same
         meta["image_codec"] = image_codec
+    if jpeg_sync_mcus is not None:
+        meta["jpeg_sync_mcus"] = jpeg_sync_mcus
     with open(os.path.join(path, "meta.json"), "w") as f:
         json.dump(meta, f)
 
@@ -135,6 +159,58 @@ def _check_jpeg(data, i):
     except ops.JpegRefused as exc:
         raise ValueError(f"image {i}: {exc} (code {exc.code}); re-encode it as baseline JPEG or write a raw shard") from exc
     return int(info.height), int(info.width), int(info.coef_count)
+
+
+def _check_sync_mcus(v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError(f"jpeg_sync_mcus must be an integer >= 1, got {v!r}")
+    return int(v)
+
+
+def _sync_index(data, i, sync_mcus):
+    from bioscanclip.hip import ops
+    try:
+        return ops.jpeg_sync_index(data, sync_mcus)
+    except ops.JpegRefused as exc:
+        raise ValueError(f"image {i}: {exc} (code {exc.code}): the stream cannot be indexed") from exc
+
+
+def _save_sync(path, sync, save):
+    """image_sync.npy / image_sync_offsets.npy from the per-stream entry arrays."""
+    offs = np.concatenate([[0], np.cumsum([len(a) for a in sync])]).astype(np.int64)
+    save(os.path.join(path, "image_sync.npy"), np.concatenate(sync).astype(np.int32).reshape(-1, 4) if sync else np.zeros((0, 4), np.int32))
+    save(os.path.join(path, "image_sync_offsets.npy"), offs)
+
+
+def add_jpeg_sync_index(path, sync_mcus=None):
+    """Index an existing JPEG shard in place (host only): writes the same ``image_sync.npy`` / ``image_sync_offsets.npy`` and
+    ``meta["jpeg_sync_mcus"]`` as ``write_shard(..., jpeg_sync_mcus=sync_mcus)`` would have.  The arrays are written under temporary
+    names and renamed, and meta.json is replaced last and atomically, so a reader never sees an index its meta.json does not
+    describe (a shard already indexed at another spacing first loses its meta key, the same way).  ``sync_mcus=None``:
+    ``DEFAULT_JPEG_SYNC_MCUS``."""
+    sync_mcus = _check_sync_mcus(DEFAULT_JPEG_SYNC_MCUS if sync_mcus is None else sync_mcus)
+    sh = Shard(path)
+    if sh.image_codec != "jpeg":
+        raise ValueError(f"{path}: only a JPEG shard has streams to index (image_codec is {sh.image_codec!r})")
+    sync = []
+    for i in range(sh.n):
+        o = int(sh.image_index[i][0])
+        sync.append(_sync_index(sh.images[o:o + int(sh.image_nbytes[i])], i, sync_mcus))
+
+    def save(name, arr):
+        tmp = name + ".tmp.npy"
+        np.save(tmp, arr)
+        os.replace(tmp, name)
+
+    def save_meta(meta):
+        tmp = os.path.join(path, "meta.json.tmp")
+        with open(tmp, "w") as f:
+            json.dump(meta, f)
+        os.replace(tmp, os.path.join(path, "meta.json"))
+    if sh.jpeg_sync_mcus not in (None, sync_mcus):
+        save_meta({k: v for k, v in sh.meta.items() if k != "jpeg_sync_mcus"})
+    _save_sync(path, sync, save)
+    save_meta(dict(sh.meta, jpeg_sync_mcus=sync_mcus))
 
 
 def is_shard(path):
@@ -163,6 +239,13 @@ class Shard:
         self.taxonomy = {t: ld(t) for t in _TAXA}
         self.image_nbytes = ld("image_bytes") if self.image_codec == "jpeg" else None
         self.image_ncoefs = ld("image_coefs") if self.image_codec == "jpeg" else None
+        self.jpeg_sync_mcus = self.meta.get("jpeg_sync_mcus") if self.image_codec == "jpeg" else None
+        self.image_sync = self.image_sync_offsets = None
+        if self.jpeg_sync_mcus is not None:
+            self.image_sync, self.image_sync_offsets = ld("image_sync"), ld("image_sync_offsets")
+            if (len(self.image_sync_offsets) != self.n + 1 or self.image_sync.ndim != 2 or self.image_sync.shape[1] != 4
+                    or int(self.image_sync_offsets[-1]) != len(self.image_sync)):
+                raise ValueError(f"{path}: image_sync.npy / image_sync_offsets.npy disagree with n={self.n}")
         if self.image_nbytes is not None and len(self.image_nbytes) != self.n:
             raise ValueError(f"{path}: image_bytes.npy has {len(self.image_nbytes)} rows for n={self.n}")
         if not (len(self.image_index) == len(self.labels) == len(self.processid) == self.n and len(self.barcode_offsets) == self.n + 1):
@@ -220,15 +303,28 @@ class ShardLoader:
     SLOTS = 3
 
     def __init__(self, shard, batch_size, rank=0, world_size=1, shuffle=False, seed=0, for_training=True, with_text=True,
-                 device="cuda", augment_seed=None, decode_threads=4):
-        """``decode_threads`` (1..16, JPEG shards only): loader threads that entropy-decode a batch side by side."""
+                 device="cuda", augment_seed=None, decode_threads=4, entropy="host"):
+        """``decode_threads`` (1..16, JPEG shards only): loader threads that entropy-decode a batch side by side.
+        ``entropy`` (JPEG shards): ``"host"`` Huffman-decodes on those threads; ``"gpu"`` sends the stored bytes up and decodes them
+        on the device from the shard's sync index (``write_shard(jpeg_sync_mcus=...)`` / ``add_jpeg_sync_index``).  In GPU mode a
+        stream or index damaged after the shard was written -- shards are validated when written, so nothing else -- is found by
+        the device; the loader reads a batch's status words where it next synchronises on that batch's staging slot (before the
+        slot is refilled, and at the end of the iteration), so the ``RuntimeError`` naming the shard and the samples can arrive
+        up to ``SLOTS - 1`` batches after the damaged batch was yielded."""
         from bioscanclip.util.gpu_pipeline import GpuAugment
         self.shard = Shard(shard) if isinstance(shard, str) else shard
         self.decode_threads = int(decode_threads)
         if not 1 <= self.decode_threads <= MAX_DECODE_THREADS:   # a fixed bound, never the machine's CPU count: the box is shared
             raise ValueError(f"decode_threads must be in 1..{MAX_DECODE_THREADS}, got {decode_threads}")
+        if entropy not in ENTROPY_MODES:
+            raise ValueError(f"entropy must be one of {ENTROPY_MODES}, got {entropy!r}")
+        if entropy == "gpu" and (self.shard.image_codec != "jpeg" or self.shard.image_sync is None):
+            what = "a raw shard has no streams to decode" if self.shard.image_codec != "jpeg" else "this JPEG shard has no sync index"
+            raise ValueError(f"{self.shard.path}: entropy='gpu' needs a JPEG shard with a sync index ({what}); write it with "
+                             "write_shard(..., jpeg_sync_mcus=...) or index it in place with shards.add_jpeg_sync_index(path)")
+        self.entropy = entropy
         self._pool = None
-        if self.shard.image_codec == "jpeg" and self.decode_threads > 1:
+        if self.shard.image_codec == "jpeg" and self.decode_threads > 1 and entropy == "host":
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix="bsclip-jpeg")
         self.batch_size, self.rank, self.world_size = int(batch_size), rank, world_size
@@ -296,7 +392,7 @@ class ShardLoader:
         mh, T = slot["meta_host"], int(sh.meta["text_len"])
         off_h = mh[:B + 1]
         off_h.copy_(torch.tensor(doffs, dtype=torch.int64))
-        host = {"sizes": sizes, "nbytes": nbytes, "dna_offsets": off_h, "n_dna": doffs[-1],
+        host = {"sizes": sizes, "nbytes": nbytes, "indices": idx, "dna_offsets": off_h, "n_dna": doffs[-1],
                 "params": [self.augment.sample(*_resized_size(h, w, self.augment.resize_to)) for h, w in sizes],
                 "processid": [p.decode() for p in sh.processid[sel]]}
         if self.for_training:
@@ -312,7 +408,9 @@ class ShardLoader:
                 t = mh[base + k * self.batch_size * T:base + k * self.batch_size * T + B * T].view(B, T)
                 t.copy_(torch.from_numpy(np.ascontiguousarray(a[sel])))
                 host["text"].append(t)
-        if jpeg:
+        if jpeg and self.entropy == "gpu":
+            host.update(self._stage_jpeg_gpu(slot, idx, rows))
+        elif jpeg:
             host["ncoef"] = self._stage_jpeg(slot, idx, rows)
         return host
 
@@ -347,22 +445,103 @@ class ShardLoader:
                 except ops.JpegRefused as exc:
                     raise RuntimeError(f"{sh.path}: sample {idx[k]}: {exc}") from exc
         run(decode)
-        rec = slot["rec_host"].numpy()[:B]
+        self._place_records(slot["rec_host"].numpy()[:B], rows, coef_off, idx)
+        return ncoef
+
+    def _place_records(self, rec, rows, coef_off, idx):
+        """The batch fields of the B records the library wrote: where each image's coefficients, pixels and tables are."""
+        B = len(idx)
         if not (np.array_equal(rec[:, 5], rows[:, 1]) and np.array_equal(rec[:, 4], rows[:, 2])):
-            raise RuntimeError(f"{sh.path}: image_index.npy disagrees with the streams' own sizes (samples {list(idx)})")
+            raise RuntimeError(f"{self.shard.path}: image_index.npy disagrees with the streams' own sizes (samples {list(idx)})")
         pix_off = np.concatenate([[0], np.cumsum(rows[:, 1] * rows[:, 2] * 3)])[:B]
-        for col, v in ((0, coef_off[:B]), (2, pix_off)):          # the batch fields of the records: 64-bit offsets as two int32
+        for col, v in ((0, coef_off[:B]), (2, pix_off)):          # 64-bit offsets as two int32
             rec[:, col] = (v & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
             rec[:, col + 1] = (v >> 32).astype(np.int32)
         rec[:, 9:12] += 3 * np.arange(B, dtype=np.int32)[:, None]   # image k's tables are slots 3k .. 3k + 2
-        return ncoef
+
+    def _stage_jpeg_gpu(self, slot, idx, rows):
+        """GPU entropy mode: copy the batch's streams back to back into the slot's pinned byte buffer, gather their sync-index
+        entries and parse their headers into device-ready tables and records.  Nothing is decoded on the host."""
+        from bioscanclip.hip import lib as _l, ops
+        sh, B, bs = self.shard, len(idx), self.batch_size
+        sel = np.asarray(idx)
+        lens = np.asarray(sh.image_nbytes[sel], dtype=np.int64)
+        byte_off = np.concatenate([[0], np.cumsum(lens)])
+        e0 = np.asarray(sh.image_sync_offsets[sel], dtype=np.int64)
+        ents = np.asarray(sh.image_sync_offsets[sel + 1], dtype=np.int64) - e0
+        ent_off = np.concatenate([[0], np.cumsum(ents)])
+        counts = np.asarray(sh.image_ncoefs[sel], dtype=np.int64)
+        coef_off = np.concatenate([[0], np.cumsum(counts)])
+        ncoef, nbytes, nsync = int(coef_off[-1]), int(byte_off[-1]), int(ent_off[-1])
+        with torch.cuda.stream(self.stream):
+            if slot.get("cap_coef", 0) < ncoef:
+                slot["cap_coef"] = int(ncoef * 1.25) + 4096
+                slot["coef_dev"] = torch.empty(slot["cap_coef"], dtype=torch.int16, device=self.device)
+                slot["planes_dev"] = torch.empty(ops.jpeg_pixels_workspace_bytes(slot["cap_coef"]), dtype=torch.uint8, device=self.device)
+            if slot.get("cap_bytes", 0) < nbytes:
+                slot["cap_bytes"] = int(nbytes * 1.25) + 4096
+                slot["bytes_host"] = torch.empty(slot["cap_bytes"], dtype=torch.uint8).pin_memory()
+                slot["bytes_dev"] = torch.empty(slot["cap_bytes"], dtype=torch.uint8, device=self.device)
+            if slot.get("cap_sync", 0) < nsync:
+                slot["cap_sync"] = int(nsync * 1.25) + 64
+                slot["sync_host"] = torch.empty((slot["cap_sync"], 4), dtype=torch.int32).pin_memory()
+                slot["sync_dev"] = torch.empty((slot["cap_sync"], 4), dtype=torch.int32, device=self.device)
+            if "huff_host" not in slot:     # allocated once per slot, like meta_host
+                slot["rec_host"] = torch.empty((bs, _l.JPEG_REC), dtype=torch.int32).pin_memory()
+                slot["seg_host"] = torch.zeros((bs, _l.JPEG_SEG_REC), dtype=torch.int32).pin_memory()
+                slot["qtab_host"] = torch.empty((bs * 3, 64), dtype=torch.int16).pin_memory()
+                slot["huff_host"] = torch.empty((bs, 4 * _l.JPEG_HUFF_BYTES), dtype=torch.uint8).pin_memory()
+                slot["status_host"] = torch.zeros(bs, dtype=torch.int32).pin_memory()
+                slot["huff_dev"] = torch.empty((bs, 4 * _l.JPEG_HUFF_BYTES), dtype=torch.uint8, device=self.device)
+                slot["status_dev"] = torch.zeros(bs, dtype=torch.int32, device=self.device)
+        bytes_np, sync_np = slot["bytes_host"].numpy(), slot["sync_host"].numpy()
+        base = sh.images.ctypes.data
+        huff_p, rec_p, qtab_p = slot["huff_host"].data_ptr(), slot["rec_host"].data_ptr(), slot["qtab_host"].data_ptr()
+        for k in range(B):
+            o, n = int(rows[k][0]), int(lens[k])
+            bytes_np[byte_off[k]:byte_off[k] + n] = sh.images[o:o + n]
+            sync_np[ent_off[k]:ent_off[k + 1]] = sh.image_sync[e0[k]:e0[k] + ents[k]]
+            try:
+                ops.jpeg_device_tables(base + o, n, huff_p + 4 * _l.JPEG_HUFF_BYTES * k, qtab_p + 384 * k, rec_p + 64 * k)
+            except ops.JpegRefused as exc:
+                raise RuntimeError(f"{sh.path}: sample {idx[k]}: {exc}") from exc
+        seg = slot["seg_host"].numpy()[:B]
+        seg[:, 0], seg[:, 1], seg[:, 2], seg[:, 3] = byte_off[:B], lens, ent_off[:B], ents
+        seg[:, 4], seg[:, 5] = int(sh.jpeg_sync_mcus), np.arange(B)
+        self._place_records(slot["rec_host"].numpy()[:B], rows, coef_off, idx)
+        return {"ncoef": ncoef, "jpeg_bytes": nbytes, "jpeg_sync": nsync}
+
+    def _check_status(self, slot):
+        """GPU entropy mode: the status words of the batch this slot last held.  The caller has synchronised on the slot's event."""
+        idx = slot.pop("status_idx", None)
+        if idx is None:
+            return
+        st = slot["status_host"][:len(idx)].numpy()
+        if st.any():
+            bad = [int(i) for i, s in zip(idx, st) if s]
+            raise RuntimeError(f"{self.shard.path}: the device found damaged JPEG bytes or sync-index entries in samples {bad} (status "
+                               f"{[int(s) for s in st if s]}, BSCLIP_JPEG_SEG_* bits); the batch that held them was yielded up to "
+                               f"{self.SLOTS - 1} batches ago")
 
     def _enqueue(self, slot, host):
         """Device half, on the loader's side stream: H2D copies + the two transforms; records the slot's ready event."""
         from bioscanclip.hip import ops
         B = len(host["sizes"])
         with torch.cuda.stream(self.stream):
-            if "ncoef" in host:      # JPEG shard: coefficients, tables and records go up, the pixels are made in img_dev
+            if "jpeg_bytes" in host:   # JPEG shard, GPU entropy: bytes, index and tables go up, the device decodes into coef_dev
+                n, nb, ne = host["ncoef"], host["jpeg_bytes"], host["jpeg_sync"]
+                slot["bytes_dev"][:nb].copy_(slot["bytes_host"][:nb], non_blocking=True)
+                slot["sync_dev"][:ne].copy_(slot["sync_host"][:ne], non_blocking=True)
+                slot["huff_dev"][:B].copy_(slot["huff_host"][:B], non_blocking=True)
+                qtab_dev = slot["qtab_host"][:3 * B].to(self.device, non_blocking=True)
+                rec_dev = torch.empty((B, 16), dtype=torch.int32, device=self.device)
+                seg_dev = torch.empty((B, 8), dtype=torch.int32, device=self.device)
+                ops.jpeg_entropy_device(slot["bytes_dev"], slot["sync_dev"], slot["huff_dev"][:B], slot["rec_host"][:B], slot["seg_host"][:B],
+                                        rec_dev, seg_dev, B, slot["coef_dev"], n, slot["status_dev"][:B])
+                slot["status_host"][:B].copy_(slot["status_dev"][:B], non_blocking=True)   # read once the slot's event has passed
+                slot["status_idx"] = list(host["indices"])
+                ops.jpeg_pixels(slot["coef_dev"], n, qtab_dev, slot["rec_host"][:B], rec_dev, B, slot["planes_dev"], slot["img_dev"])
+            elif "ncoef" in host:    # JPEG shard: coefficients, tables and records go up, the pixels are made in img_dev
                 n = host["ncoef"]
                 slot["coef_dev"][:n].copy_(slot["coef_host"][:n], non_blocking=True)
                 qtab_dev = slot["qtab_host"][:3 * B].to(self.device, non_blocking=True)
@@ -395,6 +574,7 @@ class ShardLoader:
         dev = self.device
 
         def producer():
+            cpu0 = time.thread_time()
             try:
                 torch.cuda.set_device(dev)
                 for k, b in enumerate(batches):
@@ -403,11 +583,19 @@ class ShardLoader:
                         # the slot's pinned buffers are about to be refilled: its previous H2D copies (and the kernels that read
                         # its device staging buffers) must have run -- three batches ago, so this never waits in practice
                         slot["out"]["ready"].synchronize()
+                        self._check_status(slot)
                     host = self._stage(slot, b)
                     q.put((k, b, self._enqueue(slot, host)))
+                if self.entropy == "gpu":      # the last SLOTS batches: nothing refills their slots, so they are looked at here
+                    for slot in self._slots:
+                        if "status_idx" in slot:
+                            slot["out"]["ready"].synchronize()
+                            self._check_status(slot)
                 q.put(None)
             except BaseException as exc:   # noqa: BLE001 - surface producer failures in the consumer
                 q.put(exc)
+            finally:
+                self.producer_cpu_seconds = time.thread_time() - cpu0     # tools/jpeg_loader_bench.py reads it after th.join()
 
         th = threading.Thread(target=producer, daemon=True)
         th.start()
@@ -433,13 +621,15 @@ class ShardLoader:
             pool.shutdown(wait=False)
 
 
-def convert_hdf5_split(hdf5_path, split, out_dir, dataset="bioscan_1m", labels=None, image_codec="raw", reencode=False):
+def convert_hdf5_split(hdf5_path, split, out_dir, dataset="bioscan_1m", labels=None, image_codec="raw", reencode=False,
+                       jpeg_sync_mcus=None):
     """Write one split of the reference's HDF5 file (DATA.md:23-35; datasets image / image_mask / barcode /
     language_tokens_* / processid | image_file / order / family / genus / species, read as ``Dataset_for_CL`` reads them,
     dataset.py:219-265) as a shard directory.  Needs h5py, which this image does not have: run it where the data lives.
     ``image_codec="raw"`` decodes every image with Pillow; ``"jpeg"`` copies the stored streams (no Pillow) after checking that the
     loader's decoder takes each one.  Streams it does not take raise (``write_shard`` names the first ten) -- or, with ``reencode=True``, are
-    re-encoded through Pillow as baseline 4:4:4 quality 95 and counted in meta.json ("reencoded")."""
+    re-encoded through Pillow as baseline 4:4:4 quality 95 and counted in meta.json ("reencoded").  ``jpeg_sync_mcus`` goes to
+    ``write_shard``: the sync index for ``ShardLoader(entropy="gpu")``."""
     try:
         import io
         import h5py
@@ -474,7 +664,7 @@ def convert_hdf5_split(hdf5_path, split, out_dir, dataset="bioscan_1m", labels=N
                 g["language_tokens_input_ids"][:], g["language_tokens_token_type_ids"][:], g["language_tokens_attention_mask"][:],
                 [p.decode("utf-8") for p in g[pid_key][:]], labels=labels,
                 taxonomy={t: [v.decode("utf-8") for v in g[t][:]] for t in _TAXA}, split=split, dataset=dataset,
-                image_codec=image_codec)
+                image_codec=image_codec, jpeg_sync_mcus=jpeg_sync_mcus)
     if image_codec == "jpeg" and reencode:                                    # pragma: no cover
         with open(os.path.join(out_dir, "meta.json")) as f:
             meta = json.load(f)

@@ -1,7 +1,8 @@
 // Host half of the JPEG decode: marker parsing and Huffman decoding of baseline sequential 8-bit streams into quantised
 // coefficients.  Plain C++ (no HIP headers), no allocation (all state lives in a Decoder on the caller's stack), no globals:
 // safe to call from any number of loader threads at once.  The data-parallel half (dequantise, inverse DCT, upsampling,
-// colour) is csrc/jpeg.hip.
+// colour) is csrc/jpeg.hip.  At the end of this file: the sync index and the device-ready tables with which the same coefficients
+// are decoded on the device instead (csrc/jpeg_segment.h, csrc/jpeg_entropy.hip); the decoder itself does not use them.
 //
 // Accepted: SOF0, 8-bit, one component (grey) or three (YCbCr) with luma sampling H, V in {1, 2} and chroma 1x1 (4:4:4, 4:2:2,
 // 4:4:0, 4:2:0), one interleaved scan, restart intervals, any size up to 4096 x 4096.  Everything else is refused with a code
@@ -20,6 +21,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include "jpeg_segment.h"
 
 namespace bsclip_jpeg {
 
@@ -425,6 +428,113 @@ inline int entropy_decode(const uint8_t* bytes, size_t n, int16_t* coef_out, int
     }
     if (rc != OK && msg && msg_len) snprintf(msg, msg_len, "%s", d.msg);
     return rc;
+}
+
+// ---- the sync index and the device-ready tables ("entropy decode on the device") -----------------------------------
+// The four tables a scan selects, in the segment decoder's form, and the selector word that says which each component uses.  A scan
+// whose components select more than two DC or more than two AC tables (baseline allows two of each) is refused.
+inline void seg_huff_from(const Huff& h, SegHuff* o) {
+    memset(o, 0, sizeof(*o));
+    memcpy(o->look, h.look, sizeof(o->look));
+    for (int len = 1; len <= 16; ++len) o->maxcode[len] = h.maxcode[len], o->valoff[len] = h.valoff[len];
+    o->maxcode[0] = -1;
+    o->nvals = h.nvals;
+    memcpy(o->vals, h.vals, sizeof(o->vals));
+}
+
+inline int seg_tables(Decoder& d, SegHuff* tabs, int* sel_out) {
+    int dcid[2] = {-1, -1}, acid[2] = {-1, -1}, sel = 0;
+    for (int c = 0; c < d.f.ncomp; ++c) {
+        int sd = -1, sa = -1;
+        for (int k = 0; k < 2 && sd < 0; ++k)
+            if (dcid[k] < 0 || dcid[k] == d.f.dcsel[c]) dcid[k] = d.f.dcsel[c], sd = k;
+        for (int k = 0; k < 2 && sa < 0; ++k)
+            if (acid[k] < 0 || acid[k] == d.f.acsel[c]) acid[k] = d.f.acsel[c], sa = k;
+        if (sd < 0 || sa < 0) return d.fail(ERR_SOF, "unsupported JPEG: the scan selects more than two DC or two AC Huffman tables");
+        sel |= (sd << c) | (sa << (4 + c));
+    }
+    for (int k = 0; k < 2; ++k) {
+        seg_huff_from(d.dc[dcid[k] < 0 ? dcid[0] : dcid[k]], tabs + k);
+        seg_huff_from(d.ac[acid[k] < 0 ? acid[0] : acid[k]], tabs + 2 + k);
+    }
+    *sel_out = sel;
+    return OK;
+}
+
+inline SegGeom seg_geom(const Frame& f, int sel) { return SegGeom{f.ncomp, f.hs, f.vs, f.mcus_x, f.mcus_x * f.mcus_y, sel}; }
+
+// Headers of one stream -> SEG_TABLES device-ready Huffman tables, the quantisation tables (3 x 64 uint16) and the 16-int record
+// with word 14 = the selector word (the pixel kernels ignore it).  Decodes nothing.
+inline int device_tables(const uint8_t* bytes, size_t n, SegHuff* huff_out, uint16_t* qtab_out, int32_t* record_out, char* msg,
+                         size_t msg_len) {
+    Decoder d;
+    int rc, sel = 0;
+    if (!bytes || !huff_out || !qtab_out || !record_out) rc = d.fail(ERR_ARGS, "null pointer");
+    else rc = d.parse(bytes, n);
+    if (rc == OK) rc = seg_tables(d, huff_out, &sel);
+    if (rc == OK) {
+        memset(qtab_out, 0, 3 * 64 * sizeof(uint16_t));
+        for (int c = 0; c < d.f.ncomp; ++c) memcpy(qtab_out + 64 * c, d.qt[d.f.qsel[c]], 64 * sizeof(uint16_t));
+        d.write_record(record_out);
+        record_out[14] = sel;
+    }
+    if (rc != OK && msg && msg_len) snprintf(msg, msg_len, "%s", d.msg);
+    return rc;
+}
+
+// The sync index of one stream: SYNC_ENTRY int32 per segment (segment_range says which MCUs each covers).  Walks the scan with the
+// segment decoder itself, storing nothing, so an indexed stream is one the device decodes with status 0.  out == null: returns the
+// entry count, which the frame, the restart interval and sync_mcus fix.  Otherwise returns the count written or an error code: the
+// decoder's own for everything the decoder refuses, ERR_ARGS for a stream of 2^28 bytes or more, sync_mcus < 1 or a short buffer,
+// ERR_CORRUPT for data bytes between the last MCU and the marker that ends an interval or the scan.
+inline int64_t sync_index(const uint8_t* bytes, size_t n, int sync_mcus, int32_t* out, int64_t capacity, char* msg, size_t msg_len) {
+    Decoder d;
+    SegHuff tabs[SEG_TABLES];
+    int rc, sel = 0;
+    int64_t count = 0;
+    if (!bytes) rc = d.fail(ERR_ARGS, "null input");
+    else if (n >= (size_t)MAX_STREAM) rc = d.fail(ERR_ARGS, "stream of %zu bytes: the index holds bit positions of streams below 2^28 bytes", n);
+    else if (sync_mcus < 1) rc = d.fail(ERR_ARGS, "sync_mcus=%d must be at least 1", sync_mcus);
+    else rc = d.parse(bytes, n);
+    if (rc == OK) rc = seg_tables(d, tabs, &sel);
+    if (rc == OK) {
+        const SegGeom g = seg_geom(d.f, sel);
+        count = segment_count(g.nmcu, d.f.restart, sync_mcus);
+        if (out && capacity < count) rc = d.fail(ERR_ARGS, "index buffer holds %lld entries but the stream needs %lld", (long long)capacity, (long long)count);
+        if (out && rc == OK) {
+            int32_t e[SYNC_ENTRY] = {(int32_t)(d.f.scan_pos * 8), 0, 0, 0};
+            int next_rst = 0;
+            for (int j = 0; j < (int)count && rc == OK; ++j) {
+                int first, cnt;
+                bool chained;
+                segment_range(j, g.nmcu, d.f.restart, sync_mcus, &first, &cnt, &chained);
+                e[1] = first;
+                memcpy(out + (size_t)j * SYNC_ENTRY, e, sizeof(e));
+                SegEnd end;
+                const int st = decode_segment<false>(bytes, (uint32_t)n, e, first, cnt, g, tabs, nullptr, &end);
+                if (st & SEG_OVERRUN) rc = d.fail(ERR_TRUNCATED, "truncated stream: entropy data ends before MCU %d", first + cnt);
+                else if (st) rc = d.fail(ERR_CORRUPT, "corrupt stream: unassigned code or run length past the block in MCUs %d..%d", first, first + cnt - 1);
+                else if (chained) {
+                    e[0] = end.bitpos, e[2] = end.pred[0];
+                    e[3] = g.ncomp == 3 ? pack_chroma(end.pred[1], end.pred[2]) : 0;
+                } else {
+                    if (end.real >= 8) rc = d.fail(ERR_CORRUPT, "corrupt stream: data where a marker belongs near byte %u", end.fetch);
+                    if (rc == OK && first + cnt < g.nmcu) {   // the restart marker, found as the decoder finds it
+                        size_t at = end.fetch;
+                        while (at < n && bytes[at] == 0xFF && at + 1 < n && bytes[at + 1] == 0xFF) ++at;
+                        if (at + 2 > n) rc = d.fail(ERR_TRUNCATED, "truncated stream: ends where RST%d belongs", next_rst);
+                        else if (bytes[at] != 0xFF || bytes[at + 1] != 0xD0 + next_rst)
+                            rc = d.fail(ERR_CORRUPT, "corrupt stream: 0x%02X%02X where RST%d belongs at byte %zu", bytes[at], bytes[at + 1], next_rst, at);
+                        else if (at + 2 >= n) rc = d.fail(ERR_TRUNCATED, "truncated stream: ends after RST%d", next_rst);
+                        next_rst = (next_rst + 1) & 7;
+                        e[0] = (int32_t)((at + 2) * 8), e[2] = e[3] = 0;
+                    }
+                }
+            }
+        }
+    }
+    if (rc != OK && msg && msg_len) snprintf(msg, msg_len, "%s", d.msg);
+    return rc != OK ? rc : count;
 }
 
 }  // namespace bsclip_jpeg

@@ -129,8 +129,19 @@ def fp16_towers(args):
     return towers
 
 
+def jpeg_entropy_mode(args):
+    """``hip_jpeg_entropy=host|gpu`` (default ``host``): where a JPEG shard's streams are Huffman-decoded -- on loader threads, or on
+    the device from the shard's sync index (``shards.add_jpeg_sync_index``).  Anything else is refused here, before any GPU work."""
+    mode = getattr(args, "hip_jpeg_entropy", None)
+    mode = "host" if mode is None or mode == "" else str(mode)
+    if mode not in ("host", "gpu"):
+        raise ValueError(f"hip_jpeg_entropy must be 'host' or 'gpu', got {mode!r}")
+    return mode
+
+
 def main_process(rank: int, world_size: int, args):
     towers16 = fp16_towers(args)
+    jpeg_entropy = jpeg_entropy_mode(args)
     if getattr(args, "debug_flag", False) or rank != 0:
         args.activate_wandb = False
         args.save_inference = False
@@ -152,7 +163,7 @@ def main_process(rank: int, world_size: int, args):
         # k-mer tokeniser; shuffled like the reference's pre-training loader (train_cl.py: shuffle=True)
         pre_train_dataloader = shards.ShardLoader(str(dataset), int(mc.batch_size), rank=rank, world_size=world_size, shuffle=True,
                                                   seed=int(getattr(args, "seed", 0)), for_training=True, with_text=with_text,
-                                                  device=device)
+                                                  device=device, entropy=jpeg_entropy)
     elif dataset not in ("synthetic", "synthetic_raw"):
         raise NotImplementedError("the HDF5 file itself is outside the accelerated path (SURVEY 8f-3; h5py is absent): convert a "
                                   "split with bioscanclip.util.shards.convert_hdf5_split and pass dataset=<shard directory>, or use "
@@ -239,6 +250,7 @@ def main(argv=None):
     if "model_config" not in args:
         raise SystemExit("usage: train_cl.py 'model_config=<name>' [key=value ...]")
     fp16_towers(args)   # refuse an unbuilt fp16 backward before any GPU work
+    jpeg_entropy_mode(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     print_when_rank_zero(f'world_size: {world_size}', rank)

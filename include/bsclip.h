@@ -580,6 +580,54 @@ int bsclip_jpeg_pixels(const int16_t* coef_dev, int64_t coef_count, const uint16
                        const int32_t* records_host, int32_t* records_dev, int B, void* scratch, int64_t scratch_bytes,
                        void* out_u8, int64_t out_capacity, void* stream);
 
+/* ---- JPEG shards, entropy decode on the device (opt-in, the host decoder above stays the default) ------------
+ * Huffman decoding is serial only while nobody knows where a code starts.  A SYNC INDEX, made once on the host when a shard is
+ * written, cuts a scan into segments that decode independently: one entry at MCU 0, one at the first MCU of every restart
+ * interval, and one every sync_mcus MCUs counted from the start of the current restart interval.  No segment crosses a restart
+ * marker.  Which MCUs segment j covers, and how many segments there are, follows from the frame, the restart interval and
+ * sync_mcus alone; a segment ends where the next begins, the last at the MCU count.
+ * Index entry, int32[4]:
+ *     [0] position of the segment's first entropy-coded bit, 8 * byte + bit from the start of the stream (bit 0 = the byte's most
+ *         significant); the byte is always a data byte, never a stuffed 0x00 and never a marker
+ *     [1] index of the segment's first MCU
+ *     [2] DC predictor of Y at that point
+ *     [3] DC predictors of Cb (low 16 bits) and Cr (high 16 bits), both two's-complement int16; 0 for a grey image
+ * jpeg_sync_index (HOST: no device call, no allocation, no globals, thread-safe, its own error text): walks the scan with the
+ *   segment decoder and writes the entries.  index_out == NULL: returns the entry count.  Otherwise returns the count written
+ *   (<= capacity entries) or a negative code: the entropy decoder's own for whatever that refuses, BSCLIP_ERR_INVALID for a stream
+ *   of 2^28 bytes or more, sync_mcus < 1 or a short buffer, BSCLIP_JPEG_ERR_CORRUPT for data bytes between the last MCU of a
+ *   restart interval (or of the scan) and its marker, BSCLIP_JPEG_ERR_SOF for a scan that selects more than two DC or two AC tables.
+ * jpeg_device_tables (HOST, same properties): parses a stream's headers once and writes what the device needs:
+ *   huff_out  4 tables of BSCLIP_JPEG_HUFF_BYTES each (DC slot 0, DC slot 1, AC slot 0, AC slot 1; 4-byte aligned): the 9-bit
+ *             look-up, the per-length largest codes and symbol offsets and the symbols, expanded here on the host
+ *   qtab_out, record_out  as bsclip_jpeg_entropy_decode writes them, and record word 14 = the selector word: bit c = DC slot of
+ *             component c, bit 4 + c = its AC slot (word 13, the restart interval, now matters too).
+ * jpeg_entropy_device: the coefficients of B images, written exactly as bsclip_jpeg_entropy_decode writes them, one lane per
+ *   segment.  bytes_dev: the streams, anywhere in [0, bytes_capacity < 2^31); sync_dev: int32 [sync_entries][4]; huff_dev:
+ *   huff_slots groups of 4 tables; coef_dev int16 [coef_count].  records_host: the B 16-int records (coefficient offset, sizes,
+ *   restart interval, selector word); segments_host int32 [B][8]:
+ *     {byte offset, byte length (< 2^28), first index entry, index entries, sync_mcus, table-group slot, 0, 0}.
+ *   Both stay in HOST memory and are validated before anything is launched (sizes against the block count, the entry count against
+ *   frame, restart interval and sync_mcus, every range against bytes_capacity / sync_entries / huff_slots / coef_count); then the
+ *   library copies them to records_dev [B][16] / segments_dev [B][8] (device scratch) and zeroes status_dev (int32 [B]) on
+ *   `stream` itself.  After the launch every element of each image's coefficient range is defined, and status_dev[b] is 0 or an
+ *   or of the BSCLIP_JPEG_SEG_* bits: the image's bytes or index are damaged and its coefficients must not be used.
+ *   sync_dev, coef_dev 16-byte aligned; the others 4-byte.  Images must not overlap (not checked). */
+#define BSCLIP_JPEG_HUFF_BYTES 1420
+#define BSCLIP_JPEG_SEG_BAD_CODE 1    /* a code no table assigns */
+#define BSCLIP_JPEG_SEG_BAD_RUN 2     /* a zero run that leaves its block */
+#define BSCLIP_JPEG_SEG_OVERRUN 4     /* bits consumed past the byte range or a marker */
+#define BSCLIP_JPEG_SEG_END_POS 8     /* a segment did not end where the next one starts */
+#define BSCLIP_JPEG_SEG_END_PRED 16   /* DC predictors at a segment's end differ from the next entry's */
+#define BSCLIP_JPEG_SEG_BAD_ENTRY 32  /* an entry's first MCU or bit position is not its segment's */
+int64_t bsclip_jpeg_sync_index(const void* host_bytes, int64_t n, int sync_mcus, int32_t* host_index_out, int64_t capacity);
+int bsclip_jpeg_device_tables(const void* host_bytes, int64_t n, void* host_huff_out, uint16_t* host_qtab_out,
+                              int32_t* host_record_out);
+int bsclip_jpeg_entropy_device(const void* bytes_dev, int64_t bytes_capacity, const int32_t* sync_dev, int64_t sync_entries,
+                               const void* huff_dev, int huff_slots, const int32_t* records_host, const int32_t* segments_host,
+                               int32_t* records_dev, int32_t* segments_dev, int B, int16_t* coef_dev, int64_t coef_count,
+                               int32_t* status_dev, void* stream);
+
 /* ---- LoRA / head gradients -------------------------------------------------------------------------------------
  * lora_grad: for one layer, from dqkv (bf16 [M, ld_dqkv], q cols [0,H), v cols [2H,3H)) and the augmented LN
  *   output h (bf16 [M, ld_h]: cols [0,H) = y, [H,H+4) = t_q, [H+4,H+8) = t_v):

@@ -13,6 +13,15 @@ count 1 / 2 / 4 / 8:
 The bar (README): the step consumes 6 540 samples/s per GPU.  Writes profiles/jpeg_loader_bench.json.
 
     python tools/jpeg_loader_bench.py [--n 1024] [--epochs 2] [--reps 20]
+
+``--entropy both`` adds the entropy axis and writes profiles/jpeg_loader_bench_gpu_entropy.json instead: the host path at 1 / 2 / 4 / 8
+decode threads and the GPU path (``ShardLoader(entropy="gpu")``) at sync_mcus 2 / 4 / 8 / 16 / 32 take turns, one epoch each, inside the
+same run -- one warm-up round, then --epochs timed rounds -- and each configuration reports end-to-end samples/s, the producer
+thread's CPU seconds per 1 000 samples (``time.thread_time``; the decode pool's threads are not in it, so the process's CPU seconds
+are reported next to it), the image path's H2D bytes per sample counted from the shapes, and for the GPU path the index's share of
+the stream bytes and the entropy kernel's device-event time for B images.  The issue's workload is ``--n 4096 --epochs 4``.
+``--kernel-only`` only launches the entropy kernel (B images, default sync_mcus, --reps times): the program to put behind
+``rocprofv3 --kernel-trace --stats --``.
 """
 import argparse
 import io
@@ -50,6 +59,91 @@ def make_images(n, seed):
     return out
 
 
+def entropy_kernel_us(streams, sync_mcus, reps):
+    """Device-event times (us) of bsclip_jpeg_entropy_device over ``streams`` (copies and memset of the records included)."""
+    import torch
+    from bioscanclip.hip import lib, ops
+    B = len(streams)
+    idx = [ops.jpeg_sync_index(s, sync_mcus) for s in streams]
+    huff = np.zeros((B, 4 * lib.JPEG_HUFF_BYTES), dtype=np.uint8)
+    qtab, rec, seg = np.zeros((B, 3, 64), dtype=np.uint16), np.zeros((B, 16), dtype=np.int32), np.zeros((B, 8), dtype=np.int32)
+    blob, eo, co = bytearray(), 0, 0
+    for k, s in enumerate(streams):
+        src = np.frombuffer(s, dtype=np.uint8)
+        ops.jpeg_device_tables(src.ctypes.data, src.size, huff[k].ctypes.data, qtab[k].ctypes.data, rec[k].ctypes.data)
+        rec[k, 0] = co
+        seg[k] = (len(blob), len(s), eo, len(idx[k]), sync_mcus, k, 0, 0)
+        blob += s
+        eo, co = eo + len(idx[k]), co + 64 * int(rec[k, 12])
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    bytes_dev, sync_dev, huff_dev = dev(np.frombuffer(bytes(blob), dtype=np.uint8).copy()), dev(np.concatenate(idx)), dev(huff)
+    rec_host, seg_host = torch.from_numpy(rec).pin_memory(), torch.from_numpy(seg).pin_memory()
+    rec_dev, seg_dev = torch.empty((B, 16), dtype=torch.int32, device="cuda"), torch.empty((B, 8), dtype=torch.int32, device="cuda")
+    coef, status = torch.empty(co, dtype=torch.int16, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+    times = []
+    for r in range(reps + 3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.jpeg_entropy_device(bytes_dev, sync_dev, huff_dev, rec_host, seg_host, rec_dev, seg_dev, B, coef, co, status)
+        e1.record()
+        torch.cuda.synchronize()
+        if r >= 3:
+            times.append(e0.elapsed_time(e1) * 1e3)
+    assert int(status.abs().sum()) == 0, "the bench pictures must decode with status 0"
+    return times
+
+
+def entropy_axis(args, tmp, sample_streams, common, count):
+    """Host path at 1 / 2 / 4 / 8 threads and GPU path at each sync_mcus, alternating epoch by epoch in one run."""
+    import torch
+    from bioscanclip.hip import lib
+    from bioscanclip.util import shards
+    n, B = args.n, args.batch
+    stream_bytes = sum(len(s) for s in sample_streams) / n
+    configs = []
+    for T in (1, 2, 4, 8):
+        configs.append({"name": f"host_t{T}", "entropy": "host", "decode_threads": T, "path": os.path.join(tmp, "jpeg"),
+                        "h2d_bytes_per_sample": 2 * count + 384 + 64})
+    for s in (2, 4, 8, 16, 32):
+        path = os.path.join(tmp, f"jpeg_sync{s}")
+        shards.write_shard(path, sample_streams, image_codec="jpeg", jpeg_sync_mcus=s, **common)
+        entries = len(np.load(os.path.join(path, "image_sync.npy"))) / n
+        kt = entropy_kernel_us(sample_streams[:B], s, args.reps)
+        configs.append({"name": f"gpu_sync{s}", "entropy": "gpu", "sync_mcus": s, "path": path, "index_entries_per_image": entries,
+                        "index_over_stream_bytes": 16 * entries / stream_bytes,
+                        "h2d_bytes_per_sample": stream_bytes + 16 * entries + 4 * lib.JPEG_HUFF_BYTES + 384 + 2 * 64 + 32,
+                        "entropy_kernel_us_median": statistics.median(kt), "entropy_kernel_us_min": min(kt), "entropy_kernel_B": B})
+    for c in configs:
+        kw = {"decode_threads": c["decode_threads"]} if c["entropy"] == "host" else {"entropy": "gpu"}
+        c["loader"] = shards.ShardLoader(c["path"], batch_size=B, shuffle=True, seed=1, for_training=True, with_text=True, **kw)
+        c["rates"], c["producer_cpu"], c["process_cpu"] = [], [], []
+    for epoch in range(args.epochs + 1):        # round 0 warms every configuration up
+        for c in configs:
+            ld = c["loader"]
+            ld.set_epoch(epoch)
+            torch.cuda.synchronize()
+            t0, p0, seen = time.perf_counter(), time.process_time(), 0
+            for batch in ld:
+                seen += batch[1].shape[0]
+            torch.cuda.synchronize()
+            if epoch:
+                c["rates"].append(seen / (time.perf_counter() - t0))
+                c["producer_cpu"].append(ld.producer_cpu_seconds / seen * 1e3)
+                c["process_cpu"].append((time.process_time() - p0) / seen * 1e3)
+    out = {}
+    for c in configs:
+        out[c["name"]] = {k: v for k, v in c.items() if k not in ("loader", "path", "name", "rates", "producer_cpu", "process_cpu")}
+        out[c["name"]].update({"samples_per_s": {"median": statistics.median(c["rates"]), "runs": c["rates"]},
+                               "producer_thread_cpu_s_per_1000": statistics.median(c["producer_cpu"]),
+                               "process_cpu_s_per_1000": statistics.median(c["process_cpu"]),
+                               "feeds_the_step": statistics.median(c["rates"]) >= STEP_RATE})
+    ok = [c for c in configs if c["entropy"] == "gpu" and c["index_over_stream_bytes"] <= 0.10]
+    best = max(ok, key=lambda c: statistics.median(c["rates"]))
+    out["chosen_sync_mcus"] = best["sync_mcus"]
+    out["gpu_reaches_host_at_two_threads"] = statistics.median(best["rates"]) >= statistics.median(configs[1]["rates"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1024)
@@ -59,8 +153,12 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--streams", default=None, help="directory that keeps the bench's JPEG files: written when Pillow is here, read "
                     "when it is not (a GPU box without Pillow then measures the files made elsewhere)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_loader_bench.json"))
+    ap.add_argument("--entropy", choices=("host", "both"), default="host", help="both: the host / GPU entropy axis (see above)")
+    ap.add_argument("--kernel-only", action="store_true", help="launch the entropy kernel alone, for a profiler")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_loader_bench.json" if args.entropy == "host" else "jpeg_loader_bench_gpu_entropy.json")
     cached = sorted(f for f in os.listdir(args.streams) if f.endswith(".jpg")) if args.streams and os.path.isdir(args.streams) else []
     try:
         from PIL import Image
@@ -91,6 +189,10 @@ def main():
     jpeg_bytes, raw_bytes = sum(len(s) for s in sample_streams), n * H * W * 3
     info = ops.jpeg_probe(streams[0])
     count = int(info.coef_count)
+    if args.kernel_only:
+        t = entropy_kernel_us(sample_streams[:B], shards.DEFAULT_JPEG_SYNC_MCUS, args.reps)
+        print(json.dumps({"entropy_kernel_us_median": statistics.median(t), "B": B, "sync_mcus": shards.DEFAULT_JPEG_SYNC_MCUS}))
+        return 0
 
     # ---- host entropy decode alone ------------------------------------------------------------------------------------------
     result = {"images": f"{H}x{W} 4:2:0 quality 90 (Pillow), {len(streams)} distinct, shard of {n}", "jpeg_bytes_per_image": jpeg_bytes / n,
@@ -168,6 +270,8 @@ def main():
             r = rate(os.path.join(tmp, "jpeg"), decode_threads=T)
             result["threads"][T]["jpeg_loader_samples_per_s"] = {"median": statistics.median(r), "runs": r}
             result["threads"][T]["feeds_the_step"] = statistics.median(r) >= STEP_RATE
+        if args.entropy == "both":
+            result["entropy_axis"] = entropy_axis(args, tmp, sample_streams, common, count)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     result["where"] = f"{torch.cuda.get_device_name(0)}, {torch.get_num_threads()} torch CPU threads, one process"
