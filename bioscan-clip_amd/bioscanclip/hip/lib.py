@@ -101,6 +101,8 @@ SIGNATURES = {
     "bsclip_retrieval_index_build": (I, [P, I, I, P, P]),
     "bsclip_topk_ip_indexed_workspace_floats": (L, [I, I, I]),
     "bsclip_topk_ip_indexed": (I, [P, I, P, I, I, I, P, P, P, P]),
+    "bsclip_retrieval_index_append": (I, [P, I, I, P, I, I, P]),
+    "bsclip_feature_rows": (I, [P, P, P, I, I, L, L, P, P, P, P, P, P]),
     "bsclip_retrieval_hit_ranks": (I, [P, I, I, P, I, P, I, P, P, P]),
     "bsclip_retrieval_class_counts": (I, [P, P, I, I, P, P, I, P, P, P, P]),
     "bsclip_retrieval_match_bits": (I, [P, I, I, P, I, P, I, P, I, I, P, P, P]),

@@ -690,6 +690,47 @@ def topk_ip_indexed(queries, index, K, k):
     return scores, idx
 
 
+def retrieval_index_empty(K, D, device):
+    """A zero-filled index buffer for K keys of width D: what ``retrieval_index_append`` fills and ``topk_ip_indexed`` searches."""
+    _req(K >= 1 and D >= 64 and D % 64 == 0, "retrieval_index_empty: K >= 1, D % 64 == 0")
+    return torch.zeros(_l.load().bsclip_retrieval_index_floats(K, D), dtype=F32, device=device)
+
+
+def retrieval_index_append(index, K, keys, row0):
+    """Rows ``[row0, row0 + n)`` of an index for K keys (``retrieval_index_empty``) from ``keys`` f32 ``[n, D]``: the rows
+    ``retrieval_index_build`` of the whole table would have written, bit for bit."""
+    _req(keys.dim() == 2 and keys.dtype == F32 and keys.is_contiguous() and keys.is_cuda, "retrieval_index_append: contiguous f32 GPU [n,D]")
+    n, D = keys.shape
+    _req(n >= 1 and D % 64 == 0 and 0 <= row0 and row0 + n <= K, "retrieval_index_append: n >= 1, D % 64 == 0, 0 <= row0, row0 + n <= K")
+    _req(index.dtype == F32 and index.is_contiguous() and index.device == keys.device
+         and index.numel() == _l.load().bsclip_retrieval_index_floats(K, D), "retrieval_index_append: index is not that of [K,D] keys")
+    check(_l.load().bsclip_retrieval_index_append(_p(keys), n, D, _p(index), K, int(row0), _stream()))
+
+
+def feature_rows(image, dna, text, row0, t_image=None, t_dna=None, t_text=None, t_avg=None, t_cat=None):
+    """One batch of encoder outputs (each f32 ``[B, D]`` or None) into rows ``[row0, row0 + B)`` of its ``[N, D]`` table (None exactly
+    where the input is), ``(image + dna) * 0.5`` into ``t_avg [N, D]`` and ``[image | dna]`` into ``t_cat [N, 2 D]`` (both optional)."""
+    ins, tabs = (image, dna, text), (t_image, t_dna, t_text)
+    first = next((x for x in ins if x is not None), None)
+    _req(first is not None and first.dim() == 2 and first.is_cuda, "feature_rows: at least one f32 GPU [B,D] input")
+    (B, D), dev = first.shape, first.device
+    given = [t for t in (*tabs, t_avg) if t is not None]
+    _req(len(given) > 0 and given[0].dim() == 2, "feature_rows: a table per input")
+    N = given[0].shape[0]
+    _req(B >= 1 and D % 4 == 0 and 0 <= row0 and row0 + B <= N, "feature_rows: B >= 1, D % 4 == 0, 0 <= row0, row0 + B <= N")
+    for x, t in zip(ins, tabs):
+        _req((x is None) == (t is None), "feature_rows: an input and its table are given together")
+        if x is not None:
+            _req(x.dtype == F32 and x.is_contiguous() and x.device == dev and tuple(x.shape) == (B, D), "feature_rows: inputs contiguous f32 [B,D]")
+    for t, width in (*[(t, D) for t in tabs], (t_avg, D), (t_cat, 2 * D)):
+        if t is not None:
+            _req(t.dtype == F32 and t.is_contiguous() and t.device == dev and tuple(t.shape) == (N, width),
+                 "feature_rows: tables contiguous f32 [N,D] (t_cat [N,2D]) on the inputs' GPU")
+    _req((t_avg is None and t_cat is None) or (image is not None and dna is not None), "feature_rows: t_avg / t_cat need image and dna")
+    check(_l.load().bsclip_feature_rows(_p(image), _p(dna), _p(text), B, D, int(row0), N, _p(t_image), _p(t_dna), _p(t_text), _p(t_avg),
+                                        _p(t_cat), _stream()))
+
+
 def _eval_flag(flag, device):
     if flag is None:
         return torch.zeros(1, dtype=I32, device=device), True

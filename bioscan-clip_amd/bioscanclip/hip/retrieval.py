@@ -99,6 +99,20 @@ class RetrievalIndex:
         self.device = keys.device
         self.index = ops.retrieval_index_build(keys)
 
+    @classmethod
+    def empty(cls, K, D, device=None):
+        """An index of K keys of width D with no row written yet (a zero-filled operand): ``append`` fills it as the keys arrive.
+        Once every row in ``[0, K)`` has been appended it is, bit for bit, ``RetrievalIndex(keys)`` of the whole table."""
+        self = cls.__new__(cls)
+        self.K, self.D = int(K), int(D)
+        self.index = ops.retrieval_index_empty(self.K, self.D, torch.device(device if device is not None else "cuda"))
+        self.device = self.index.device
+        return self
+
+    def append(self, rows, row0):
+        """``rows`` (f32 GPU ``[n, D]``) become the keys ``[row0, row0 + n)``."""
+        ops.retrieval_index_append(self.index, self.K, rows, int(row0))
+
     def search(self, queries, k):
         """(similarities f32 ``[Q, k]``, indices int64 ``[Q, k]``) as GPU tensors -- what ``ops.topk_ip(queries, keys, k)`` returns."""
         return ops.topk_ip_indexed(to_gpu(queries, self.device), self.index, self.K, int(k))
@@ -185,3 +199,108 @@ def evaluate(index, key_label_ids, queries, query_label_ids, k_list, max_k=None,
     hit_rank = ops.retrieval_hit_ranks(idx, kl.dev, ql.dev, flag=flag)
     acc, per_class = score_hit_ranks(hit_rank, ql, k_list, max_k, flag=flag, vocab=vocab, levels=levels)
     return (acc, per_class, idx) if return_indices else (acc, per_class)
+
+
+# ---- the accuracy table of three splits (inference_and_print_result, reference scripts/inference_and_eval.py:633-715) ------------
+
+QUERY_FEATURES = ["encoded_image_feature", "encoded_dna_feature", "encoded_language_feature", "averaged_feature", "concatenated_feature"]
+KEY_FEATURES = QUERY_FEATURES + ["all_key_features"]
+
+
+class HostSplit:
+    """One split given as the host dictionary of ``get_features_and_label`` plus its encoded label ids (``ids[name]`` for ``name`` in
+    ``label_list`` / ``all_key_features_label``), in the form ``score_cells`` reads: every feature uploaded once, every key type's
+    index built once, every label array uploaded once.  ``features.SplitFeatures`` offers the same five methods on tables that
+    never left the GPU."""
+
+    def __init__(self, split, ids):
+        self.split, self.ids = split, ids
+        self._gpu, self._index, self._labels = {}, {}, {}
+
+    def has(self, name):
+        return name in self.split
+
+    def feature(self, name):
+        return self.split[name]
+
+    def query(self, name):
+        if name not in self._gpu:
+            self._gpu[name] = to_gpu(self.split[name])
+        return self._gpu[name]
+
+    def index(self, name):
+        if name not in self._index:
+            self._index[name] = RetrievalIndex(self.split[name])
+        return self._index[name]
+
+    def labels(self, name="label_list"):
+        if name not in self._labels:
+            self._labels[name] = Labels(self.ids[name])
+        return self._labels[name]
+
+    def label_dicts(self, name="label_list"):
+        return self.split[name]
+
+
+def score_cells(keys, seen, unseen, k_list, vocab, with_predictions=False):
+    """The cell loop of ``inference_and_print_result`` on splits resident on the GPU (``HostSplit`` or ``features.SplitFeatures``):
+    the same order, skip rules and sticky ``all_key_features_label`` rule.  Returns ``(acc_dict, per_class_acc, pred_dict)``;
+    ``pred_dict[q][kf]`` holds the int64 ``[Q, max_k]`` GPU index tensors (``curr_seen_indices`` / ``curr_unseen_indices``), or with
+    ``with_predictions`` the host path's string lists (``curr_seen_pred_list`` / ``curr_unseen_pred_list``)."""
+    max_k = k_list[-1]
+    acc_dict, per_class_acc, pred_dict = {}, {}, {}
+    keys_label = "label_list"
+    for q in QUERY_FEATURES:
+        if not seen.has(q):
+            continue
+        acc_dict[q], per_class_acc[q], pred_dict[q] = {}, {}, {}
+        for kf in KEY_FEATURES:
+            if not keys.has(kf):
+                continue
+            acc_dict[q][kf], per_class_acc[q][kf], pred_dict[q][kf] = {}, {}, {}
+            key_f, seen_f, unseen_f = keys.feature(kf), seen.feature(q), unseen.feature(q)
+            if key_f is None:
+                continue
+            if kf == "all_key_features":
+                keys_label = "all_key_features_label"  # sticks for later key types, as in the reference (:666)
+            if seen_f is None or unseen_f is None or key_f.shape[-1] != seen_f.shape[-1] or key_f.shape[-1] != unseen_f.shape[-1]:
+                continue
+            for s, split in (("seen", seen), ("unseen", unseen)):
+                acc, per_class, idx = evaluate(keys.index(kf), keys.labels(keys_label), split.query(q), split.labels(), k_list,
+                                               max_k=max_k, vocab=vocab, levels=LEVELS, return_indices=True)
+                acc_dict[q][kf][s], per_class_acc[q][kf][s] = acc, per_class
+                if with_predictions:
+                    names = keys.label_dicts(keys_label)
+                    pred_dict[q][kf][f"curr_{s}_pred_list"] = [{level: [names[i][level] for i in row] for level in LEVELS}
+                                                              for row in idx.cpu().numpy()]
+                else:
+                    pred_dict[q][kf][f"curr_{s}_indices"] = idx
+    return acc_dict, per_class_acc, pred_dict
+
+
+def print_accuracy_table(acc_dict, k_list):
+    """The printed table of the reference's ``print_micro_and_macro_acc``: one line per (query type, key type, kind, k)."""
+    for q in QUERY_FEATURES:
+        for kf in KEY_FEATURES:
+            cell = acc_dict.get(q, {}).get(kf)
+            if not cell:
+                continue
+            for kind in ("micro_acc", "macro_acc"):
+                for k in k_list:
+                    nums = [round(cell[s][kind][k][level], 4) for s in ("seen", "unseen") for level in LEVELS]
+                    print(f"Query_feature: {q}||Key_feature: {kf}||{kind} top-{k}\t" + "\t".join(map(str, nums)))
+
+
+def evaluate_resident(keys, seen, unseen, k_list=None, args=None, with_predictions=False):
+    """``inference_and_print_result_gpu`` on three ``features.SplitFeatures``: the tables, the key indices filled during extraction and
+    the ``Labels`` are read where they are -- nothing is downloaded, uploaded or encoded again.  The three splits must share one
+    vocabulary (``features.extract_splits``, or ``shards.taxonomy_ids`` over the three shards).  Same cell loop (``score_cells``),
+    printed table and return value."""
+    if k_list is None:
+        k_list = [1, 3, 5]
+    if not (keys.vocab == seen.vocab == unseen.vocab):
+        raise ValueError("evaluate_resident: the three splits were encoded with different vocabularies; encode their labels together "
+                         "(features.extract_splits, or shards.taxonomy_ids over the three shards)")
+    result = score_cells(keys, seen, unseen, k_list, keys.vocab, with_predictions=with_predictions)
+    print_accuracy_table(result[0], k_list)
+    return result

@@ -276,6 +276,48 @@ class Shard:
         return [{t: self.taxonomy[t][i].decode() for t in _TAXA} for i in idx]
 
 
+LEVELS = _TAXA
+EVAL_SPLITS = {"val": ("all_keys", "val_seen", "val_unseen"), "test": ("all_keys", "test_seen", "test_unseen")}
+
+
+def eval_splits(root, which="val"):
+    """The (keys, seen, unseen) shard directories of an evaluation root: a directory whose sub-directories are shards named after the
+    reference's splits (dataset.py:371-530) -- ``all_keys`` and ``val_seen`` / ``val_unseen`` or ``test_seen`` / ``test_unseen``.
+    Other sub-directories are ignored; a split that is absent or is not a shard raises ValueError."""
+    if which not in EVAL_SPLITS:
+        raise ValueError(f"eval split must be one of {tuple(EVAL_SPLITS)}, got {which!r}")
+    paths = []
+    for name in EVAL_SPLITS[which]:
+        path = os.path.join(str(root), name)
+        if not is_shard(path):
+            raise ValueError(f"{root}: no shard for the split {name!r} (an evaluation root holds the shard directories "
+                             f"{', '.join(EVAL_SPLITS[which])})")
+        paths.append(path)
+    return tuple(paths)
+
+
+def taxonomy_ids(shard_list, levels=LEVELS):
+    """``hip/retrieval.encode_labels`` of the shards' ``label_dicts`` (every sample, in the given order) without building them:
+    returns ``(arrays, vocab)``, one int32 ``[n, L]`` array per shard and ``vocab[level]`` = the names in id order.  Ids are handed
+    out per level in order of first appearance over the shards in turn; equal strings get equal ids.  Works on the memory-mapped
+    byte arrays with ``np.unique``: no Python loop over samples."""
+    shard_list = [Shard(s) if isinstance(s, str) else s for s in shard_list]
+    levels = list(levels)
+    counts = [len(s) for s in shard_list]
+    ids = np.empty((sum(counts), len(levels)), dtype=np.int32)
+    vocab = {}
+    for j, lv in enumerate(levels):
+        names = np.concatenate([np.asarray(s.taxonomy[lv]) for s in shard_list]) if shard_list else np.zeros(0, dtype="S1")
+        uniq, first, inverse = np.unique(names, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")            # the distinct names in order of first appearance
+        rank = np.empty(len(uniq), dtype=np.int32)
+        rank[order] = np.arange(len(uniq), dtype=np.int32)
+        ids[:, j] = rank[inverse.reshape(-1)]
+        vocab[lv] = [v.decode() for v in uniq[order].tolist()]
+    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return [np.ascontiguousarray(ids[bounds[i]:bounds[i + 1]]) for i in range(len(shard_list))], vocab
+
+
 class _Range(torch.utils.data.Dataset):
     def __init__(self, n):
         self.n = n

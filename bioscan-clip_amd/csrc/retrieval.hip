@@ -304,6 +304,80 @@ extern "C" int bsclip_retrieval_index_build(const float* keys, int K, int D, flo
     return BSCLIP_OK;
 }
 
+// The key side for rows [row0, row0 + n) of an index the caller zero-filled: the rows a batch of key features becomes, written as
+// they arrive.  A row's operand depends on that row alone (one wave per row), and the pad rows bsclip_retrieval_index_build writes
+// are zero bits, so appends that cover [0, K) leave the buffer bsclip_retrieval_index_build(keys[K, D]) leaves.
+extern "C" int bsclip_retrieval_index_append(const float* keys, int n, int D, float* index, int K_capacity, int row0, void* stream) {
+    BSCLIP_REQUIRE(keys && index, "bsclip_retrieval_index_append: null pointer");
+    BSCLIP_REQUIRE(n > 0 && K_capacity > 0 && D > 0 && D % 64 == 0, "bsclip_retrieval_index_append: n=%d K_capacity=%d D=%d (D %% 64 == 0)",
+                   n, K_capacity, D);
+    BSCLIP_REQUIRE(row0 >= 0 && (int64_t)row0 + n <= K_capacity, "bsclip_retrieval_index_append: row0=%d + n=%d exceeds K_capacity=%d",
+                   row0, n, K_capacity);
+    BSCLIP_REQUIRE(aligned_to(16, keys, index), "bsclip_retrieval_index_append: keys and index must be 16-B aligned");
+    hipLaunchKernelGGL((normalize_split4_kernel<true>), dim3(ceil_div(n, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), keys, n,
+                       n, D, reinterpret_cast<bf16_t*>(index) + (size_t)row0 * 4 * D);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+// ---- feature tables: a batch of encoder outputs into rows [row0, row0 + B) of the split's resident tables ----------------------
+// get_features_and_label (scripts/inference_and_eval.py:734-784) keeps, per split, the image / DNA / text features and two derived
+// ones: averaged_feature = np.mean([image, dna], axis=0) and concatenated_feature = np.concatenate((image, dna), axis=1).
+
+namespace {
+
+struct FeatureRows {
+    const float* in[3];  // image, dna, text: [B, D], nullable
+    float* table[3];     // their [N, D] tables, null exactly where the input is
+    float* avg;          // [N, D], nullable
+    float* cat;          // [N, 2 D], nullable
+};
+
+// One lane per 16-byte chunk of a row; every branch on a pointer is kernel-uniform.  (a + b) * 0.5f: the sum rounds once and the
+// halving is exact, which is the f32 rounding of the float64 mean numpy forms from two f32 values.
+__global__ __launch_bounds__(256) void feature_rows_kernel(FeatureRows f, int B, int D4, int64_t row0) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * D4) return;
+    const int b = (int)(i / D4), c = (int)(i % D4) * 4, D = D4 * 4;
+    const size_t src = (size_t)b * D + c, row = (size_t)(row0 + b);
+    f32x4 v[3] = {};
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        if (!f.in[m]) continue;
+        v[m] = ld_stream(reinterpret_cast<const f32x4*>(f.in[m] + src));
+        st_stream(f.table[m] + row * D + c, v[m]);
+    }
+    if (f.avg) st_stream(f.avg + row * D + c, (v[0] + v[1]) * 0.5f);
+    if (f.cat) {
+        st_stream(f.cat + row * 2 * D + c, v[0]);
+        st_stream(f.cat + row * 2 * D + D + c, v[1]);
+    }
+}
+
+}  // namespace
+
+extern "C" int bsclip_feature_rows(const float* image, const float* dna, const float* text, int B, int D, int64_t row0, int64_t N,
+                                   float* t_image, float* t_dna, float* t_text, float* t_avg, float* t_cat, void* stream) {
+    BSCLIP_REQUIRE(B >= 1 && D >= 4 && D % 4 == 0, "bsclip_feature_rows: B=%d D=%d (B >= 1, D %% 4 == 0)", B, D);
+    BSCLIP_REQUIRE(row0 >= 0, "bsclip_feature_rows: row0=%lld (>= 0)", (long long)row0);
+    BSCLIP_REQUIRE(row0 <= N - B, "bsclip_feature_rows: row0=%lld + B=%d exceeds N=%lld", (long long)row0, B, (long long)N);
+    BSCLIP_REQUIRE(image || dna || text, "bsclip_feature_rows: no input (image, dna and text are all null)");
+    BSCLIP_REQUIRE(!image == !t_image, "bsclip_feature_rows: image and t_image must be given together");
+    BSCLIP_REQUIRE(!dna == !t_dna, "bsclip_feature_rows: dna and t_dna must be given together");
+    BSCLIP_REQUIRE(!text == !t_text, "bsclip_feature_rows: text and t_text must be given together");
+    BSCLIP_REQUIRE(!t_avg || (image && dna), "bsclip_feature_rows: t_avg needs both image and dna");
+    BSCLIP_REQUIRE(!t_cat || (image && dna), "bsclip_feature_rows: t_cat needs both image and dna");
+    BSCLIP_REQUIRE(aligned_to(16, image, dna, text, t_image, t_dna, t_text, t_avg, t_cat),
+                   "bsclip_feature_rows: inputs and tables must be 16-B aligned");
+    const FeatureRows f = {{image, dna, text}, {t_image, t_dna, t_text}, t_avg, t_cat};
+    const int64_t chunks = (int64_t)B * (D / 4);
+    BSCLIP_REQUIRE(chunks <= (int64_t)0x7fffffff * 256, "bsclip_feature_rows: B=%d x D=%d is too large for one launch", B, D);
+    hipLaunchKernelGGL(feature_rows_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), f, B,
+                       D / 4, row0);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
 extern "C" int64_t bsclip_topk_ip_indexed_workspace_floats(int Q, int K, int D) {
     if (Q <= 0 || K <= 0 || D <= 0) return -1;
     const int64_t Kp = pad_keys(K), Qs = Q < TOPK_SLAB ? Q : TOPK_SLAB;

@@ -11,6 +11,10 @@ Mirrored entry points (same names, argument meaning and return shapes as the ref
     main                       :786-871   (config -> load_clip_model -> checkpoint unless load_ckpt=false -> features -> table;
                                            splits from the synthetic evaluation loaders, feature cache as .npz)
 
+``eval_shards=<root>`` evaluates a directory of shard splits (``shards.eval_splits``; ``eval_split=val|test``) instead of the synthetic
+loaders: every split is walked once with all towers per batch (``bioscanclip/hip/features.py``), and with ``hip_eval=gpu`` the features,
+key indices and label ids never leave the GPU (``retrieval.evaluate_resident``).
+
 ``hip_eval=gpu`` (default ``host``) selects ``inference_and_print_result_gpu``: the same cell table with one key index per key type
 (built once, searched by every query type and both splits), labels as int32 ids, and hit matching / per-class counting as HIP
 kernels (``bioscanclip/hip/retrieval.py``); the tables are equal to the host path's, bit for bit.
@@ -25,16 +29,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from bioscanclip.epoch.inference_epoch import get_feature_and_label  # noqa: E402
 from bioscanclip.hip import ops  # noqa: E402
-from bioscanclip.hip.retrieval import LEVELS, to_gpu  # noqa: E402
+from bioscanclip.hip.retrieval import KEY_FEATURES, LEVELS, QUERY_FEATURES, print_accuracy_table, to_gpu  # noqa: E402
 
-All_TYPE_OF_FEATURES_OF_QUERY = [
-    "encoded_image_feature",
-    "encoded_dna_feature",
-    "encoded_language_feature",
-    "averaged_feature",
-    "concatenated_feature",
-]
-All_TYPE_OF_FEATURES_OF_KEY = All_TYPE_OF_FEATURES_OF_QUERY + ["all_key_features"]
+All_TYPE_OF_FEATURES_OF_QUERY = QUERY_FEATURES
+All_TYPE_OF_FEATURES_OF_KEY = KEY_FEATURES
 
 
 def search_topk(query_feature, keys_feature, max_k, device=None):
@@ -126,15 +124,7 @@ def get_features_and_label(dataloader, model, device, for_key_set=False, for_ope
 
 
 def print_micro_and_macro_acc(acc_dict, k_list, args=None):
-    for q in All_TYPE_OF_FEATURES_OF_QUERY:
-        for kf in All_TYPE_OF_FEATURES_OF_KEY:
-            cell = acc_dict.get(q, {}).get(kf)
-            if not cell:
-                continue
-            for kind in ("micro_acc", "macro_acc"):
-                for k in k_list:
-                    nums = [round(cell[s][kind][k][level], 4) for s in ("seen", "unseen") for level in LEVELS]
-                    print(f"Query_feature: {q}||Key_feature: {kf}||{kind} top-{k}\t" + "\t".join(map(str, nums)))
+    print_accuracy_table(acc_dict, k_list)
 
 
 def inference_and_print_result(keys_dict, seen_dict, unseen_dict, args=None, small_species_list=None, k_list=None):
@@ -205,68 +195,51 @@ def inference_and_print_result_gpu(keys_dict, seen_dict, unseen_dict, args=None,
     and ``per_class_acc``.  Every key type's index is built once and every query feature uploaded once; the labels are encoded to
     int32 ids once per call.  ``pred_dict[q][kf]`` holds the int64 ``[Q, max_k]`` GPU index tensors (``curr_seen_indices`` /
     ``curr_unseen_indices``); ``with_predictions=True`` builds the host path's string lists from them instead."""
-    from bioscanclip.hip.retrieval import Labels, RetrievalIndex, encode_labels, evaluate
+    from bioscanclip.hip.retrieval import HostSplit, encode_labels, score_cells
     if k_list is None:
         k_list = [1, 3, 5]
-    max_k = k_list[-1]
-    acc_dict, per_class_acc, pred_dict = {}, {}, {}
     label_lists = {"label_list": keys_dict["label_list"], "all_key_features_label": keys_dict.get("all_key_features_label") or [],
                    "seen": seen_dict["label_list"], "unseen": unseen_dict["label_list"]}
     arrays, vocab = encode_labels(*label_lists.values(), levels=LEVELS)
     label_ids = dict(zip(label_lists, arrays))
-    uploaded, indices, queries = {}, {}, {}
-
-    def labels_of(name):
-        if name not in uploaded:
-            uploaded[name] = Labels(label_ids[name])
-        return uploaded[name]
-
-    def query_of(split, q, feature):
-        if (split, q) not in queries:
-            queries[split, q] = to_gpu(feature)
-        return queries[split, q]
-
-    keys_label = "label_list"
-    for q in All_TYPE_OF_FEATURES_OF_QUERY:
-        if q not in seen_dict:
-            continue
-        acc_dict[q], per_class_acc[q], pred_dict[q] = {}, {}, {}
-        for kf in All_TYPE_OF_FEATURES_OF_KEY:
-            if kf not in keys_dict:
-                continue
-            acc_dict[q][kf], per_class_acc[q][kf], pred_dict[q][kf] = {}, {}, {}
-            keys, seen, unseen = keys_dict[kf], seen_dict[q], unseen_dict[q]
-            if keys is None:
-                continue
-            if kf == "all_key_features":
-                keys_label = "all_key_features_label"  # sticks for later key types, as in the reference (:666)
-            if seen is None or unseen is None or keys.shape[-1] != seen.shape[-1] or keys.shape[-1] != unseen.shape[-1]:
-                continue
-            if kf not in indices:
-                indices[kf] = RetrievalIndex(keys)
-            for s, feature in (("seen", seen), ("unseen", unseen)):
-                acc, per_class, idx = evaluate(indices[kf], labels_of(keys_label), query_of(s, q, feature), labels_of(s), k_list,
-                                               max_k=max_k, vocab=vocab, levels=LEVELS, return_indices=True)
-                acc_dict[q][kf][s], per_class_acc[q][kf][s] = acc, per_class
-                if with_predictions:
-                    names = label_lists[keys_label]
-                    pred_dict[q][kf][f"curr_{s}_pred_list"] = [{level: [names[i][level] for i in row] for level in LEVELS}
-                                                              for row in idx.cpu().numpy()]
-                else:
-                    pred_dict[q][kf][f"curr_{s}_indices"] = idx
+    keys = HostSplit(dict(keys_dict, all_key_features_label=label_lists["all_key_features_label"]),
+                     {name: label_ids[name] for name in ("label_list", "all_key_features_label")})
+    seen, unseen = HostSplit(seen_dict, {"label_list": label_ids["seen"]}), HostSplit(unseen_dict, {"label_list": label_ids["unseen"]})
+    acc_dict, per_class_acc, pred_dict = score_cells(keys, seen, unseen, k_list, vocab, with_predictions=with_predictions)
     print_micro_and_macro_acc(acc_dict, k_list, args)
     return acc_dict, per_class_acc, pred_dict
+
+
+EVAL_SPLITS = ("val", "test")
+
+
+def shard_eval_loaders(args, with_text, which=None, batch_size=24):
+    """The (keys, seen, unseen) evaluation loaders of ``eval_shards=<root>`` (``shards.eval_splits``): ``ShardLoader`` in evaluation mode
+    (Resize -> CenterCrop, no shuffle) at the reference's batch 24 (:846); ``eval_split=val|test`` (default val) picks the query
+    splits and ``hip_jpeg_entropy=host|gpu`` (default host) says where a JPEG shard's streams are Huffman-decoded."""
+    from bioscanclip.util import shards
+    which = str(getattr(args, "eval_split", "val")) if which is None else which
+    if which not in EVAL_SPLITS:
+        raise ValueError(f"eval_split must be one of {EVAL_SPLITS}, not {which!r}")
+    entropy = getattr(args, "hip_jpeg_entropy", None)
+    entropy = "host" if entropy is None or entropy == "" else str(entropy)
+    if entropy not in shards.ENTROPY_MODES:
+        raise ValueError(f"hip_jpeg_entropy must be one of {shards.ENTROPY_MODES}, got {entropy!r}")
+    return [shards.ShardLoader(path, batch_size, for_training=False, shuffle=False, with_text=with_text, entropy=entropy)
+            for path in shards.eval_splits(str(args.eval_shards), which)]
 
 
 def main(argv=None):
     """Reference entry (scripts/inference_and_eval.py:786-871): config -> ``load_clip_model`` -> checkpoint
     (``model_config.ckpt_path`` unless ``model_config.load_ckpt`` is false, :839-843) -> features of the key / seen / unseen
     splits -> accuracy table.  The HDF5 splits are not available here: the splits come from the synthetic
-    evaluation loaders; extracted features are cached as ``.npz`` (h5py is absent) under the reference's directory layout
+    evaluation loaders, or with ``eval_shards=<root>`` from a directory of shard splits (``shard_eval_loaders``); extracted features
+    are cached as ``.npz`` (h5py is absent) under the reference's directory layout
     (``extracted_embedding/<dataset>/<model_output_name>/``) and reused with ``load_inference=true`` (:797-833).
     ``hip_operands=fp16`` (default bf16) runs the three encoders on fp16 operands (``set_operand_format``); the cache records the
     format it was extracted with and is reused only by a run of the same format.  ``hip_eval=gpu`` (default host) scores the
-    table with ``inference_and_print_result_gpu``."""
+    table with ``inference_and_print_result_gpu``.  Shard splits are walked once (``features.extract_split``); with ``hip_eval=gpu``
+    their features, key indices and label ids stay on the GPU through the scoring (``retrieval.evaluate_resident``)."""
     from bioscanclip.hip.engine import OPERAND_FORMATS, set_operand_format
     from bioscanclip.util.config import load_config
     from bioscanclip.util.synthetic import SyntheticEvalLoader
@@ -275,17 +248,21 @@ def main(argv=None):
     args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
     mc = args.model_config
     evaluate_splits = select_eval(args)
+    from_shards = getattr(args, "eval_shards", None) not in (None, "")
+    which = str(getattr(args, "eval_split", "val"))
+    if from_shards and which not in EVAL_SPLITS:
+        raise ValueError(f"eval_split must be one of {EVAL_SPLITS}, not {which!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("inference_and_eval needs a ROCm GPU: the encoders and the top-k search run in libbsclip_hip.so")
     device = torch.device("cuda", 0)
     k_list = _k_list(args)
     root = str(getattr(args, "project_root_path", "."))
     folder = os.path.join(root, "extracted_embedding", str(getattr(mc, "dataset", "synthetic")), str(mc.model_output_name))
-    feats_path = os.path.join(folder, "extracted_feature_from_val_split.npz")
+    feats_path = os.path.join(folder, f"extracted_feature_from_{which if from_shards else 'val'}_split.npz")
     operands = str(getattr(args, "hip_operands", "bf16"))
     if operands not in OPERAND_FORMATS:
         raise ValueError(f"hip_operands must be one of {OPERAND_FORMATS}, not {operands!r}")
-    splits = None
+    splits, resident = None, None
     if getattr(args, "load_inference", False) and os.path.exists(feats_path):
         z = np.load(feats_path, allow_pickle=True)
         cached = str(z["operands"]) if "operands" in z.files else "bf16"   # caches from before the switch were extracted on bf16
@@ -299,19 +276,31 @@ def main(argv=None):
         set_operand_format(model, operands)
         model.eval()
         with_text = hasattr(mc, "language")
-        bs, n = 24, int(getattr(args, "synthetic_eval_batches", 2))   # the reference evaluates at batch 24 (:846)
-        mk = lambda seed: SyntheticEvalLoader(bs, n, with_text=with_text, seed=seed)
-        splits = [get_features_and_label(mk(4321), model, device, for_key_set=True),
-                  get_features_and_label(mk(4322), model, device), get_features_and_label(mk(4323), model, device)]
+        if from_shards:
+            from bioscanclip.hip.features import extract_splits
+            resident = extract_splits(shard_eval_loaders(args, with_text, which), model, device, index=eval_mode(args) == "gpu")
+            if eval_mode(args) == "host" or getattr(args, "save_inference", False):
+                splits = [split.as_dict() for split in resident]
+        else:
+            bs, n = 24, int(getattr(args, "synthetic_eval_batches", 2))   # the reference evaluates at batch 24 (:846)
+            mk = lambda seed: SyntheticEvalLoader(bs, n, with_text=with_text, seed=seed)
+            splits = [get_features_and_label(mk(4321), model, device, for_key_set=True),
+                      get_features_and_label(mk(4322), model, device), get_features_and_label(mk(4323), model, device)]
         if getattr(args, "save_inference", False):
             os.makedirs(folder, exist_ok=True)
             np.savez(feats_path, keys=np.array(splits[0], dtype=object), seen=np.array(splits[1], dtype=object),
                      unseen=np.array(splits[2], dtype=object), operands=np.array(operands))
-    keys_dict, seen_dict, unseen_dict = splits
-    result = evaluate_splits(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
+    if resident is not None and eval_mode(args) == "gpu":
+        from bioscanclip.hip.retrieval import evaluate_resident
+        result = evaluate_resident(*resident, k_list=k_list, args=args)
+        queries = [(s.tables["encoded_image_feature"], s.file_name_list, s.label_dicts()) for s in resident[1:]]
+    else:
+        keys_dict, seen_dict, unseen_dict = splits
+        result = evaluate_splits(keys_dict, seen_dict, unseen_dict, args, small_species_list=None, k_list=k_list)
+        queries = [(s["encoded_image_feature"], s["file_name_list"], s["label_list"]) for s in (seen_dict, unseen_dict)]
     if _silhouette(args):
-        for split in (seen_dict, unseen_dict):
-            calculate_silhouette_score(args, split["encoded_image_feature"], (split["file_name_list"], split["label_list"]))
+        for image_features, names, label_list in queries:
+            calculate_silhouette_score(args, image_features, (names, label_list))
     return result
 
 

@@ -14,7 +14,8 @@ AdamW (+ optional one_cycle / exponential / step / cosine scheduler, stepped per
     ``dataset=synthetic_raw`` feeds raw uint8 images + nucleotide strings through the GPU input pipeline (the reference's
     augmentation chain and 5-mer tokeniser as HIP kernels, bioscanclip/util/gpu_pipeline.py);
   * the per-epoch evaluation (``eval_phase``, reference train_cl.py:217-243) runs natively: feature extraction with the HIP
-    encoders and top-k retrieval with ``bsclip_topk_ip`` in place of faiss.
+    encoders and top-k retrieval with ``bsclip_topk_ip`` in place of faiss, on the synthetic evaluation loaders
+    (``synthetic_eval=true``) or on the val splits of a directory of shard splits (``eval_shards=<root>``, ``eval_phase_shards``).
 """
 import datetime
 import os
@@ -67,6 +68,35 @@ def eval_phase(model, device, all_keys_dataloader, seen_val_dataloader, unseen_v
     acc_dict, _, pred_dict = inference_and_print_result(keys_dict, seen_val_dict, unseen_val_dict, args=args,
                                                         small_species_list=None, k_list=k_list)
     return acc_dict, pred_dict
+
+
+def eval_phase_shards(model, device, loaders, k_list, args):
+    """``eval_phase`` on the (keys, seen, unseen) ``ShardLoader``s of ``eval_shards=<root>``: every split is walked once with all towers
+    per batch (``features.extract_splits``).  ``hip_eval=gpu`` scores the resident tables (``retrieval.evaluate_resident``); the default
+    ``host`` hands their host dictionaries to ``inference_and_print_result``.  Same return value as ``eval_phase``."""
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    from inference_and_eval import eval_mode, inference_and_print_result
+    from bioscanclip.hip.features import extract_splits
+    from bioscanclip.hip.retrieval import evaluate_resident
+    on_gpu = eval_mode(args) == "gpu"        # refuses an unknown hip_eval before any feature is extracted
+    splits = extract_splits(loaders, model, device, index=on_gpu)
+    if on_gpu:
+        acc_dict, _, pred_dict = evaluate_resident(*splits, k_list=k_list, args=args)
+    else:
+        acc_dict, _, pred_dict = inference_and_print_result(*[s.as_dict() for s in splits], args=args, small_species_list=None,
+                                                            k_list=k_list)
+    return acc_dict, pred_dict
+
+
+def eval_source(args):
+    """Where the per-epoch evaluation reads its splits: ``"synthetic"`` (``synthetic_eval=true``), ``"shards"`` (``eval_shards=<root>``) or
+    None for no evaluation.  Both at once is refused here, before any GPU work."""
+    synthetic = bool(getattr(args, "synthetic_eval", False))
+    from_shards = getattr(args, "eval_shards", None) not in (None, "")
+    if synthetic and from_shards:
+        raise ValueError("synthetic_eval=true and eval_shards=<root> both name the evaluation splits: give one of them")
+    return "synthetic" if synthetic else "shards" if from_shards else None
 
 
 def ddp_setup(rank: int, world_size: int, port):
@@ -209,7 +239,13 @@ def main_process(rank: int, world_size: int, args):
 
     broadcast_model(model, rank)  # before the first step, like the reference (train_cl.py:149)
     eval_loaders = None
-    if getattr(args, "synthetic_eval", False):
+    if eval_source(args) == "shards" and rank == 0:
+        # the val splits of an evaluation root (shards.eval_splits), at the reference's evaluation batch 24
+        if HERE not in sys.path:
+            sys.path.insert(0, HERE)
+        from inference_and_eval import shard_eval_loaders
+        eval_loaders = shard_eval_loaders(args, with_text, "val")
+    elif eval_source(args) == "synthetic":
         n_eval = int(getattr(args, "synthetic_eval_batches", 2))
         eval_loaders = [SyntheticEvalLoader(min(int(mc.batch_size), 24), n_eval, with_text=with_text, seed=s_)
                         for s_ in (7001, 7002, 7003)]  # keys, seen, unseen
@@ -229,7 +265,10 @@ def main_process(rank: int, world_size: int, args):
                 torch.save(model.state_dict(), last_ckpt_path)  # reference key names: loadable by the reference
                 print(f'Last ckpt: {last_ckpt_path}')
             if eval_loaders is not None:
-                acc_dict, _ = eval_phase(model, device, *eval_loaders, k_list, args=args, rank=rank)
+                if eval_source(args) == "shards":
+                    acc_dict, _ = eval_phase_shards(model, device, eval_loaders, k_list, args)
+                else:
+                    acc_dict, _ = eval_phase(model, device, *eval_loaders, k_list, args=args, rank=rank)
                 cell = acc_dict['encoded_image_feature']['encoded_image_feature']
                 overall_acc = (cell['seen']['micro_acc'][1]['species'] + cell['unseen']['micro_acc'][1]['species']) / 2
                 if best_overall_acc is None or best_overall_acc < overall_acc:
@@ -251,6 +290,7 @@ def main(argv=None):
         raise SystemExit("usage: train_cl.py 'model_config=<name>' [key=value ...]")
     fp16_towers(args)   # refuse an unbuilt fp16 backward before any GPU work
     jpeg_entropy_mode(args)
+    eval_source(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     print_when_rank_zero(f'world_size: {world_size}', rank)

@@ -401,6 +401,18 @@ int bsclip_retrieval_index_build(const float* keys, int K, int D, float* index, 
 int64_t bsclip_topk_ip_indexed_workspace_floats(int Q, int K, int D);
 int bsclip_topk_ip_indexed(const float* queries, int Q, const float* index, int K, int D, int k, float* scores_out,
                            int64_t* idx_out, float* workspace, void* stream);
+/* The key side of bsclip_retrieval_index_build for rows [row0, row0 + n) of an index sized by
+ * bsclip_retrieval_index_floats(K_capacity, D) that the caller has zero-filled: keys f32 [n, D] become those rows of the operand.
+ * Any sequence of appends covering [0, K) leaves the buffer bit-identical to bsclip_retrieval_index_build of the whole [K, D] table
+ * (the zero pad rows included); bsclip_topk_ip_indexed reads it unchanged.  D % 64 == 0, row0 + n <= K_capacity, 16-B aligned. */
+int bsclip_retrieval_index_append(const float* keys, int n, int D, float* index, int K_capacity, int row0, void* stream);
+/* Feature tables of one evaluation split (get_features_and_label, scripts/inference_and_eval.py:734-784), filled a batch at a time:
+ * rows [row0, row0 + B) of each given table f32 [N, D] receive the rows of its input f32 [B, D] unchanged; t_avg [N, D] receives
+ * (image + dna) * 0.5f (averaged_feature: the f32 rounding of numpy's float64 mean of two f32 values) and t_cat [N, 2 D] receives
+ * [image | dna] (concatenated_feature).  image / dna / text are nullable, each together with its table; t_avg and t_cat are
+ * nullable and need both image and dna.  D % 4 == 0, B >= 1, 0 <= row0, row0 + B <= N, every pointer 16-B aligned.  One launch. */
+int bsclip_feature_rows(const float* image, const float* dna, const float* text, int B, int D, int64_t row0, int64_t N,
+                        float* t_image, float* t_dna, float* t_text, float* t_avg, float* t_cat, void* stream);
 /* Scoring on integer label ids (make_prediction's label lookup :424-437, top_k_micro_accuracy :448-464, top_k_macro_accuracy
  * :467-511); integers only, the caller forms the ratios.
  *   hit_ranks: idx int64 [Q, k] (k <= 16), key_labels int32 [K, L], query_labels int32 [Q, L], L <= 8 levels ->
