@@ -207,19 +207,21 @@ def test_gemm_patch_epilogue(ops):
     a = dev(rnd(B * 196, 768, seed=1).bfloat16())
     w = dev(rnd(768, 768, seed=2, scale=0.05).bfloat16())
     bias, pos = dev(rnd(768, seed=3)), dev(rnd(197, 768, seed=4))
-    out = torch.zeros(B * 197, 768, device="cuda")
+    out = torch.full((B * 197, 768), float("nan"), device="cuda")      # NaN, not zeros: a class row the kernel wrote zeros to shows
     ops.gemm(a, w, out, EPI_PATCH_F32, bias=bias, resid=pos)
     ref = (a.float() @ w.float().t() + bias).reshape(B, 196, 768) + pos[1:]
     got = out.reshape(B, 197, 768)
     assert rel_err(got[:, 1:], ref) < TOL_F32
-    assert (got[:, 0] == 0).all()
+    assert torch.isnan(got[:, 0]).all(), "a class-token row was written"
     from bioscanclip.hip.lib import EPI_PATCH_BF16
     for tile in (1, 4, 5):
         ops.set_gemm_tile(tile)
-        out16 = torch.zeros(B * 197, 768, device="cuda", dtype=torch.bfloat16)
+        out16 = torch.full((B * 197, 768), float("nan"), device="cuda", dtype=torch.bfloat16)
         ops.gemm(a, w, out16, EPI_PATCH_BF16, bias=bias, resid=pos)
         ops.set_gemm_tile(0)
-        assert torch.equal(out16, out.bfloat16()), f"tile {tile}"      # the f32 result rounded once; row 0 of each image untouched
+        got16 = out16.reshape(B, 197, 768)
+        assert torch.equal(got16[:, 1:], got[:, 1:].bfloat16()), f"tile {tile}"      # the f32 result rounded once
+        assert torch.isnan(got16[:, 0]).all(), f"tile {tile}: a class-token row was written"
 
 
 def test_gemm_rejects_bad_shapes(ops):
