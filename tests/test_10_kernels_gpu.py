@@ -244,8 +244,8 @@ def test_layernorm_fwd_bwd(ops, H, eps, xbf16):
     A = dev(rnd(8, H, seed=4, scale=0.05))
     ld = H + 64
     y16 = torch.full((M, ld), 7.0, device="cuda", dtype=torch.bfloat16)
-    y32 = torch.empty(M, H, device="cuda")
-    stats = torch.empty(M, 2, device="cuda")
+    y32 = torch.full((M, H), float("nan"), device="cuda")
+    stats = torch.full((M, 2), float("nan"), device="cuda")
     ops.layernorm_fwd(x, g, b, eps, y_bf16=y16, y_f32=y32, lora_a=A, stats=stats)
     xf = x.float().requires_grad_(True)
     ref = torch.nn.functional.layer_norm(xf, (H,), g, b, eps)
@@ -255,7 +255,7 @@ def test_layernorm_fwd_bwd(ops, H, eps, xbf16):
     assert (y16[:, H + 8:] == 0).all()
     assert rel_err(stats[:, 0], xf.mean(-1)) < 1e-4
     # plain variant (no lora, no f32 copy)
-    y16b = torch.empty(M, H, device="cuda", dtype=torch.bfloat16)
+    y16b = torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16)
     ops.layernorm_fwd(x, g, b, eps, y_bf16=y16b, stats=stats)
     assert rel_err(y16b.float(), ref) < TOL_BF16
 
@@ -270,15 +270,15 @@ def test_layernorm_fwd_bwd(ops, H, eps, xbf16):
                 dy_ln = dy_ln + g_resid
             (gx,) = torch.autograd.grad(ref, xf, dy_ln, retain_graph=True)
             want = gx + (g_resid if mode == 0 else 0)
-            dx32 = torch.empty(M, H, device="cuda")
-            dx16 = torch.empty(M, H, device="cuda", dtype=torch.bfloat16)
+            dx32 = torch.full((M, H), float("nan"), device="cuda")
+            dx16 = torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16)
             ops.layernorm_bwd(x, stats, g, mode, g_resid=g_resid, g_gemm=g_gemm, dt=dt if use_lora else None,
                               lora_a=A if use_lora else None, dx_f32=dx32, dx_bf16=dx16)
             assert rel_err(dx32, want) < 5e-5, (mode, use_lora)
             assert rel_err(dx16.float(), want) < TOL_BF16
     # only a GEMM gradient (top of the ViT / MLM head)
     (gx,) = torch.autograd.grad(ref, xf, g_gemm.float())
-    dx32 = torch.empty(M, H, device="cuda")
+    dx32 = torch.full((M, H), float("nan"), device="cuda")
     ops.layernorm_bwd(x, stats, g, 0, g_gemm=g_gemm, dx_f32=dx32)
     assert rel_err(dx32, gx) < 5e-5
 
@@ -498,7 +498,7 @@ def test_lora_grad(ops, H):
     dqkv = dev(rnd(M, 3 * H, seed=1).bfloat16())
     h = dev(rnd(M, H + 64, seed=2).bfloat16())
     lb = dev(rnd(2, H, 4, seed=3, scale=0.1))
-    dt = torch.empty(M, 8, device="cuda")
+    dt = torch.full((M, 8), float("nan"), device="cuda")
     dA, dBq, dBv = torch.zeros(8, H, device="cuda"), torch.zeros(H, 4, device="cuda"), torch.zeros(H, 4, device="cuda")
     ops.lora_grad(dqkv, h, M, H, lb, dt, dA, dBq, dBv)
     dq, dv = dqkv[:, :H].float(), dqkv[:, 2 * H:].float()
@@ -600,7 +600,7 @@ def test_small_ops(ops):
     ops.transpose_bf16(src, 300, 200, dst)
     assert torch.equal(dst[:, :300], src.t()) and (dst[:, 300:] == 0).all()
     x = dev(rnd(1003, seed=4))
-    y = torch.empty(1003, device="cuda", dtype=torch.bfloat16)
+    y = torch.full((1003,), float("nan"), device="cuda", dtype=torch.bfloat16)
     ops.cast_f32_bf16(x, y)
     assert torch.equal(y, x.bfloat16())
     w = torch.zeros(3 * 768, 832, device="cuda", dtype=torch.bfloat16)
@@ -705,7 +705,7 @@ def test_ln_param_grad(ops, H, xbf16):
     if xbf16:   # the 16-bit stream: the kernel and the reference below see the same rounded x
         x = x.bfloat16()
     gamma, beta = dev(rnd(H, seed=2) * 0.2 + 1), dev(rnd(H, seed=3) * 0.1)
-    y, stats = torch.empty(M, H + 64, device="cuda", dtype=torch.bfloat16), torch.empty(M, 2, device="cuda")
+    y, stats = torch.full((M, H + 64), float("nan"), device="cuda", dtype=torch.bfloat16), torch.full((M, 2), float("nan"), device="cuda")
     ops.layernorm_fwd(x, gamma, beta, 1e-6, y_bf16=y, stats=stats)
     g_gemm = dev(rnd(M, H, seed=4)).bfloat16()
     g_resid = dev(rnd(M, H, seed=5))
