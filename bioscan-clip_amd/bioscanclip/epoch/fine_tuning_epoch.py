@@ -41,6 +41,20 @@ def label_batch_to_species_idx(label_batch, unique_species_for_seen):
     return torch.tensor([unique_species_for_seen.index(species) for species in species_list])
 
 
+class ResidentTargets:
+    """``targets_of`` hook of the drivers below for a ``ShardLoader(labels="ids")``: the split's class-index column (int32 ``[n]``,
+    ``shards.class_indices``) is uploaded once and a batch's targets are that column at the batch's sample indices (slot 6 of the
+    batch) -- torch indexing on the device, no label dictionaries and no ``list.index``.  A species outside the class list is
+    ``shards.NOT_A_CLASS`` in the column and ends in the drivers' existing out-of-range errors."""
+
+    def __init__(self, class_index, device):
+        import numpy as np
+        self.column = torch.from_numpy(np.ascontiguousarray(class_index, dtype=np.int32)).to(device)
+
+    def __call__(self, batch):
+        return self.column[batch[6].to(self.column.device)]
+
+
 def _require_fused(criterion):
     ok = (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.ignore_index == -100
           and criterion.reduction == "mean" and criterion.label_smoothing == 0.0)
@@ -69,8 +83,9 @@ def _check_flag(flag, n_classes):
                          "nothing to the loss or the gradients of this epoch")
 
 
-def _run_epoch(args, classifiers, inputs_of, dataloader, optimizer, criterion, unique_species_for_seen, epoch, device):
-    """The loop shared by the one- and the two-classifier driver.  ``inputs_of(batch)`` -> one input per classifier."""
+def _run_epoch(args, classifiers, inputs_of, dataloader, optimizer, criterion, unique_species_for_seen, epoch, device, targets_of=None):
+    """The loop shared by the one- and the two-classifier driver.  ``inputs_of(batch)`` -> one input per classifier;
+    ``targets_of(batch)`` -> the integer targets ``[B]`` (default: ``label_batch_to_species_idx`` of the batch's label dictionaries)."""
     _require_fused(criterion)
     for m in classifiers:
         _require_classifier(m)
@@ -82,7 +97,10 @@ def _run_epoch(args, classifiers, inputs_of, dataloader, optimizer, criterion, u
     flag = torch.zeros(1, dtype=torch.int32, device=device)
     losses = []
     for step, batch in steps:
-        target = label_batch_to_species_idx(batch[6], unique_species_for_seen).to(device)
+        if targets_of is None:
+            target = label_batch_to_species_idx(batch[6], unique_species_for_seen).to(device)
+        else:
+            target = targets_of(batch).to(device)
         optimizer.zero_grad()
         loss = None
         for m, x in zip(classifiers, inputs_of(batch)):
@@ -108,27 +126,29 @@ def _run_epoch(args, classifiers, inputs_of, dataloader, optimizer, criterion, u
 
 
 def fine_tuning_epoch(args, model, insect_train_dataloader, optimizer, criterion, unique_species_for_seen, epoch, device,
-                      modality="image"):
+                      modality="image", targets_of=None):
     """Reference fine_tuning_epoch.py:11-37: one epoch of one classifier (``modality``: "image" or "dna"); returns the mean loss."""
     if modality not in ("image", "dna"):
         raise NotImplementedError(f"modality {modality!r}: only the image and DNA encoders have classifiers (no text-tower classifier)")
     return _run_epoch(args, [model], lambda batch: [_modality_input(batch, modality, device)[0]], insect_train_dataloader,
-                      optimizer, criterion, unique_species_for_seen, epoch, device)
+                      optimizer, criterion, unique_species_for_seen, epoch, device, targets_of=targets_of)
 
 
 def fine_tuning_epoch_image_and_dna(args, image_classifier, dna_classifier, insect_train_dataloader, optimizer, criterion,
-                                    unique_species_for_seen, epoch, device):
+                                    unique_species_for_seen, epoch, device, targets_of=None):
     """Reference fine_tuning_epoch.py:78-104: both classifiers per batch, loss = CE(image) + CE(dna); returns the mean loss."""
     image_classifier.train()
     dna_classifier.train()
     return _run_epoch(args, [image_classifier, dna_classifier],
                       lambda batch: [batch[1].to(device), batch[2].to(device)], insect_train_dataloader, optimizer, criterion,
-                      unique_species_for_seen, epoch, device)
+                      unique_species_for_seen, epoch, device, targets_of=targets_of)
 
 
-def evaluate_epoch(model, dataloader, device, unique_species_for_seen, k_values=None, modality="image"):
+def evaluate_epoch(model, dataloader, device, unique_species_for_seen, k_values=None, modality="image", targets_of=None):
     """Reference fine_tuning_epoch.py:39-76: ``{"top{k}_accuracy": share of samples whose target is among the k highest logits}``.
-    Ties between equal logits resolve to the lower class index (the reference's argsort leaves them unspecified)."""
+    Ties between equal logits resolve to the lower class index (the reference's argsort leaves them unspecified).
+    ``targets_of(batch)`` replaces ``label_batch_to_species_idx`` (which raises on the host for a species outside the class list):
+    a target outside [0, C) then is handed to the counting kernel as a label outside its class range, so the flag word raises."""
     from bioscanclip.hip import ops
     _require_classifier(model)
     if k_values is None:
@@ -141,14 +161,18 @@ def evaluate_epoch(model, dataloader, device, unique_species_for_seen, k_values=
     kmax = min(max(k_values), C)    # argsort(...)[:, :max(k)] has no more than C columns
     class_ids = torch.arange(C, dtype=torch.int32, device=device).view(C, 1)   # "key labels" of the hit search: class c is c
     flag = torch.zeros(1, dtype=torch.int32, device=device)
-    ranks = []
+    ranks, outside = [], []
     steps = enumerate(dataloader)
     if tqdm is not None:
         steps = tqdm(steps, total=len(dataloader))
     with torch.no_grad():
         for _, batch in steps:
             x, label_batch = _modality_input(batch, modality, device)
-            target = label_batch_to_species_idx(label_batch, unique_species_for_seen).to(device, torch.int32).view(-1, 1)
+            if targets_of is None:
+                target = label_batch_to_species_idx(label_batch, unique_species_for_seen).to(device, torch.int32).view(-1, 1)
+            else:
+                target = targets_of(batch).to(device, torch.int32).view(-1, 1)
+                outside.append(((target < 0) | (target >= C)).to(torch.int32))   # 0 = the one class of the count below, 1 = outside it
             output = model(x)
             _, predictions = ops.class_topk(output, C, kmax)
             ranks.append(ops.retrieval_hit_ranks(predictions, class_ids, target.contiguous(), flag=flag))   # first rank of the target, or kmax
@@ -157,7 +181,8 @@ def evaluate_epoch(model, dataloader, device, unique_species_for_seen, k_values=
     hit_rank = torch.cat(ranks)
     n = hit_rank.shape[0]
     # one "class" for every sample: right[j, 0] = the samples whose target sits within the first k_values[j] predictions
-    _, right = ops.retrieval_class_counts(hit_rank, torch.zeros_like(hit_rank), [0, 1], k_values, flag=flag)
+    one_class = torch.cat(outside).contiguous() if outside else torch.zeros_like(hit_rank)
+    _, right = ops.retrieval_class_counts(hit_rank, one_class, [0, 1], k_values, flag=flag)
     counts = torch.cat([right.view(-1), flag]).tolist()   # the evaluation's only download: one integer per k (+ the flag word)
     ops.check_retrieval_flag(counts[-1])
     return {f"top{k}_accuracy": counts[j] * 1.0 / n for j, k in enumerate(k_values)}

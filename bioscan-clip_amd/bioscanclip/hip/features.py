@@ -29,9 +29,10 @@ class SplitFeatures:
     ``file_name_list`` and, for a key set, ``indices[name]`` -- the ``RetrievalIndex`` of every key type, filled during the walk.
     The methods ``has`` / ``feature`` / ``query`` / ``index`` / ``labels`` / ``label_dicts`` are what ``retrieval.score_cells`` reads."""
 
-    def __init__(self, file_name_list, tables, label_ids, vocab, indices, device):
+    def __init__(self, file_name_list, tables, label_ids, vocab, indices, device, confidences=None, class_indices=None):
         self.file_name_list, self.tables, self.label_ids, self.vocab = file_name_list, tables, label_ids, vocab
         self.indices, self.device = indices, device
+        self.confidences, self.class_indices = confidences, class_indices    # method two: [N, k] of the classifier that rode along
         self._labels = {}
 
     def has(self, name):
@@ -85,8 +86,18 @@ def _loader_labels(loader, labels):
     return np.ascontiguousarray(np.asarray(ids, dtype=np.int32)[order]), vocab
 
 
-def extract_split(loader, model, device, for_key_set=False, index=True, labels=None):
+def extract_split(loader, model, device, for_key_set=False, index=True, labels=None, towers=None, classifier=None, n_classes=None,
+                  top_k=5, append_to=None):
     """One walk over ``loader`` (a ``ShardLoader(for_training=False)``): the features of every tower ``model`` has, in device tables.
+
+    ``towers``: run only these of ``"image"``, ``"dna"``, ``"text"`` (each must exist in the model); the other towers' tables stay
+    None, as for a model without them.  The seen / unseen protocols need the image tower for their query splits and seen keys and
+    the DNA tower for their unseen keys, nothing else.
+    ``classifier`` (method two; ``n_classes`` = its C): the same walk also runs this image classifier on every batch and
+    ``bsclip_class_softmax_topk`` writes its ``top_k`` confidences and class indices into rows ``[row0, row0 + B)`` of the split's
+    ``confidences`` f32 / ``class_indices`` int64 ``[N, top_k]`` tables.
+    ``append_to = {table name: (RetrievalIndex, first row)}``: every batch's rows of that table are also appended to an index the
+    caller owns, from that row on -- one index over the key splits of several walks.
 
     ``labels``: ``(ids, vocab)`` of the loader's whole shard as ``shards.taxonomy_ids`` returns them for it -- pass the ids encoded
     together with the other splits' so that the three share one vocabulary (``extract_splits`` does); default: the shard on its own.
@@ -95,9 +106,18 @@ def extract_split(loader, model, device, for_key_set=False, index=True, labels=N
     batch.  Returns a ``SplitFeatures``."""
     device = torch.device(device)
     encoders = {"image": model.image_encoder, "dna": model.dna_encoder, "text": model.language_encoder}
-    towers = [m for m, enc in encoders.items() if enc is not None]
+    if towers is None:
+        towers = [m for m, enc in encoders.items() if enc is not None]
+    else:
+        towers = [m for m in encoders if m in tuple(towers)]
+        absent = [m for m in towers if encoders[m] is None]
+        if absent or len(towers) != len(tuple(towers)):
+            raise ValueError(f"extract_split: towers must name encoders of the model (image, dna, text); the model has no {absent}")
     if not towers:
         raise ValueError("extract_split: the model has no encoder")
+    if classifier is not None and (n_classes is None or not 1 <= int(top_k) <= min(16, int(n_classes))):
+        raise ValueError("extract_split: a classifier needs n_classes and 1 <= top_k <= min(16, n_classes)")
+    append_to = dict(append_to or {})
     if "text" in towers and not getattr(loader, "with_text", True):
         raise ValueError("extract_split: the model has a text tower but the loader was built with with_text=False")
     label_ids, vocab = _loader_labels(loader, labels)
@@ -107,6 +127,10 @@ def extract_split(loader, model, device, for_key_set=False, index=True, labels=N
     both, every = "image" in towers and "dna" in towers, len(towers) == 3
     tables = dict.fromkeys([*_TABLE_OF.values(), "averaged_feature", "concatenated_feature", "all_key_features"])
     indices, names, row0 = {}, [], 0
+    conf = class_idx = None
+    if classifier is not None:
+        conf = torch.empty(N, int(top_k), dtype=torch.float32, device=device)
+        class_idx = torch.empty(N, int(top_k), dtype=torch.int64, device=device)
 
     def allocate(D):
         new = lambda rows, width: torch.empty(rows, width, dtype=torch.float32, device=device)
@@ -128,6 +152,11 @@ def extract_split(loader, model, device, for_key_set=False, index=True, labels=N
     with torch.no_grad():
         for processid, image, dna, input_ids, token_type_ids, attention_mask, _ in loader:
             out = {}
+            if classifier is not None:
+                if row0 + image.shape[0] > N:
+                    raise RuntimeError(f"extract_split: the loader yielded more than its {N} samples")
+                ops.class_softmax_topk(classifier(image.to(device)), int(n_classes), int(top_k),
+                                       out=(conf[row0:row0 + image.shape[0]], class_idx[row0:row0 + image.shape[0]]))
             if "image" in towers:
                 out["image"] = HF.l2_normalize(encoders["image"](image.to(device)).float())
             if "dna" in towers:
@@ -150,11 +179,13 @@ def extract_split(loader, model, device, for_key_set=False, index=True, labels=N
                         idx.append(tables[name][k * N + row0:k * N + row0 + B], k * N + row0)
                 else:
                     idx.append(tables[name][row0:row0 + B], row0)
+            for name, (idx, first) in append_to.items():
+                idx.append(tables[name][row0:row0 + B], int(first) + row0)
             names += list(processid)
             row0 += B
     if row0 != N:
         raise RuntimeError(f"extract_split: the loader yielded {row0} of its {N} samples")
-    return SplitFeatures(names, tables, label_ids, vocab, indices, device)
+    return SplitFeatures(names, tables, label_ids, vocab, indices, device, confidences=conf, class_indices=class_idx)
 
 
 def extract_splits(loaders, model, device, index=True):

@@ -895,13 +895,19 @@ def ce_fwd_bwd(logits, targets, C, loss_out, row_loss, dlogits=None, dlogits_spl
         check_ce_flag(int(flag.item()))
 
 
-def _class_topk(name, logits, C, k):
+def _class_topk(name, logits, C, k, out=None):
     ldc = _rowmajor(logits, "logits")
     B = logits.shape[0]
     _req(logits.dtype == F32 and B >= 1 and 1 <= C <= logits.shape[1] and ldc % 4 == 0, f"{name}: logits f32 [B, >= C], row stride % 4 == 0")
     _req(1 <= k <= min(16, C), f"{name}: 1 <= k <= 16, k <= C")
-    out = torch.empty(B, k, dtype=F32, device=logits.device)
-    idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
+    if out is None:
+        out = torch.empty(B, k, dtype=F32, device=logits.device)
+        idx = torch.empty(B, k, dtype=torch.int64, device=logits.device)
+    else:
+        out, idx = out
+        for t, dt in ((out, F32), (idx, torch.int64)):
+            _req(t.dtype == dt and t.is_contiguous() and t.device == logits.device and tuple(t.shape) == (B, k),
+                 f"{name}: out = (f32 [B, k], int64 [B, k]), contiguous, on the logits' GPU")
     check(getattr(_l.load(), "bsclip_" + name)(_p(logits), ldc, B, C, k, _p(out), _p(idx), _stream()))
     return out, idx
 
@@ -912,10 +918,11 @@ def class_topk(logits, C, k):
     return _class_topk("class_topk", logits, C, k)
 
 
-def class_softmax_topk(logits, C, k):
+def class_softmax_topk(logits, C, k, out=None):
     """``F.softmax(logits[:, :C], -1)`` then ``torch.topk(..., k, sorted=True)`` in one kernel: (confidences f32 [B, k], class indices
-    int64 [B, k]) on the GPU, ordered by logit descending, ties to the lower class index.  ``logits`` as for ``class_topk``."""
-    return _class_topk("class_softmax_topk", logits, C, k)
+    int64 [B, k]) on the GPU, ordered by logit descending, ties to the lower class index.  ``logits`` as for ``class_topk``.
+    ``out``: the pair of tensors to write to, e.g. rows ``[row0, row0 + B)`` of a split's ``[Q, k]`` tables."""
+    return _class_topk("class_softmax_topk", logits, C, k, out=out)
 
 
 def check_silhouette_flag(word):

@@ -61,6 +61,7 @@ FORMAT, VERSION = "bsclip-shard", 1
 CODECS = ("raw", "jpeg")
 MAX_DECODE_THREADS = 16
 ENTROPY_MODES = ("host", "gpu")
+LABEL_MODES = (None, "ids")
 DEFAULT_JPEG_SYNC_MCUS = 4     # the sweep over {2, 4, 8, 16, 32} on the bench pictures
 _TAXA = ("order", "family", "genus", "species")
 _TEXT = ("language_tokens_input_ids", "language_tokens_token_type_ids", "language_tokens_attention_mask")
@@ -296,6 +297,47 @@ def eval_splits(root, which="val"):
     return tuple(paths)
 
 
+PROTOCOL_SPLITS = ("train_seen", "seen_keys", "val_unseen_keys", "test_unseen_keys", "val_seen", "val_unseen", "test_seen", "test_unseen")
+NOT_A_CLASS = -1               # class index of a species outside the class list: the kernels' range checks flag it
+
+
+def protocol_splits(root, names=PROTOCOL_SPLITS):
+    """The shard directories ``names`` of a protocol root, in that order: a directory whose sub-directories are shards named after
+    the splits of the reference's seen / unseen protocols (``PROTOCOL_SPLITS``).  The contract of ``eval_splits``: other
+    sub-directories are ignored; a split that is absent or is not a shard raises ValueError."""
+    names = tuple(names)
+    unknown = [n for n in names if n not in PROTOCOL_SPLITS]
+    if unknown:
+        raise ValueError(f"protocol splits are {', '.join(PROTOCOL_SPLITS)}, got {unknown}")
+    paths = []
+    for name in names:
+        path = os.path.join(str(root), name)
+        if not is_shard(path):
+            raise ValueError(f"{root}: no shard for the split {name!r} (a protocol root holds the shard directories "
+                             f"{', '.join(names)})")
+        paths.append(path)
+    return tuple(paths)
+
+
+def class_index_table(species_vocab, classes):
+    """int32 ``[len(species_vocab)]``: species id (``taxonomy_ids``'s ``vocab["species"]`` order) -> its position in the class list
+    ``classes`` as ``list.index`` gives it (the first occurrence of a repeated name), ``NOT_A_CLASS`` for a species that is not
+    listed.  Host only, one pass over the two name lists; ``table[ids[:, species]]`` then is a whole split's class-index column."""
+    first = {}
+    for c, name in enumerate(classes):
+        first.setdefault(name, c)
+    return np.asarray([first.get(name, NOT_A_CLASS) for name in species_vocab], dtype=np.int32).reshape(-1)
+
+
+def class_indices(ids, table, level=None):
+    """The int32 ``[n]`` class-index column of one split: ``table`` (``class_index_table``) looked up with the split's species ids
+    (``ids``: the int32 ``[n, L]`` array of ``taxonomy_ids`` -- its last column unless ``level`` says otherwise -- or ``[n]``)."""
+    ids = np.asarray(ids)
+    if ids.ndim == 2:
+        ids = ids[:, -1 if level is None else level]
+    return np.ascontiguousarray(np.asarray(table, dtype=np.int32)[ids])
+
+
 def taxonomy_ids(shard_list, levels=LEVELS):
     """``hip/retrieval.encode_labels`` of the shards' ``label_dicts`` (every sample, in the given order) without building them:
     returns ``(arrays, vocab)``, one int32 ``[n, L]`` array per shard and ``vocab[level]`` = the names in id order.  Ids are handed
@@ -345,8 +387,11 @@ class ShardLoader:
     SLOTS = 3
 
     def __init__(self, shard, batch_size, rank=0, world_size=1, shuffle=False, seed=0, for_training=True, with_text=True,
-                 device="cuda", augment_seed=None, decode_threads=4, entropy="host"):
-        """``decode_threads`` (1..16, JPEG shards only): loader threads that entropy-decode a batch side by side.
+                 device="cuda", augment_seed=None, decode_threads=4, entropy="host", labels=None):
+        """``labels`` (slot 6 of the yielded tuple): ``None`` keeps what ``for_training`` selects (the training index labels, or the
+        taxonomy dictionaries); ``"ids"`` yields the batch's sample indices instead, int64 ``[B]`` on the device, and builds no label
+        dictionaries -- for consumers that keep the split's labels as resident columns and index them (``last_indices`` as a tensor).
+        ``decode_threads`` (1..16, JPEG shards only): loader threads that entropy-decode a batch side by side.
         ``entropy`` (JPEG shards): ``"host"`` Huffman-decodes on those threads; ``"gpu"`` sends the stored bytes up and decodes them
         on the device from the shard's sync index (``write_shard(jpeg_sync_mcus=...)`` / ``add_jpeg_sync_index``).  In GPU mode a
         stream or index damaged after the shard was written -- shards are validated when written, so nothing else -- is found by
@@ -364,7 +409,9 @@ class ShardLoader:
             what = "a raw shard has no streams to decode" if self.shard.image_codec != "jpeg" else "this JPEG shard has no sync index"
             raise ValueError(f"{self.shard.path}: entropy='gpu' needs a JPEG shard with a sync index ({what}); write it with "
                              "write_shard(..., jpeg_sync_mcus=...) or index it in place with shards.add_jpeg_sync_index(path)")
-        self.entropy = entropy
+        if labels not in LABEL_MODES:
+            raise ValueError(f"labels must be one of {LABEL_MODES}, got {labels!r}")
+        self.entropy, self.labels = entropy, labels
         self._pool = None
         if self.shard.image_codec == "jpeg" and self.decode_threads > 1 and entropy == "host":
             from concurrent.futures import ThreadPoolExecutor
@@ -437,9 +484,9 @@ class ShardLoader:
         host = {"sizes": sizes, "nbytes": nbytes, "indices": idx, "dna_offsets": off_h, "n_dna": doffs[-1],
                 "params": [self.augment.sample(*_resized_size(h, w, self.augment.resize_to)) for h, w in sizes],
                 "processid": [p.decode() for p in sh.processid[sel]]}
-        if self.for_training:
+        if self.for_training or self.labels == "ids":
             lab = mh[self.batch_size + 1:self.batch_size + 1 + B]
-            lab.copy_(torch.from_numpy(np.ascontiguousarray(sh.labels[sel])))
+            lab.copy_(torch.from_numpy(np.ascontiguousarray(sel if self.labels == "ids" else sh.labels[sel], dtype=np.int64)))
             host["label"] = lab
         else:
             host["label"] = sh.label_dicts(idx)
@@ -602,7 +649,7 @@ class ShardLoader:
                 out["text"] = [t.to(self.device, non_blocking=True) for t in host["text"]]
             else:
                 out["text"] = [None, None, None]
-            out["label"] = host["label"].to(self.device, non_blocking=True) if self.for_training else host["label"]
+            out["label"] = host["label"].to(self.device, non_blocking=True) if torch.is_tensor(host["label"]) else host["label"]
             ev = torch.cuda.Event()
             ev.record(self.stream)
             out["ready"] = ev

@@ -24,6 +24,13 @@ Mirrored entry points (same names, argument meaning and return shapes as the ref
 label matches are bit masks, the 1 000 thresholds are one sweep launch per split, the tables come from integer class counts.  Its
 output dictionaries equal the host path's with ``==``; ``final_pred_labels`` holds strings only with ``with_predictions=True``
 (otherwise ``None``, and ``merged`` carries the GPU handle the membership check reads).
+
+``eval_shards=<root>`` reads the seven splits from a protocol root of shards (``shards.protocol_splits``: ``seen_keys``,
+``val_unseen_keys``, ``test_unseen_keys``, ``val_seen``, ``val_unseen``, ``test_seen``, ``test_unseen``) instead of the synthetic loaders.
+With ``hip_eval=gpu`` every split is walked once with the one tower it needs and features, key indices and label ids stay on the GPU
+(``bioscanclip/hip/protocols.py``); with ``hip_eval=host`` the functions below walk ``ShardLoader(for_training=False)`` loaders.
+``eval_batch_size`` (default 40, the reference's) and ``hip_jpeg_entropy=host|gpu`` as in ``inference_and_eval.py``; a ``synthetic_*``
+option next to ``eval_shards`` is refused.
 """
 import os
 import sys
@@ -154,9 +161,13 @@ class MergedOnGpu:
         return merged_predictions(self.split, self.threshold, self.seen_key_labels, self.unseen_key_labels)
 
     def member_share(self, species_list, ks=(1, 3, 5)):
+        """``species_list``: names, or the int32 0/1 member table over the species ids itself (``ProtocolRoot.member_table``)."""
         from bioscanclip.hip.method_one import member_share
-        listed = set(species_list)
-        table = np.asarray([int(name in listed) for name in self.vocab["species"]], dtype=np.int32)
+        if isinstance(species_list, np.ndarray):
+            table = np.ascontiguousarray(species_list, dtype=np.int32)
+        else:
+            listed = set(species_list)
+            table = np.asarray([int(name in listed) for name in self.vocab["species"]], dtype=np.int32)
         return member_share(self.split, self.threshold, table, ks=ks, level="species")
 
 
@@ -270,6 +281,67 @@ def check_for_acc_about_correct_predict_seen_or_unseen(final_pred_list, species_
     return shares
 
 
+def shard_source(args, overrides=()):
+    """``(root, entropy, batch_size)`` of ``eval_shards=<root>`` (``root`` None without it).  Refused before any GPU work: a
+    ``synthetic_*`` option among the command line's ``overrides`` next to ``eval_shards`` (both name the splits; the configuration
+    file's own defaults do not count), an unknown ``hip_jpeg_entropy``, a batch size below 1."""
+    from bioscanclip.util import shards
+    root = getattr(args, "eval_shards", None)
+    root = None if root in (None, "") else str(root)
+    synthetic = sorted({ov.strip().strip("'").strip('"').lstrip("+").split("=", 1)[0] for ov in overrides} & {k for k in args if str(k).startswith("synthetic_")})
+    if root is not None and synthetic:
+        raise ValueError(f"{', '.join(synthetic)} and eval_shards=<root> both name the splits: give one of them")
+    entropy = getattr(args, "hip_jpeg_entropy", None)
+    entropy = "host" if entropy is None or entropy == "" else str(entropy)
+    if entropy not in shards.ENTROPY_MODES:
+        raise ValueError(f"hip_jpeg_entropy must be one of {shards.ENTROPY_MODES}, got {entropy!r}")
+    batch_size = int(getattr(args, "eval_batch_size", 40))           # the reference evaluates at batch 40 (:295)
+    if batch_size < 1:
+        raise ValueError(f"eval_batch_size must be >= 1, got {batch_size}")
+    return root, entropy, batch_size
+
+
+METHOD_ONE_SPLITS = ("seen_keys", "val_unseen_keys", "test_unseen_keys", "val_seen", "val_unseen", "test_seen", "test_unseen")
+PARTS = (("val", "val_seen", "val_unseen"), ("test", "test_seen", "test_unseen"))
+
+
+def report(results, part, seen_species, unseen_species, k_list):
+    """What ``main`` prints per part: the table rows and the two membership checks."""
+    print_acc_for_google_doc(*results[part], K_LIST=k_list)
+    print("For seen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(results[part][0]), seen_species)
+    print("For unseen")
+    check_for_acc_about_correct_predict_seen_or_unseen(_predictions_of(results[part][1]), unseen_species)
+
+
+def method_1_from_shards(args, original_model, proto, device):
+    """``main`` from ``load_model`` on for a protocol root.  ``hip_eval=gpu``: both key indices built once during one walk per key
+    split, one walk per query split, member tables from the joint ids; ``hip_eval=host``: the functions above on shard loaders."""
+    from bioscanclip.hip import protocols
+    k_list = _k_list(args)
+    results, threshold = {}, None
+    unseen_key_splits = protocols.UNSEEN_KEY_SPLITS
+    if eval_mode(args) == "gpu":
+        keys = protocols.method_one_keys(proto, original_model, device, width=int(getattr(args.model_config, "output_dim", 768)))
+        key_rows = (protocols.LabelRows(keys[1].ids, proto.vocab), protocols.LabelRows(keys[3].ids, proto.vocab))
+        seen_species, unseen_species = proto.member_table("seen_keys"), proto.member_table(*unseen_key_splits)
+    else:
+        seen_species, unseen_species = proto.species_names("seen_keys"), proto.species_names(*unseen_key_splits)
+    for part, seen, unseen in PARTS:
+        if eval_mode(args) == "gpu":
+            splits = [protocols.method_one_split(proto, name, original_model, device, keys) for name in (seen, unseen)]
+            results[part] = score_splits_on_gpu(args, splits, [protocols.ground_truth(proto, name) for name in (seen, unseen)], proto.vocab,
+                                                *key_rows, searched_threshold=threshold)
+        else:
+            ld = lambda name: proto.loader(name, labels=None)
+            results[part] = method_1_inference_and_eval_for_seen_and_unseen(
+                args, original_model, ld(seen), ld(unseen), ld("seen_keys"), ld(unseen_key_splits[0]), ld(unseen_key_splits[1]), device,
+                searched_threshold=threshold)
+        threshold = results[part][0]['best_threshold']              # the val threshold is the test splits' searched_threshold
+        report(results, part, seen_species, unseen_species, k_list)
+    return results
+
+
 def _predictions_of(output_dict):
     return output_dict["final_pred_labels"] if output_dict["final_pred_labels"] is not None else output_dict["merged"]
 
@@ -285,19 +357,30 @@ def main(argv=None):
     from bioscanclip.util.synthetic import SyntheticEvalLoader
     from bioscanclip.util.util import load_model_and_checkpoint
     here = os.path.dirname(os.path.abspath(__file__))
-    args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = load_config(os.path.join(here, "..", "bioscanclip", "config"), argv)
     eval_mode(args)
+    root, entropy, eval_batch = shard_source(args, argv)
     mc = args.model_config
     if getattr(mc, "for_open_clip", False):
         raise NotImplementedError("the open_clip branch is not part of the HIP-accelerated path")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("method-one evaluation runs on one GPU")
+    if root is not None:
+        from bioscanclip.util import shards
+        shards.protocol_splits(root, METHOD_ONE_SPLITS)
     if not torch.cuda.is_available():
         raise RuntimeError("method_one_eval needs a ROCm GPU: the encoders and the top-k search run in libbsclip_hip.so")
     global K_LIST
     K_LIST = _k_list(args)
     device = torch.device("cuda", 0)
     print("Construct dataloader...")
+    if root is not None:
+        from bioscanclip.hip.protocols import ProtocolRoot
+        proto = ProtocolRoot(root, METHOD_ONE_SPLITS, batch_size=eval_batch, entropy=entropy, device=device)
+        original_model, _ = load_model_and_checkpoint(args, device)
+        original_model.eval()
+        return method_1_from_shards(args, original_model, proto, device)
     bs, n = 40, int(getattr(args, "synthetic_eval_batches", 2))    # the reference evaluates at batch 40 (:295)
     mk = lambda seed: SyntheticEvalLoader(bs, n, with_text=False, seed=seed)
     seen_keys, val_unseen_keys, test_unseen_keys = mk(5301), mk(5302), mk(5303)

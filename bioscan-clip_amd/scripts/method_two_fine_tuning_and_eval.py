@@ -42,6 +42,13 @@ has C = the seen species outputs, not a literal 916; which parameters train foll
 (``bioscanclip/epoch/fine_tuning_epoch.py``); the HDF5 splits come from ``SyntheticEvalLoader``; and the last membership check, which
 in the reference passes the test-unseen species list twice (:563-564), checks against val + test unseen species in both places, as
 the method-one script does.
+``eval_shards=<root>`` reads the eight splits from a protocol root of shards (``shards.protocol_splits``).  The classifier is
+fine-tuned on ``train_seen`` -- shuffled, a new order per epoch, batch ``model_config.batch_size``, the evaluation transform unless
+``fine_tune_augment=true`` selects the training augmentation chain -- with its targets taken from a class-index column resident on the
+GPU (``fine_tuning_epoch.ResidentTargets``), so no label dictionary is built for a training batch.  With ``hip_eval=gpu`` each query
+split is walked once: the classifier's softmax top-5 goes straight into the split's ``[Q, 5]`` tables while the original model's image
+features are filed (``bioscanclip/hip/protocols.py``); with ``hip_eval=host`` the functions below walk shard loaders.
+``eval_batch_size`` (default 40), ``hip_jpeg_entropy=host|gpu``; a ``synthetic_*`` option next to ``eval_shards`` is refused.
 Keys: ``fine_tune_epochs`` (default 1), ``synthetic_steps_per_epoch`` (20), ``synthetic_eval_batches`` (2), ``model_config.batch_size``
 (the training batch; evaluation runs at 40), ``model_config.fine_tuning_set.fine_tune_model_output_dir`` (``last.pth``), ``save_ckpt``.
 """
@@ -62,7 +69,7 @@ from inference_and_eval import LEVELS, make_prediction  # noqa: E402
 from method_one_eval import (MAX_K, MergedOnGpu, _k_list, _key_features, _predictions_of,  # noqa: E402,F401
                              check_for_acc_about_correct_predict_seen_or_unseen, decide_prediction_with_threshold, eval_mode,
                              get_all_unique_species_from_dataloader, get_final_pred_and_acc, harmonic_mean, merge_checked,
-                             print_acc_for_google_doc, score_splits_on_gpu, search_threshold)
+                             PARTS, print_acc_for_google_doc, report, score_splits_on_gpu, search_threshold, shard_source)
 
 K_LIST = None
 
@@ -211,19 +218,59 @@ def _class_list(species_level_label_to_index_dict):
 
 
 def fine_tuning_epoch(args, model, train_dataloader, val_seen_dataloader, val_unseen_dataloader, optimizer, criterion, device,
-                      species_level_label_to_index_dict, epoch=0):
-    """``(epoch_loss, seen_evaluation_result)`` (:328-351) through ``bioscanclip.epoch.fine_tuning_epoch`` -- the fused HIP loss."""
+                      species_level_label_to_index_dict, epoch=0, targets_of=None, val_targets_of=None):
+    """``(epoch_loss, seen_evaluation_result)`` (:328-351) through ``bioscanclip.epoch.fine_tuning_epoch`` -- the fused HIP loss.
+    ``targets_of`` / ``val_targets_of``: the drivers' hooks for loaders that yield sample indices instead of label dictionaries."""
     classes = _class_list(species_level_label_to_index_dict)
-    epoch_loss = _epoch.fine_tuning_epoch(args, model, train_dataloader, optimizer, criterion, classes, epoch, device)
+    epoch_loss = _epoch.fine_tuning_epoch(args, model, train_dataloader, optimizer, criterion, classes, epoch, device, targets_of=targets_of)
     print("Eval on seen val.")
-    seen_evaluation_result = evaluate_epoch(model, val_seen_dataloader, device, species_level_label_to_index_dict)
+    seen_evaluation_result = evaluate_epoch(model, val_seen_dataloader, device, species_level_label_to_index_dict,
+                                            targets_of=val_targets_of)
     print("Evaluation Result:", seen_evaluation_result)
     return epoch_loss, seen_evaluation_result
 
 
-def evaluate_epoch(model, dataloader, device, species_level_label_to_index_dict, k_values=None):
+def evaluate_epoch(model, dataloader, device, species_level_label_to_index_dict, k_values=None, targets_of=None):
     """``{"top{k}_accuracy": ...}`` for k in 1, 3, 5 (:354-385), counted on the GPU."""
-    return _epoch.evaluate_epoch(model, dataloader, device, _class_list(species_level_label_to_index_dict), k_values=k_values)
+    return _epoch.evaluate_epoch(model, dataloader, device, _class_list(species_level_label_to_index_dict), k_values=k_values,
+                                 targets_of=targets_of)
+
+
+def method_2_from_shards(args, image_classifier, original_model, proto, label_map, idx_to_all_labels, class_table, device):
+    """The evaluation half of ``main`` for a protocol root: ``{"val": ..., "test": ...}``.  ``hip_eval=gpu``: the unseen-key index
+    built once during one walk per key split, one walk per query split with the classifier riding along, member tables from the
+    joint ids; ``hip_eval=host``: ``method_2_inference_and_eval_for_seen_and_unseen`` on shard loaders."""
+    from bioscanclip.hip import protocols
+    from bioscanclip.hip.method_two import linspace_thresholds
+    from bioscanclip.hip.retrieval import Labels
+    k_list = _k_list(args)
+    gpu = eval_mode(args) == "gpu"
+    val_keys, test_keys = protocols.UNSEEN_KEY_SPLITS
+    C = len(idx_to_all_labels)
+    if gpu:
+        unseen_index, unseen_labels = protocols.unseen_key_index(proto, original_model, device,
+                                                                 width=int(getattr(args.model_config, "output_dim", 768)))
+        classes = Labels(class_table, device)
+        class_rows = [idx_to_all_labels[c] for c in range(C)]
+        unseen_rows = protocols.LabelRows(unseen_labels.ids, proto.vocab)
+        seen_species, unseen_species = proto.member_table("seen_keys"), proto.member_table(val_keys, test_keys)
+    else:
+        seen_species, unseen_species = proto.species_names("seen_keys"), proto.species_names(val_keys, test_keys)
+    results, threshold = {}, None
+    for part, seen, unseen in PARTS:
+        if gpu:
+            splits = [protocols.method_two_split(proto, name, image_classifier, C, classes, original_model, device, unseen_index,
+                                                 unseen_labels, top_k=MAX_K) for name in (seen, unseen)]
+            results[part] = score_splits_on_gpu(args, splits, [protocols.ground_truth(proto, name) for name in (seen, unseen)], proto.vocab,
+                                                class_rows, unseen_rows, searched_threshold=threshold, grid=linspace_thresholds)
+        else:
+            ld = lambda name: proto.loader(name, labels=None)
+            results[part] = method_2_inference_and_eval_for_seen_and_unseen(
+                args, image_classifier, original_model, ld(seen), ld(unseen), ld(val_keys), ld(test_keys), label_map, idx_to_all_labels,
+                device, searched_threshold=threshold)
+        threshold = results[part][0]['best_threshold']              # the val threshold is the test splits' searched_threshold
+        report(results, part, seen_species, unseen_species, k_list)
+    return results
 
 
 def main(argv=None):
@@ -237,11 +284,16 @@ def main(argv=None):
     from bioscanclip.util.synthetic import SyntheticEvalLoader
     from bioscanclip.util.util import load_model_and_checkpoint
     here = os.path.dirname(os.path.abspath(__file__))
-    args = load_config(os.path.join(here, "..", "bioscanclip", "config"), list(sys.argv[1:] if argv is None else argv))
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = load_config(os.path.join(here, "..", "bioscanclip", "config"), argv)
     eval_mode(args)
+    root, entropy, eval_batch = shard_source(args, argv)
     if "model_config" not in args:
         raise SystemExit("usage: method_two_fine_tuning_and_eval.py 'model_config=<name>' [key=value ...]")
     mc = args.model_config
+    if root is not None:
+        from bioscanclip.util import shards
+        shards.protocol_splits(root)
     if getattr(mc, "for_open_clip", False):
         raise NotImplementedError("the open_clip branch is not part of the HIP-accelerated path")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -255,12 +307,23 @@ def main(argv=None):
     torch.cuda.set_device(device)
 
     print("Construct dataloader...")
-    n_eval = int(getattr(args, "synthetic_eval_batches", 2))
-    mk = lambda seed: SyntheticEvalLoader(40, n_eval, with_text=False, seed=seed)
-    train_seen = SyntheticEvalLoader(int(mc.batch_size), int(getattr(args, "synthetic_steps_per_epoch", 20)), seed=6300)
-    seen_keys, val_unseen_keys, test_unseen_keys = mk(6301), mk(6302), mk(6303)
-    seen_val, unseen_val, seen_test, unseen_test = mk(6304), mk(6305), mk(6306), mk(6307)
-    species_level_label_to_index_dict, idx_to_all_labels = load_all_seen_species_name_and_create_label_map(train_seen)
+    proto, targets_of, val_targets_of = None, None, None
+    if root is not None:
+        from bioscanclip.hip.protocols import ProtocolRoot
+        proto = ProtocolRoot(root, shards.PROTOCOL_SPLITS, batch_size=eval_batch, entropy=entropy, device=device)
+        species_level_label_to_index_dict, idx_to_all_labels, class_table = proto.sorted_class_list("train_seen")
+        classes = _class_list(species_level_label_to_index_dict)
+        train_seen = proto.loader("train_seen", batch_size=int(mc.batch_size), shuffle=True,
+                                  for_training=bool(getattr(args, "fine_tune_augment", False)))
+        seen_val, unseen_val = proto.loader("val_seen"), proto.loader("val_unseen")
+        targets_of, val_targets_of = proto.targets(classes, "train_seen"), proto.targets(classes, "val_seen")
+    else:
+        n_eval = int(getattr(args, "synthetic_eval_batches", 2))
+        mk = lambda seed: SyntheticEvalLoader(40, n_eval, with_text=False, seed=seed)
+        train_seen = SyntheticEvalLoader(int(mc.batch_size), int(getattr(args, "synthetic_steps_per_epoch", 20)), seed=6300)
+        seen_keys, val_unseen_keys, test_unseen_keys = mk(6301), mk(6302), mk(6303)
+        seen_val, unseen_val, seen_test, unseen_test = mk(6304), mk(6305), mk(6306), mk(6307)
+        species_level_label_to_index_dict, idx_to_all_labels = load_all_seen_species_name_and_create_label_map(train_seen)
     print(f"{len(idx_to_all_labels)} seen species")
 
     original_model, _ = load_model_and_checkpoint(args, device)
@@ -283,14 +346,20 @@ def main(argv=None):
         save_ckpt = False
     else:
         for epoch in range(int(getattr(args, "fine_tune_epochs", 1))):
+            if proto is not None:
+                train_seen.set_epoch(epoch)                            # a new order of train_seen per epoch
             history.append(fine_tuning_epoch(args, image_classifier, train_seen, seen_val, unseen_val, optimizer, criterion, device,
-                                             species_level_label_to_index_dict, epoch=epoch))
+                                             species_level_label_to_index_dict, epoch=epoch, targets_of=targets_of,
+                                             val_targets_of=val_targets_of))
             print(f"epoch {epoch}: loss {history[-1][0]:.6f}")
     if save_ckpt:
         os.makedirs(str(out_dir), exist_ok=True)
         torch.save(image_classifier.state_dict(), last_ckpt_path)
         print(f'Last ckpt: {last_ckpt_path}')
     image_classifier.eval()
+    if proto is not None:
+        return {"history": history, **method_2_from_shards(args, image_classifier, original_model, proto, species_level_label_to_index_dict,
+                                                           idx_to_all_labels, class_table, device)}
 
     run = lambda seen, unseen, threshold: method_2_inference_and_eval_for_seen_and_unseen(
         args, image_classifier, original_model, seen, unseen, val_unseen_keys, test_unseen_keys, species_level_label_to_index_dict,

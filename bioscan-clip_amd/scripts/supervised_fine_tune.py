@@ -11,8 +11,12 @@ Differences, all deliberate:
   * which parameters train follows the regime of the loaded model (the reference switches ``requires_grad`` on for every parameter
     under the LoRA wrappers): in the LoRA regime the LoRA pairs, the projection heads and the new Linear train; with
     ``disable_lora: true`` every parameter does;
-  * the INSECT dataset loaders are not rebuilt: ``dataset=synthetic`` (the only choice) feeds synthetic batches of the reference's
+  * the INSECT dataset loaders are not rebuilt: ``dataset=synthetic`` (the default) feeds synthetic batches of the reference's
     layout whose labels are taxonomy-name dicts (``SyntheticEvalLoader``), as ``train_cl.py`` does for its ``synthetic_eval=true``;
+    ``dataset=<root>`` names a protocol root of shards (``shards.protocol_splits``): training on ``train_seen`` (shuffled, a new
+    order per epoch, the evaluation transform unless ``fine_tune_augment=true``), evaluation on ``val_seen``, the class list
+    ``train_seen``'s species in order of first appearance, the targets a class-index column resident on the GPU
+    (``fine_tuning_epoch.ResidentTargets``; ``hip_jpeg_entropy=host|gpu`` for JPEG shards);
   * head, loss, top-k and the accuracy counts run on the HIP kernels (bsclip_ce_fwd_bwd, bsclip_class_topk); one GPU, no graph capture.
 Keys: ``fine_tune_epochs`` (default 1), ``synthetic_steps_per_epoch`` (20), ``synthetic_eval_batches`` (2), ``model_config.batch_size``.
 """
@@ -34,6 +38,7 @@ from bioscanclip.util.synthetic import SyntheticEvalLoader  # noqa: E402
 from bioscanclip.util.util import EncoderWithExtraLayer, load_model_and_checkpoint  # noqa: E402
 
 K_VALUES = [1, 3, 5]
+SHARD_SPLITS = ("train_seen", "val_seen")
 
 
 def unique_species(dataloader):
@@ -51,8 +56,16 @@ def main(argv=None):
     if "model_config" not in args:
         raise SystemExit("usage: supervised_fine_tune.py 'model_config=<name>' [key=value ...]")
     mc = args.model_config
-    if getattr(args, "dataset", "synthetic") != "synthetic":
-        raise NotImplementedError("the INSECT dataset loaders are not part of the HIP path: dataset=synthetic is the only choice")
+    dataset = str(getattr(args, "dataset", "synthetic"))
+    if dataset != "synthetic":
+        from bioscanclip.util import shards
+        if not os.path.isdir(dataset):
+            raise NotImplementedError("the INSECT dataset loaders are not part of the HIP path: dataset=synthetic, or a protocol root "
+                                      "of shards (a directory holding train_seen and val_seen)")
+        shards.protocol_splits(dataset, SHARD_SPLITS)
+        entropy = str(getattr(args, "hip_jpeg_entropy", None) or "host")
+        if entropy not in shards.ENTROPY_MODES:
+            raise ValueError(f"hip_jpeg_entropy must be one of {shards.ENTROPY_MODES}, got {entropy!r}")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("supervised fine-tuning runs on one GPU")
     if not hasattr(mc, "dna"):
@@ -69,9 +82,18 @@ def main(argv=None):
     batch_size = int(mc.batch_size)
     steps = int(getattr(args, "synthetic_steps_per_epoch", 20))
     n_eval = int(getattr(args, "synthetic_eval_batches", 2))
-    train_loader = SyntheticEvalLoader(batch_size, steps, seed=8001)
-    val_loader = SyntheticEvalLoader(batch_size, n_eval, seed=8002)
-    classes = unique_species(train_loader)
+    train_targets = val_targets = None
+    if dataset != "synthetic":
+        from bioscanclip.hip.protocols import ProtocolRoot
+        proto = ProtocolRoot(dataset, SHARD_SPLITS, batch_size=batch_size, entropy=entropy, device=device)
+        train_loader = proto.loader("train_seen", shuffle=True, for_training=bool(getattr(args, "fine_tune_augment", False)))
+        val_loader = proto.loader("val_seen")
+        classes = proto.first_appearance_classes("train_seen")
+        train_targets, val_targets = proto.targets(classes, "train_seen"), proto.targets(classes, "val_seen")
+    else:
+        train_loader = SyntheticEvalLoader(batch_size, steps, seed=8001)
+        val_loader = SyntheticEvalLoader(batch_size, n_eval, seed=8002)
+        classes = unique_species(train_loader)
     print(f"{len(classes)} species in the training labels")
 
     out_dim = int(getattr(mc, "output_dim", 768))
@@ -86,10 +108,12 @@ def main(argv=None):
     epochs = int(getattr(args, "fine_tune_epochs", 1))
     rows = []
     for epoch in range(epochs):
+        if dataset != "synthetic":
+            train_loader.set_epoch(epoch)
         loss = fine_tuning_epoch_image_and_dna(args, image_classifier, dna_classifier, train_loader, optimizer, criterion, classes,
-                                               epoch, device)
-        acc_i = evaluate_epoch(image_classifier, val_loader, device, classes, k_values=K_VALUES, modality="image")
-        acc_d = evaluate_epoch(dna_classifier, val_loader, device, classes, k_values=K_VALUES, modality="dna")
+                                               epoch, device, targets_of=train_targets)
+        acc_i = evaluate_epoch(image_classifier, val_loader, device, classes, k_values=K_VALUES, modality="image", targets_of=val_targets)
+        acc_d = evaluate_epoch(dna_classifier, val_loader, device, classes, k_values=K_VALUES, modality="dna", targets_of=val_targets)
         rows.append((epoch, loss, acc_i, acc_d))
         cells = "  ".join(f"{name} top{k} {acc[f'top{k}_accuracy']:.4f}" for name, acc in (("image", acc_i), ("dna", acc_d)) for k in K_VALUES)
         print(f"epoch {epoch}: loss {loss:.6f}  {cells}")
