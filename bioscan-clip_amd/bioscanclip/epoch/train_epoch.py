@@ -141,5 +141,8 @@ def train_epoch(activate_wandb, total_epochs, epoch, dataloader, model, optimize
         report(pending[0], value, pending[1])
 
     mean_loss = running / max(n_steps, 1)
-    print(f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}")
+    if torch.is_tensor(getattr(criterion, "logit_scale", None)):   # learnable temperature: one read-back per epoch
+        print(f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}, logit scale: {criterion.current_scale().item():.6f}")
+    else:
+        print(f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}")
     return mean_loss

@@ -151,12 +151,16 @@ class _null:
 
 
 def flat_buffers(model):
-    """The FlatParams of every HIP encoder engine under ``model`` (built lazily by the first forward)."""
+    """The FlatParams of every HIP encoder engine under ``model`` (built lazily by the first forward), and the learnable
+    temperature's own (``SimpleCLIP.bind_temperature``) when the model has one."""
     out = []
     for m in model.modules():
         eng = getattr(m, "_engine", None)
         if eng is not None and hasattr(eng, "flat"):
             out.append(eng.flat)
+        tflat = getattr(m, "_temperature_flat", None)
+        if tflat is not None:
+            out.append(tflat)
     return out
 
 

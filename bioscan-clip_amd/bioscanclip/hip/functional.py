@@ -62,6 +62,39 @@ class _InfoNCE(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(outs)
 
 
+class _InfoNCETrainableScale(torch.autograd.Function):
+    """``_InfoNCE`` with a learnable temperature: ``log_scale`` is t = log(scale), one f32 on the GPU that the kernels read when they
+    run (``bsclip_infonce_fwd_bwd_ts``).  The same call leaves dLoss/dt next to dLoss/dz; the returned loss carries ``scale_out``
+    = (dLoss/dt of the own rows, the scale used) for logging."""
+
+    @staticmethod
+    def forward(ctx, labels, log_scale, row0, n_local, workspace, scale_out, *zs):
+        zs = [z.contiguous() for z in zs]
+        N = zs[0].shape[0]
+        n_local = N if n_local is None else n_local
+        loss = torch.zeros(1, dtype=F32, device=zs[0].device)
+        need_grad = ctx.needs_input_grad[1] or any(ctx.needs_input_grad[6:])
+        dzs = [torch.empty(n_local, z.shape[1], dtype=F32, device=z.device) for z in zs] if need_grad else None
+        ops.infonce_fwd_bwd_ts(zs, labels, log_scale, loss, dzs, scale_out, row0=row0, n_local=n_local, workspace=workspace)
+        ctx.dzs, ctx.row0, ctx.N, ctx.scale_out, ctx.t_shape = dzs, row0, N, scale_out, log_scale.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        outs = []
+        for i, d in enumerate(ctx.dzs):
+            if not ctx.needs_input_grad[6 + i]:
+                outs.append(None)
+            elif d.shape[0] == ctx.N:
+                outs.append(d * g)
+            else:  # gathered batch: only the local rows carry gradient (SURVEY 8e)
+                full = torch.zeros(ctx.N, d.shape[1], dtype=F32, device=d.device)
+                full[ctx.row0:ctx.row0 + d.shape[0]] = d * g
+                outs.append(full)
+        dt = (ctx.scale_out[0] * g).reshape(ctx.t_shape) if ctx.needs_input_grad[1] else None
+        return (None, dt, None, None, None, None) + tuple(outs)
+
+
 _WS = {}
 
 
@@ -81,6 +114,14 @@ def infonce(zs, labels, scale, row0=0, n_local=None):
     if not zs[0].is_cuda:
         raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
     ws = _workspace(zs[0].shape[0], len(zs), zs[0].device)
+    if torch.is_tensor(scale):   # a learnable temperature: ``scale`` is its logarithm, read on the device
+        if not (scale.is_cuda and scale.dtype == F32 and scale.numel() == 1):
+            raise ValueError("infonce: a tensor scale is the log scale, a 1-element f32 CUDA tensor")
+        scale_out = torch.empty(2, dtype=F32, device=zs[0].device)
+        loss = _InfoNCETrainableScale.apply(labels.to(torch.int64).contiguous(), scale, row0, n_local, ws, scale_out,
+                                            *[z.to(F32) for z in zs])
+        loss.scale_out = scale_out   # (dLoss/dt of the own rows, the scale used)
+        return loss
     return _InfoNCE.apply(labels.to(torch.int64).contiguous(), float(scale), row0, n_local, ws, *[z.to(F32) for z in zs])
 
 

@@ -99,6 +99,9 @@ class GraphedStep:
                 flat = getattr(eng, "flat", None)
                 ws = getattr(eng, "ws", None)
                 sig.append((id(eng), None if ws is None else ws["gen"], 0 if flat is None else flat.data.data_ptr()))
+            tflat = getattr(m, "_temperature_flat", None)   # the learnable temperature's buffer: the loss kernels read it
+            if tflat is not None:
+                sig.append((id(tflat), None, tflat.data.data_ptr()))
         return tuple(sig)
 
     def accepts(self, image, dna, text, label):

@@ -624,8 +624,8 @@ def infonce_workspace_floats(N, nmod):
     return n
 
 
-def infonce_fwd_bwd(zs, labels, scale, loss_out, dzs=None, row0=0, n_local=None, workspace=None):
-    """zs: list of 2-3 f32 [N, 768]; dzs: list of f32 [n_local, 768] (or None for loss only)."""
+def _infonce_args(zs, labels, loss_out, dzs, row0, n_local, workspace):
+    """The checks ``infonce_fwd_bwd`` and ``infonce_fwd_bwd_ts`` share; returns (nmod, N, D, n_local, zp, dzp)."""
     nmod = len(zs)
     if nmod < 2:
         raise ValueError("Too less element for calculating the contrastive loss.")
@@ -643,8 +643,26 @@ def infonce_fwd_bwd(zs, labels, scale, loss_out, dzs=None, row0=0, n_local=None,
         _req(len(dzs) == nmod and all(d.dtype == F32 and d.is_contiguous() and tuple(d.shape) == (n_local, D) for d in dzs),
              "dzs f32 [n_local, D]")
         dzp = (ctypes.c_void_p * nmod)(*[d.data_ptr() for d in dzs])
+    return nmod, N, D, n_local, zp, dzp
+
+
+def infonce_fwd_bwd(zs, labels, scale, loss_out, dzs=None, row0=0, n_local=None, workspace=None):
+    """zs: list of 2-3 f32 [N, 768]; dzs: list of f32 [n_local, 768] (or None for loss only)."""
+    nmod, N, D, n_local, zp, dzp = _infonce_args(zs, labels, loss_out, dzs, row0, n_local, workspace)
     check(_l.load().bsclip_infonce_fwd_bwd(zp, nmod, _p(labels), N, D, float(scale), row0, n_local, _p(loss_out), dzp,
                                            _p(workspace), _stream()))
+
+
+def infonce_fwd_bwd_ts(zs, labels, log_scale, loss_out, dzs, scale_out, row0=0, n_local=None, workspace=None):
+    """``infonce_fwd_bwd`` at the scale exp(clamp(t, 0, ln 100)), t = ``log_scale`` (one f32 on the GPU), read by the kernels when
+    they run.  ``scale_out`` f32 [2] receives (the own rows' share of dLoss/dt, the scale used)."""
+    _req(torch.is_tensor(log_scale) and log_scale.is_cuda and log_scale.dtype == F32 and log_scale.numel() == 1,
+         "log_scale must be a 1-element f32 CUDA tensor")
+    _req(torch.is_tensor(scale_out) and scale_out.is_cuda and scale_out.dtype == F32 and scale_out.is_contiguous()
+         and scale_out.numel() >= 2, "scale_out must be a contiguous f32 CUDA tensor with >= 2 elements")
+    nmod, N, D, n_local, zp, dzp = _infonce_args(zs, labels, loss_out, dzs, row0, n_local, workspace)
+    check(_l.load().bsclip_infonce_fwd_bwd_ts(zp, nmod, _p(labels), N, D, _p(log_scale), row0, n_local, _p(loss_out), dzp,
+                                              _p(scale_out), _p(workspace), _stream()))
 
 
 def _topk_outputs(queries, K, k, msg_q, msg_k):

@@ -3,8 +3,10 @@
 ``ClipLoss`` with gather_with_grad=False, local_loss=False: loss_func.py:58-91,117-165).
 
 The arithmetic is the fused HIP InfoNCE (``bsclip_infonce_fwd_bwd``): soft-target CE over every ordered modality
-pair, temperature fixed at construction, second ``F.normalize`` applied inside (loss_func.py:43-44).
+pair, second ``F.normalize`` applied inside (loss_func.py:43-44).  The temperature is fixed at construction (a float) or
+learnable: an ``nn.Parameter`` holding t = log(scale), which the kernels read on the device (``bsclip_infonce_fwd_bwd_ts``).
 """
+import torch
 import torch.nn as nn
 
 from bioscanclip.hip.functional import infonce
@@ -25,7 +27,26 @@ class ContrastiveLoss(nn.Module):
         if criterion is not None and not isinstance(criterion, nn.CrossEntropyLoss):
             raise TypeError("ContrastiveLoss: the HIP path implements nn.CrossEntropyLoss() with soft targets only")
         self.criterion = criterion
-        self.logit_scale = logit_scale
+        # a float, or an nn.Parameter holding t = log(scale) (model.logit_scale: the model owns it, its optimizer updates it).  Kept
+        # out of this module's own parameters, so that the criterion adds nothing to a state dict or an optimizer.
+        object.__setattr__(self, "logit_scale", logit_scale)
+        self._scale_out = None
+
+    def current_scale(self):
+        """The logit scale as a device scalar tensor: for a learnable temperature the scale the last forward used (before any
+        forward, exp(clamp(t, 0, ln 100)) of the parameter's present value), the fixed float otherwise."""
+        t = self.logit_scale
+        if not torch.is_tensor(t):
+            dev = "cuda" if torch.cuda.is_available() else "cpu"
+            return torch.tensor(float(t), dtype=torch.float32, device=dev)
+        if self._scale_out is not None:
+            return self._scale_out[1]
+        return t.detach().float().clamp(0.0, 4.605170185988092).exp().reshape(())
+
+    def _infonce(self, feats, labels, **kw):
+        loss = infonce(feats, labels, self.logit_scale, **kw)
+        self._scale_out = getattr(loss, "scale_out", None)
+        return loss
 
     def forward(self, image_features, dna_features, text_features, label, logit_scale=1 / 0.07):
         # the per-call ``logit_scale`` argument is ignored, as in the reference (loss_func.py:46-47 use self.logit_scale)
@@ -33,7 +54,7 @@ class ContrastiveLoss(nn.Module):
         feature_list = [item for item in feature_list if item is not None]
         if len(feature_list) < 2:
             raise ValueError("Too less element for calculating the contrastive loss.")
-        return infonce(feature_list, label, self.logit_scale)
+        return self._infonce(feature_list, label)
 
 
 class GlobalBatchContrastiveLoss(ContrastiveLoss):
@@ -44,6 +65,8 @@ class GlobalBatchContrastiveLoss(ContrastiveLoss):
     gradients.  Equivalent to the single-process loss on the concatenated batch."""
 
     def __init__(self, criterion=None, logit_scale=1 / 0.07, group=None, overlap=True):
+        if torch.is_tensor(logit_scale):
+            raise ValueError("GlobalBatchContrastiveLoss: a trainable temperature is not built for more than one rank")
         super().__init__(criterion, logit_scale)
         self.group = group
         if overlap:  # all-gathers from the tower streams, gradient all-reduces from the encoder nodes (hip/dist.py)

@@ -5,6 +5,8 @@ text encoders, each followed by ``F.normalize(p=2, dim=-1)`` (here the HIP l2nor
 modality.  The open_clip branch (simple_clip.py:36-44,141-145) is outside the accelerated path
 and raises.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -42,11 +44,25 @@ class SimpleCLIP(nn.Module):
         self.language_encoder = language_encoder
         self.open_clip_model = None
         self.tokenizer_for_open_clip = None
+        self._temperature_flat = None
+
+    def bind_temperature(self):
+        """The learnable temperature's flat buffer (``model.logit_scale``, when the model has one): one parameter padded to four
+        floats, the home FusedAdamW updates like an engine's.  Built with the first training forward, and again when the parameter
+        was moved (``model.to``) -- ``hip.dist.flat_buffers`` finds it here."""
+        t = self._parameters.get("logit_scale")
+        if t is None or not (t.requires_grad and t.is_cuda and torch.is_grad_enabled()):
+            return
+        flat = self._temperature_flat
+        if flat is None or flat.params[0] is not t or not flat.valid():
+            from bioscanclip.hip.engine import FlatParams
+            self._temperature_flat = FlatParams([t], t.device)
 
     def forward(self, image_input, dna_input, language_input):
         image_output = None
         dna_output = None
         language_output = None
+        self.bind_temperature()
 
         # The towers are independent until the loss: each runs on its own HIP stream (forward here, backward through
         # autograd, which replays a node on the stream of its forward), so one tower's memory-bound kernels and
@@ -106,6 +122,11 @@ def _load_vit(args):
     return vit
 
 
+def trainable_temperature(args):
+    """``model_config.trainable_temperature``: the learnable logit scale (off when the key is absent)."""
+    return bool(getattr(getattr(args, "model_config", None), "trainable_temperature", False))
+
+
 def load_clip_model(args, device=None):
     """Reference simple_clip.py:125-203, same config keys (``args.model_config.{image,dna,language,output_dim,
     disable_lora}``, ``args.bioscan_bert_checkpoint``).  ``disable_lora: true`` selects full fine-tuning (hip/engine_ft.py).
@@ -154,6 +175,11 @@ def load_clip_model(args, device=None):
             raise NotImplementedError("feature-input MLP encoders are outside the accelerated path")
 
     model = SimpleCLIP(image_encoder=image_encoder, dna_encoder=dna_encoder, language_encoder=language_encoder)
+
+    if trainable_temperature(args):
+        # t = log(logit scale), the initial value of the reference's SimpleCLIP_With_Trainable_Temp sketch; the contrastive loss
+        # reads it on the device (ContrastiveLoss(logit_scale=model.logit_scale)).  Only training uses it: no forward reads it.
+        model.logit_scale = nn.Parameter(torch.tensor(math.log(1 / 0.07)))
 
     if device is not None:
         model.to(device)

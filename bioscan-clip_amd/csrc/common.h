@@ -333,7 +333,7 @@ void bsclip_launch_attn_bwd_x3(const float* qkv, int ld_qkv, const float* dctx, 
 // gemm.hip, internal: the fused InfoNCE products on the 256x256 ping-pong GEMM (see the EPI_LSE_PART / EPI_LOSS_W epilogues)
 int bsclip_gemm_infonce(int mode, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                         const int64_t* labels, const float* cnt, const float* lse_row, const float* lse_col, float* part,
-                        float logit_scale, float coef, int n_valid, int row_base, void* stream);
+                        float logit_scale, float coef, int n_valid, int row_base, const float* scale_dev, void* stream);
 
 // gemm.hip, internal: nb <= BSCLIP_GEMM_BATCH_MAX products of one shape in ONE launch of the 128x128 gemm_nt_kernel program, the
 // product on blockIdx.z and its operand pointers in a table passed by value.  epilogue: BSCLIP_EPI_F32, or BSCLIP_EPI_RESID_F32

@@ -335,9 +335,11 @@ extern "C" int bsclip_gemm_splitk_f32(const void* A, int lda, const void* B, int
 // fused InfoNCE products (called by loss.hip; not part of the public ABI)
 // ---------------------------------------------------------------------------------------------------------------
 // mode 0: pass 1 -- part[M, N/256, 4] from cosines A[M,K] . B[N,K]^T;  mode 1: pass 2 -- C = dL/dG in split form [M, 3*Np].
+// scale_dev != nullptr (trainable temperature): the logit scale is scale_dev[1], read by the kernel; `logit_scale` is unused and
+// `coef` holds the divisor P N.  Pass 1 then also fills part[..][3].
 int bsclip_gemm_infonce(int mode, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                         const int64_t* labels, const float* cnt, const float* lse_row, const float* lse_col, float* part,
-                        float logit_scale, float coef, int n_valid, int row_base, void* stream) {
+                        float logit_scale, float coef, int n_valid, int row_base, const float* scale_dev, void* stream) {
     BSCLIP_REQUIRE(A && B && labels && M > 0 && N % 256 == 0 && K % 64 == 0, "bsclip_gemm_infonce: bad shape M=%d N=%d K=%d", M, N, K);
     EpiArgs e = epi_from_public(nullptr, N);
     e.labels = labels;
@@ -349,18 +351,27 @@ int bsclip_gemm_infonce(int mode, const void* A, int lda, const void* B, int ldb
     e.coef = coef;
     e.n_valid = n_valid;
     e.row_base = row_base;
+    e.scale_dev = scale_dev;
     const int tiles_m = ceil_div(M, 256), tiles_n = N / 256;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bf16_t* a = static_cast<const bf16_t*>(A);
     const bf16_t* b = static_cast<const bf16_t*>(B);
     if (mode == 0) {
         BSCLIP_REQUIRE(part, "bsclip_gemm_infonce: part is null");
-        hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LSE_PART, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
-                           ldc, M, N, K, tiles_n, e);
+        if (scale_dev)
+            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LSE_PART_TS, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb,
+                               C, ldc, M, N, K, tiles_n, e);
+        else
+            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LSE_PART, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
+                               ldc, M, N, K, tiles_n, e);
     } else {
         BSCLIP_REQUIRE(C && cnt && lse_row && lse_col && ldc % 3 == 0, "bsclip_gemm_infonce: pass 2 operands");
-        hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LOSS_W, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
-                           ldc, M, N, K, tiles_n, e);
+        if (scale_dev)
+            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LOSS_W_TS, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
+                               ldc, M, N, K, tiles_n, e);
+        else
+            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI_LOSS_W, false>), dim3(tiles_m * tiles_n), dim3(512), 0, s, a, lda, b, ldb, C,
+                               ldc, M, N, K, tiles_n, e);
     }
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;

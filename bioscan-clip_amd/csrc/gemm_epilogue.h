@@ -23,7 +23,12 @@ struct EpiArgs {
     unsigned long long* diag;  // diagnostic build only: per-workgroup phase stamps (100 MHz wall clock)
     int pers_gw;               // persistent kernel: column tiles per super-column of its tile order (set by launch_pers)
     // fp8 main operands (OP != 0): C = epilogue(alpha[n] * (A8 . B8^T + A_aug . B_aug^T) + bias)
-    const float* alpha;                   // [N] dequantisation scale of output column n (activation scale x weight-row scale)
+    union {
+        const float* alpha;               // [N] dequantisation scale of output column n (activation scale x weight-row scale)
+        // trainable temperature (EPI_LSE_PART_TS / EPI_LOSS_W_TS, never fp8; shares the slot so that no kernel's argument block
+        // changes): scale_dev[1] is the logit scale, read when the kernel runs; `coef` then holds the divisor P N of scale / (P N)
+        const float* scale_dev;
+    };
     const bf16_t* a_aug;                  // bf16 [M, 64] K-augmentation block (LoRA t columns), nullable
     const bf16_t* b_aug;                  // bf16 [N, 64] matching weight columns (LoRA B / alpha[n])
     int ld_a_aug, ld_b_aug;
@@ -41,6 +46,9 @@ struct EpiArgs {
 };
 constexpr int EPI_LSE_PART = 100;  // internal epilogues, not part of the public enum
 constexpr int EPI_LOSS_W = 101;
+// the same two with the scale in device memory; pass 1 also fills part[..][3] = sum_j exp(x_ij - max) G_ij (for dLoss/dt)
+constexpr int EPI_LSE_PART_TS = 102;
+constexpr int EPI_LOSS_W_TS = 103;
 
 // ---------------------------------------------------------------------------------------------------------------
 // GELU table for the 256x256 kernel's epilogue

@@ -491,7 +491,12 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
     // Per output row the tile's 256 columns live in 4 waves (wc) x 4 lanes (fq) x 16 registers: in-lane reduction, two xor
     // shuffles (16, 32) across the lanes that share a row, LDS across the four waves.  Written per (row, column tile):
     // (max, sum exp(x - max), sum over same-label columns of x); infonce_combine_kernel merges the column tiles.
-    if constexpr (EPI == EPI_LSE_PART) {
+    // EPI_LSE_PART_TS: the scale comes from device memory, and the fourth float carries sum_j exp(x_ij - max) G_ij (G = cosine).
+    if constexpr (EPI == EPI_LSE_PART || EPI == EPI_LSE_PART_TS) {
+        constexpr bool TS = EPI == EPI_LSE_PART_TS;
+        float ls;
+        if constexpr (TS) ls = e.scale_dev[1];
+        else ls = e.logit_scale;
         __syncthreads();  // every wave is past its last fragment read: the staging LDS is free
         float* red = reinterpret_cast<float*>(smem);  // [256 rows][4 waves][4]
         long lcol[2][2][4];
@@ -520,13 +525,13 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
                             const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
-                            const float v = n < e.n_valid ? acc[mi][ni][i][j][c] * e.logit_scale : -INFINITY;
+                            const float v = n < e.n_valid ? acc[mi][ni][i][j][c] * ls : -INFINITY;
                             x[(ni * 2 + j) * 4 + c] = v;
                             mx = fmaxf(mx, v);
                         }
                 mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                float se = 0.f, dot = 0.f;
+                float se = 0.f, dot = 0.f, sg = 0.f;
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -536,16 +541,22 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
                             const float v = x[(ni * 2 + j) * 4 + c];
                             se += mx == -INFINITY ? 0.f : __expf(v - mx);
                             dot += lcol[ni][j][c] == li ? v : 0.f;
+                            // exp(-inf) = 0 in the padding columns, where the accumulator is finite
+                            if constexpr (TS) sg += mx == -INFINITY ? 0.f : __expf(v - mx) * acc[mi][ni][i][j][c];
                         }
                 se += __shfl_xor(se, 16, 64);
                 se += __shfl_xor(se, 32, 64);
                 dot += __shfl_xor(dot, 16, 64);
                 dot += __shfl_xor(dot, 32, 64);
-                if (fq == 0) *reinterpret_cast<f32x4*>(red + (r * 4 + wc) * 4) = f32x4{mx, se, dot, 0.f};
+                if constexpr (TS) {
+                    sg += __shfl_xor(sg, 16, 64);
+                    sg += __shfl_xor(sg, 32, 64);
+                }
+                if (fq == 0) *reinterpret_cast<f32x4*>(red + (r * 4 + wc) * 4) = f32x4{mx, se, dot, sg};
             }
         __syncthreads();
         if (tid < 256 && m0 + tid < M) {
-            float mm = -INFINITY, ss = 0.f, dd = 0.f;
+            float mm = -INFINITY, ss = 0.f, dd = 0.f, gg = 0.f;
             f32x4 p[4];
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
@@ -555,16 +566,26 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
                 ss += p[w][0] == -INFINITY ? 0.f : p[w][1] * __expf(p[w][0] - mm);
+                if constexpr (TS) gg += p[w][0] == -INFINITY ? 0.f : p[w][3] * __expf(p[w][0] - mm);
                 dd += p[w][2];
             }
-            *reinterpret_cast<f32x4*>(e.part + ((size_t)(m0 + tid) * tiles_n + tile_n) * 4) = f32x4{mm, ss, dd, 0.f};
+            *reinterpret_cast<f32x4*>(e.part + ((size_t)(m0 + tid) * tiles_n + tile_n) * 4) = f32x4{mm, ss, dd, gg};
         }
         return;
     }
     // ---- fused InfoNCE, pass 2: dLoss/dG of the tile, straight from the accumulators, in split-bf16 form --------------
     // w_ij = coef (cnt_i exp(x - lse_ab[i]) + cnt_j exp(x - lse_ba[j]) - 2 T_ij) for j < n_valid, else 0; written as the
     // operand [hi | hi | lo] of the gradient GEMM (C bf16 [M, ldc = 3 * Np]) -- the logits themselves are never stored.
-    if constexpr (EPI == EPI_LOSS_W) {
+    // EPI_LOSS_W_TS: logit scale and coef = scale / (P N) from device memory (e.coef holds P N).
+    if constexpr (EPI == EPI_LOSS_W || EPI == EPI_LOSS_W_TS) {
+        float ls, cf;
+        if constexpr (EPI == EPI_LOSS_W_TS) {
+            ls = e.scale_dev[1];
+            cf = ls / e.coef;
+        } else {
+            ls = e.logit_scale;
+            cf = e.coef;
+        }
         constexpr int SBW = 528;
         __syncthreads();
         char* slab_hi = smem + g * (64 * SBW);
@@ -600,9 +621,9 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const bf16_t* __restric
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
                             const int n = n0 + 64 * wc + 32 * ni + 16 * j + 4 * fq + c;
-                            const float xv = acc[mi][ni][i][j][c] * e.logit_scale;
+                            const float xv = acc[mi][ni][i][j][c] * ls;
                             const float t = lcol[ni][j][c] == li ? 2.0f : 0.0f;
-                            wv[c] = n < e.n_valid ? e.coef * (ci * __expf(xv - lr) + ccol[ni][j][c] * __expf(xv - lcolse[ni][j][c]) - t) : 0.f;
+                            wv[c] = n < e.n_valid ? cf * (ci * __expf(xv - lr) + ccol[ni][j][c] * __expf(xv - lcolse[ni][j][c]) - t) : 0.f;
                             hi[c] = bf2f(f2bf(wv[c]));
                         }
                         const int off = (16 * i + fr) * SBW + (64 * wc + 32 * ni + 16 * j + 4 * fq) * 2;

@@ -137,9 +137,13 @@ __global__ void loss_count_kernel(const int64_t* __restrict__ labels, int N, flo
 }
 
 // One wave per row i < N of G (cosines, ld = Np): LSE_i of s*G over j < N, and contrib_i = cnt_i*LSE_i - sum_j T_ij s G_ij
+// TS (trainable temperature): also tcontrib_i = sum_j (cnt_i p_ij - T_ij) G_ij, the row's term of dLoss/dt, from
+// sum_j exp(x_ij - m) G_ij carried next to the sum of exponentials
+template <bool TS>
 __device__ __forceinline__ void loss_row_reduce_rows(const float* __restrict__ G, int row0, int nrows, int N, int Np, float s,
                                                      const int64_t* __restrict__ labels, const float* __restrict__ cnt,
-                                                     float* __restrict__ lse, float* __restrict__ contrib) {
+                                                     float* __restrict__ lse, float* __restrict__ contrib,
+                                                     float* __restrict__ tcontrib) {
     const int lane = threadIdx.x & 63;
     const int r = (blockIdx.x * 256 + threadIdx.x) >> 6;  // row inside the slab
     if (r >= nrows) return;
@@ -149,25 +153,36 @@ __device__ __forceinline__ void loss_row_reduce_rows(const float* __restrict__ G
     float m = -INFINITY;
     for (int j = lane; j < N; j += 64) m = fmaxf(m, g[j]);
     m = wave_max(m) * s;
-    float se = 0.f, dot = 0.f;
+    float se = 0.f, dot = 0.f, sg = 0.f;
     for (int j = lane; j < N; j += 64) {
         const float x = g[j] * s;
         se += __expf(x - m);
         if (labels[j] == li) dot += x;
+        if constexpr (TS) sg += __expf(x - m) * g[j];
     }
     se = wave_sum(se);
     dot = wave_sum(dot);
+    if constexpr (TS) sg = wave_sum(sg);
     const float l = m + __logf(se);
     if (lane == 0) {
         lse[row] = l;
         contrib[row] = cnt[row] * l - dot;
+        if constexpr (TS) tcontrib[row] = cnt[row] * (sg / se) - dot / s;
     }
 }
 __global__ __launch_bounds__(256) void loss_row_reduce_kernel(const float* __restrict__ G, int row0, int nrows, int N,
                                                                int Np, float s, const int64_t* __restrict__ labels,
                                                                const float* __restrict__ cnt, float* __restrict__ lse,
                                                                float* __restrict__ contrib) {
-    loss_row_reduce_rows(G, row0, nrows, N, Np, s, labels, cnt, lse, contrib);
+    loss_row_reduce_rows<false>(G, row0, nrows, N, Np, s, labels, cnt, lse, contrib, nullptr);
+}
+// the scale is sc[1], read here; tcontrib is indexed like contrib
+__global__ __launch_bounds__(256) void loss_row_reduce_ts_kernel(const float* __restrict__ G, int row0, int nrows, int N,
+                                                                  int Np, const float* __restrict__ sc,
+                                                                  const int64_t* __restrict__ labels,
+                                                                  const float* __restrict__ cnt, float* __restrict__ lse,
+                                                                  float* __restrict__ contrib, float* __restrict__ tcontrib) {
+    loss_row_reduce_rows<true>(G, row0, nrows, N, Np, sc[1], labels, cnt, lse, contrib, tcontrib);
 }
 // directed pair blockIdx.y: all N rows of its kept logits matrix G[p] ([Np, Np]); lse / contrib are indexed by slot a * nmod + b
 __global__ __launch_bounds__(256) void loss_row_reduce_batched_kernel(const float* __restrict__ G, int nmod, int N, int Np, float s,
@@ -178,7 +193,20 @@ __global__ __launch_bounds__(256) void loss_row_reduce_batched_kernel(const floa
     int a, b;
     pair_ab(p, nmod, a, b);
     const size_t slot = a * nmod + b;
-    loss_row_reduce_rows(G + (size_t)p * Np * Np, 0, N, N, Np, s, labels, cnt, lse + slot * Np, contrib + slot * Np);
+    loss_row_reduce_rows<false>(G + (size_t)p * Np * Np, 0, N, N, Np, s, labels, cnt, lse + slot * Np, contrib + slot * Np, nullptr);
+}
+__global__ __launch_bounds__(256) void loss_row_reduce_batched_ts_kernel(const float* __restrict__ G, int nmod, int N, int Np,
+                                                                          const float* __restrict__ sc,
+                                                                          const int64_t* __restrict__ labels,
+                                                                          const float* __restrict__ cnt, float* __restrict__ lse,
+                                                                          float* __restrict__ contrib,
+                                                                          float* __restrict__ tcontrib) {
+    const int p = blockIdx.y;
+    int a, b;
+    pair_ab(p, nmod, a, b);
+    const size_t slot = a * nmod + b;
+    loss_row_reduce_rows<true>(G + (size_t)p * Np * Np, 0, N, N, Np, sc[1], labels, cnt, lse + slot * Np, contrib + slot * Np,
+                               tcontrib + slot * Np);
 }
 
 // W[i_local, j] = coef * ( cnt_i exp(sG - lse_ab[i]) + cnt_j exp(sG - lse_ba[j]) - 2 T_ij ), j < N, else 0,
@@ -211,6 +239,15 @@ __global__ __launch_bounds__(256) void loss_w_kernel(const float* __restrict__ G
                                                       const float* __restrict__ lse_ba, bf16_t* __restrict__ W) {
     loss_w_elems(G, N, Np, row0, n_local, s, coef, labels, cnt, lse_ab, lse_ba, W);
 }
+// the scale is sc[1], read here; coef = scale / den with den = P N, the host's division of the by-value form
+__global__ __launch_bounds__(256) void loss_w_ts_kernel(const float* __restrict__ G, int N, int Np, int row0, int n_local,
+                                                         const float* __restrict__ sc, float den,
+                                                         const int64_t* __restrict__ labels, const float* __restrict__ cnt,
+                                                         const float* __restrict__ lse_ab, const float* __restrict__ lse_ba,
+                                                         bf16_t* __restrict__ W) {
+    const float s = sc[1];
+    loss_w_elems(G, N, Np, row0, n_local, s, s / den, labels, cnt, lse_ab, lse_ba, W);
+}
 // directed pair blockIdx.y: rows [row0, row0 + n_local) of its kept logits matrix G[p] -> W[p] ([n_local, 3 Np], w_stride apart)
 __global__ __launch_bounds__(256) void loss_w_batched_kernel(const float* __restrict__ G, int nmod, int N, int Np, int row0,
                                                               int n_local, float s, float coef,
@@ -222,6 +259,18 @@ __global__ __launch_bounds__(256) void loss_w_batched_kernel(const float* __rest
     pair_ab(p, nmod, a, b);
     loss_w_elems(G + ((size_t)p * Np + row0) * Np, N, Np, row0, n_local, s, coef, labels, cnt, lse + (size_t)(a * nmod + b) * Np,
                  lse + (size_t)(b * nmod + a) * Np, W + p * w_stride);
+}
+__global__ __launch_bounds__(256) void loss_w_batched_ts_kernel(const float* __restrict__ G, int nmod, int N, int Np, int row0,
+                                                                 int n_local, const float* __restrict__ sc, float den,
+                                                                 const int64_t* __restrict__ labels,
+                                                                 const float* __restrict__ cnt, const float* __restrict__ lse,
+                                                                 bf16_t* __restrict__ W, size_t w_stride) {
+    const int p = blockIdx.y;
+    int a, b;
+    pair_ab(p, nmod, a, b);
+    const float s = sc[1];
+    loss_w_elems(G + ((size_t)p * Np + row0) * Np, N, Np, row0, n_local, s, s / den, labels, cnt,
+                 lse + (size_t)(a * nmod + b) * Np, lse + (size_t)(b * nmod + a) * Np, W + p * w_stride);
 }
 
 // loss = scale * sum over the directed pairs a != b of contrib[(a*nmod+b)*Np + i], i < N -- single workgroup, fixed order
@@ -244,24 +293,86 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
     if (threadIdx.x == 0) loss_out[0] = red[0] * scale;
 }
 
+// ---- trainable temperature ----
+// The scale lives in device memory as t = log s, so that a replayed graph sees each step's value.  loss_scale_kernel runs ahead of
+// everything else and leaves s = exp(clamp(t, 0, ln 100)) (open_clip's range) in sc[1]; every later kernel reads it from there.
+// The ends of the range are stored exactly (1 and 100), so that a clamped t gives the bits of the by-value entry at that scale.
+constexpr float LN_100 = 4.60517018598809136804f;
+__global__ void loss_scale_kernel(const float* __restrict__ log_scale, float* __restrict__ sc) {
+    const float t = log_scale[0];
+    sc[1] = t <= 0.f ? 1.0f : t >= LN_100 ? 100.0f : expf(t);
+}
+// loss_final_kernel's loss (the same sums in the same order: the same bits), then the rank's share of dLoss/dt:
+// sc[0] = s * scale * sum over a != b and the own rows i in [row0, row0 + n_own) of tcontrib, 0 where the clamp is flat
+// (t outside [0, ln 100]) or nothing is differentiated (n_own = 0).  One workgroup, fixed order, no atomics.
+__global__ __launch_bounds__(256) void loss_final_ts_kernel(const float* __restrict__ contrib, const float* __restrict__ tcontrib,
+                                                             int nmod, int Np, int N, int row0, int n_own, float scale,
+                                                             const float* __restrict__ log_scale, float* __restrict__ sc,
+                                                             float* __restrict__ loss_out) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int slot = 0; slot < nmod * nmod; ++slot) {
+        if (slot / nmod == slot % nmod) continue;
+        for (int i = threadIdx.x; i < N; i += 256) s += contrib[(size_t)slot * Np + i];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss_out[0] = red[0] * scale;
+    __syncthreads();
+    float g = 0.f;
+    for (int slot = 0; slot < nmod * nmod; ++slot) {
+        if (slot / nmod == slot % nmod) continue;
+        for (int i = row0 + threadIdx.x; i < row0 + n_own; i += 256) g += tcontrib[(size_t)slot * Np + i];
+    }
+    red[threadIdx.x] = g;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float t = log_scale[0];
+        sc[0] = (n_own > 0 && t >= 0.f && t <= LN_100) ? red[0] * (sc[1] * scale) : 0.f;
+    }
+}
+
 // merge the per-column-tile triples of pass 1: LSE_i = M + log sum_t s_t exp(m_t - M), contrib_i = cnt_i LSE_i - sum_t dot_t
-__global__ __launch_bounds__(256) void infonce_combine_kernel(const float* __restrict__ part, int N, int tiles,
-                                                              const float* __restrict__ cnt, float* __restrict__ lse,
-                                                              float* __restrict__ contrib) {
+// TS: the fourth float of a triple is sum_j exp(x_ij - m_t) G_ij over the tile; tcontrib_i as in loss_row_reduce_rows
+template <bool TS>
+__device__ __forceinline__ void infonce_combine_rows(const float* __restrict__ part, int N, int tiles, const float* __restrict__ cnt,
+                                                     float* __restrict__ lse, float* __restrict__ contrib, float scale,
+                                                     float* __restrict__ tcontrib) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const f32x4* p = reinterpret_cast<const f32x4*>(part) + (size_t)i * tiles;
     float m = -INFINITY;
     for (int t = 0; t < tiles; ++t) m = fmaxf(m, p[t][0]);
-    float s = 0.f, dot = 0.f;
+    float s = 0.f, dot = 0.f, sg = 0.f;
     for (int t = 0; t < tiles; ++t) {   // fixed order: bitwise reproducible
         const f32x4 v = p[t];
         s += v[0] == -INFINITY ? 0.f : v[1] * __expf(v[0] - m);
+        if constexpr (TS) sg += v[0] == -INFINITY ? 0.f : v[3] * __expf(v[0] - m);
         dot += v[2];
     }
     const float l = m + __logf(s);
     lse[i] = l;
     contrib[i] = cnt[i] * l - dot;
+    if constexpr (TS) tcontrib[i] = cnt[i] * (sg / s) - dot / scale;
+}
+__global__ __launch_bounds__(256) void infonce_combine_kernel(const float* __restrict__ part, int N, int tiles,
+                                                              const float* __restrict__ cnt, float* __restrict__ lse,
+                                                              float* __restrict__ contrib) {
+    infonce_combine_rows<false>(part, N, tiles, cnt, lse, contrib, 0.f, nullptr);
+}
+__global__ __launch_bounds__(256) void infonce_combine_ts_kernel(const float* __restrict__ part, int N, int tiles,
+                                                                 const float* __restrict__ cnt, float* __restrict__ lse,
+                                                                 float* __restrict__ contrib, const float* __restrict__ sc,
+                                                                 float* __restrict__ tcontrib) {
+    infonce_combine_rows<true>(part, N, tiles, cnt, lse, contrib, sc[1], tcontrib);
 }
 
 // 0 = by size (default): below 2 048 padded rows a product is <= 8 x 8 tiles of the 256 x 256 GEMM -- at the bench's N = 256 ONE
@@ -317,16 +428,21 @@ extern "C" int64_t bsclip_infonce_workspace_floats(int N, int nmod) {
     return make_layout(N, nmod, 768).total;
 }
 
-extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, float scale,
-                                      int row0, int n_local, float* loss_out, float* const* dz, float* workspace,
-                                      void* stream) {
+// What the two entries share.  sc == nullptr: `scale` by value -- bsclip_infonce_fwd_bwd, launch for launch what it always was.
+// sc != nullptr (bsclip_infonce_fwd_bwd_ts; sc is its scale_out): the same three forms with the scale read from sc[1] by every
+// kernel that needs it, one launch (loss_scale_kernel) ahead of them, and pass 1 also leaves each row's term of dLoss/dt in
+// `tcontrib`, which loss_final_ts_kernel sums over the rank's own rows.  tcontrib lies in the dacc region: pass 2 is its only
+// other user and starts after the final kernel.  `fn` names the entry in the messages.
+static int infonce_run(const char* fn, const float* const* z, int nmod, const int64_t* labels, int N, int D, float scale,
+                       const float* log_scale_dev, float* sc, int row0, int n_local, float* loss_out, float* const* dz,
+                       float* workspace, void* stream) {
     // reference error behaviour: loss_func.py:35-36 raises ValueError for < 2 modalities (mapped by the host layer)
     BSCLIP_REQUIRE(nmod >= 2 && nmod <= 3, "Too less element for calculating the contrastive loss.");
-    BSCLIP_REQUIRE(z && labels && loss_out && workspace, "bsclip_infonce_fwd_bwd: null pointer");
-    BSCLIP_REQUIRE(D == 768, "bsclip_infonce_fwd_bwd: D=%d (supported: 768)", D);
+    BSCLIP_REQUIRE(z && labels && loss_out && workspace, "%s: null pointer", fn);
+    BSCLIP_REQUIRE(D == 768, "%s: D=%d (supported: 768)", fn, D);
     BSCLIP_REQUIRE(N > 0 && N <= 16384 && row0 >= 0 && n_local >= 0 && row0 + n_local <= N,
-                   "bsclip_infonce_fwd_bwd: N=%d row0=%d n_local=%d", N, row0, n_local);
-    BSCLIP_REQUIRE(aligned_to(16, workspace), "bsclip_infonce_fwd_bwd: workspace must be 16-B aligned");
+                   "%s: N=%d row0=%d n_local=%d", fn, N, row0, n_local);
+    BSCLIP_REQUIRE(aligned_to(16, workspace), "%s: workspace must be 16-B aligned", fn);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Layout L = make_layout(N, nmod, D);
     const int Np = L.Np;
@@ -343,11 +459,15 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     float* cnt = ws + L.cnt;
     float* dacc = ws + L.dacc;
     float* part = ws + L.part;
+    float* tcontrib = dacc;   // sc only: [nmod * nmod, Np] like contrib (nmod Np D floats are there)
+    const float den = (float)(nmod * (nmod - 1)) * (float)N;
     const bool fused = g_infonce_impl == 2 || (g_infonce_impl == 0 && Np >= 2048);
     const size_t opA = (size_t)Np * 3 * D;  // elements per modality in PA / PB
     const size_t opT = (size_t)D * 3 * Np;  // elements per modality in PBt
     const int ndir = nmod * (nmod - 1);
     const bool want_dz = dz && n_local > 0;
+    const int n_own = want_dz ? n_local : 0;   // rows whose share of dLoss/dt is reported
+    if (sc) hipLaunchKernelGGL(loss_scale_kernel, dim3(1), dim3(1), 0, s, log_scale_dev, sc);   // ahead of every reader of sc[1]
     // the batched form: one slab, and the GEMM would run every product on the 128x128 tile anyway (bsclip_gemm_set_tile can say no)
     const bool batched = g_infonce_impl == 0 && !g_infonce_batched_off && Np <= SLAB_ROWS &&
                          bsclip_gemm_batched_ok(N, Np, 3 * D, BSCLIP_EPI_F32) &&
@@ -356,7 +476,7 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     if (batched) {
         ModPtrs src{};
         for (int m = 0; m < nmod; ++m) {
-            BSCLIP_REQUIRE(z[m], "bsclip_infonce_fwd_bwd: z[%d] is null", m);
+            BSCLIP_REQUIRE(z[m], "%s: z[%d] is null", fn, m);
             src.z[m] = z[m];
         }
         hipLaunchKernelGGL(loss_prep_batched_kernel, dim3(ceil_div(Np, 4), nmod), dim3(256), 0, s, src, N, Np, D, zn, inv, PA, PB);
@@ -378,21 +498,32 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
         }
         int rc = bsclip_gemm_bf16_batched(gl, ndir, 3 * D, 3 * D, Np, N, Np, 3 * D, BSCLIP_EPI_F32, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(loss_row_reduce_batched_kernel, dim3(ceil_div(N, 4), ndir), dim3(256), 0, s, G, nmod, N, Np, scale, labels,
-                           cnt, lse, contrib);
-        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, contrib, nmod, Np, N, 1.0f / ((float)ndir * (float)N),
-                           loss_out);
+        if (sc) {
+            hipLaunchKernelGGL(loss_row_reduce_batched_ts_kernel, dim3(ceil_div(N, 4), ndir), dim3(256), 0, s, G, nmod, N, Np, sc,
+                               labels, cnt, lse, contrib, tcontrib);
+            hipLaunchKernelGGL(loss_final_ts_kernel, dim3(1), dim3(256), 0, s, contrib, tcontrib, nmod, Np, N, row0, n_own,
+                               1.0f / ((float)ndir * (float)N), log_scale_dev, sc, loss_out);
+        } else {
+            hipLaunchKernelGGL(loss_row_reduce_batched_kernel, dim3(ceil_div(N, 4), ndir), dim3(256), 0, s, G, nmod, N, Np, scale,
+                               labels, cnt, lse, contrib);
+            hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, contrib, nmod, Np, N, 1.0f / ((float)ndir * (float)N),
+                               loss_out);
+        }
         BSCLIP_LAUNCH_CHECK();
         if (!want_dz) return BSCLIP_OK;
 
         // ---- pass 2: dL/dG of every pair from the kept logits, then dz_a = sum_b W_ab zn_b: the first partner written, the
         // second added (the association of the slab form: one K loop over both partners would round differently) ----
         const float coef = scale / ((float)ndir * (float)N);
-        for (int a = 0; a < nmod; ++a) BSCLIP_REQUIRE(dz[a], "bsclip_infonce_fwd_bwd: dz[%d] is null", a);
+        for (int a = 0; a < nmod; ++a) BSCLIP_REQUIRE(dz[a], "%s: dz[%d] is null", fn, a);
         long blocks = ((long)n_local * Np + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(loss_w_batched_kernel, dim3((unsigned)blocks, ndir), dim3(256), 0, s, G, nmod, N, Np, row0, n_local, scale,
-                           coef, labels, cnt, lse, W, w_stride);
+        if (sc)
+            hipLaunchKernelGGL(loss_w_batched_ts_kernel, dim3((unsigned)blocks, ndir), dim3(256), 0, s, G, nmod, N, Np, row0, n_local,
+                               sc, den, labels, cnt, lse, W, w_stride);
+        else
+            hipLaunchKernelGGL(loss_w_batched_kernel, dim3((unsigned)blocks, ndir), dim3(256), 0, s, G, nmod, N, Np, row0, n_local,
+                               scale, coef, labels, cnt, lse, W, w_stride);
         for (int k = 0; k < nmod - 1; ++k) {   // k-th partner of every a: pair a * (nmod - 1) + k
             bsclip_gemm_batch gd{};
             for (int a = 0; a < nmod; ++a) {
@@ -422,7 +553,7 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     }
 
     for (int m = 0; m < nmod; ++m) {
-        BSCLIP_REQUIRE(z[m], "bsclip_infonce_fwd_bwd: z[%d] is null", m);
+        BSCLIP_REQUIRE(z[m], "%s: z[%d] is null", fn, m);
         hipLaunchKernelGGL(loss_prep_kernel, dim3(ceil_div(Np, 4)), dim3(256), 0, s, z[m], N, Np, D,
                            zn + (size_t)m * Np * D, inv + (size_t)m * Np, PA + m * opA, PB + m * opA);
         if (dz && n_local > 0)
@@ -439,10 +570,14 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
             const int slot = a * nmod + b;
             if (fused) {
                 int rc = bsclip_gemm_infonce(0, PA + a * opA, 3 * D, PB + b * opA, 3 * D, nullptr, 0, N, Np, 3 * D, labels, cnt,
-                                             nullptr, nullptr, part, scale, 0.f, N, 0, stream);
+                                             nullptr, nullptr, part, scale, 0.f, N, 0, sc, stream);
                 if (rc) return rc;
-                hipLaunchKernelGGL(infonce_combine_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, part, N, Np / 256, cnt,
-                                   lse + (size_t)slot * Np, contrib + (size_t)slot * Np);
+                if (sc)
+                    hipLaunchKernelGGL(infonce_combine_ts_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, part, N, Np / 256, cnt,
+                                       lse + (size_t)slot * Np, contrib + (size_t)slot * Np, sc, tcontrib + (size_t)slot * Np);
+                else
+                    hipLaunchKernelGGL(infonce_combine_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, part, N, Np / 256, cnt,
+                                       lse + (size_t)slot * Np, contrib + (size_t)slot * Np);
                 continue;
             }
             for (int r0 = 0; r0 < N; r0 += L.slab) {
@@ -450,19 +585,28 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
                 int rc = bsclip_gemm_bf16(PA + a * opA + (size_t)r0 * 3 * D, 3 * D, PB + b * opA, 3 * D, G, Np, nr, Np,
                                           3 * D, BSCLIP_EPI_F32, nullptr, stream);
                 if (rc) return rc;
-                hipLaunchKernelGGL(loss_row_reduce_kernel, dim3(ceil_div(nr, 4)), dim3(256), 0, s, G, r0, nr, N, Np, scale,
-                                   labels, cnt, lse + (size_t)slot * Np, contrib + (size_t)slot * Np);
+                if (sc)
+                    hipLaunchKernelGGL(loss_row_reduce_ts_kernel, dim3(ceil_div(nr, 4)), dim3(256), 0, s, G, r0, nr, N, Np, sc,
+                                       labels, cnt, lse + (size_t)slot * Np, contrib + (size_t)slot * Np,
+                                       tcontrib + (size_t)slot * Np);
+                else
+                    hipLaunchKernelGGL(loss_row_reduce_kernel, dim3(ceil_div(nr, 4)), dim3(256), 0, s, G, r0, nr, N, Np, scale,
+                                       labels, cnt, lse + (size_t)slot * Np, contrib + (size_t)slot * Np);
             }
         }
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, contrib, nmod, Np, N, 1.0f / ((float)ndir * (float)N),
-                       loss_out);
+    if (sc)
+        hipLaunchKernelGGL(loss_final_ts_kernel, dim3(1), dim3(256), 0, s, contrib, tcontrib, nmod, Np, N, row0, n_own,
+                           1.0f / ((float)ndir * (float)N), log_scale_dev, sc, loss_out);
+    else
+        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, contrib, nmod, Np, N, 1.0f / ((float)ndir * (float)N),
+                           loss_out);
     BSCLIP_LAUNCH_CHECK();
     if (!dz || n_local == 0) return BSCLIP_OK;
 
     // ---- pass 2: d loss / d zn_a[rows row0 .. row0+n_local) = sum_b W_ab zn_b ----
     const float coef = scale / ((float)ndir * (float)N);
     for (int a = 0; a < nmod; ++a) {
-        BSCLIP_REQUIRE(dz[a], "bsclip_infonce_fwd_bwd: dz[%d] is null", a);
+        BSCLIP_REQUIRE(dz[a], "%s: dz[%d] is null", fn, a);
         float* da = dacc + (size_t)a * Np * D;
         bool first = true;
         for (int b = 0; b < nmod; ++b) {
@@ -473,7 +617,8 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
                 if (fused) {
                     rc = bsclip_gemm_infonce(1, PA + a * opA + (size_t)(row0 + l0) * 3 * D, 3 * D, PB + b * opA, 3 * D, W, 3 * Np,
                                              nr, Np, 3 * D, labels, cnt, lse + (size_t)(a * nmod + b) * Np,
-                                             lse + (size_t)(b * nmod + a) * Np, nullptr, scale, coef, N, row0 + l0, stream);
+                                             lse + (size_t)(b * nmod + a) * Np, nullptr, scale, sc ? den : coef, N, row0 + l0, sc,
+                                             stream);
                     if (rc) return rc;
                 } else {
                     rc = bsclip_gemm_bf16(PA + a * opA + (size_t)(row0 + l0) * 3 * D, 3 * D, PB + b * opA, 3 * D, G, Np, nr, Np,
@@ -482,9 +627,13 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
                     long tot = (long)nr * Np;
                     long blocks = (tot + 255) / 256;
                     if (blocks > 4096) blocks = 4096;
-                    hipLaunchKernelGGL(loss_w_kernel, dim3((unsigned)blocks), dim3(256), 0, s, G, N, Np, row0 + l0, nr, scale,
-                                       coef, labels, cnt, lse + (size_t)(a * nmod + b) * Np, lse + (size_t)(b * nmod + a) * Np,
-                                       W);
+                    if (sc)
+                        hipLaunchKernelGGL(loss_w_ts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, G, N, Np, row0 + l0, nr, sc, den,
+                                           labels, cnt, lse + (size_t)(a * nmod + b) * Np, lse + (size_t)(b * nmod + a) * Np, W);
+                    else
+                        hipLaunchKernelGGL(loss_w_kernel, dim3((unsigned)blocks), dim3(256), 0, s, G, N, Np, row0 + l0, nr, scale,
+                                           coef, labels, cnt, lse + (size_t)(a * nmod + b) * Np,
+                                           lse + (size_t)(b * nmod + a) * Np, W);
                 }
                 float* dar = da + (size_t)l0 * D;
                 bsclip_epi_args ea{};
@@ -504,6 +653,32 @@ extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int
     }
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
+}
+
+extern "C" int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, float scale,
+                                      int row0, int n_local, float* loss_out, float* const* dz, float* workspace,
+                                      void* stream) {
+    return infonce_run("bsclip_infonce_fwd_bwd", z, nmod, labels, N, D, scale, nullptr, nullptr, row0, n_local, loss_out, dz, workspace,
+                       stream);
+}
+
+// Trainable temperature: the scale is exp(clamp(*log_scale_dev, 0, ln 100)), read on the device when the kernels run (bsclip.h).
+extern "C" int bsclip_infonce_fwd_bwd_ts(const float* const* z, int nmod, const int64_t* labels, int N, int D,
+                                         const float* log_scale_dev, int row0, int n_local, float* loss_out, float* const* dz,
+                                         float* scale_out, float* workspace, void* stream) {
+    // everything is checked before the first launch (infonce_run checks the rest ahead of its own)
+    BSCLIP_REQUIRE(nmod >= 2 && nmod <= 3, "bsclip_infonce_fwd_bwd_ts: nmod=%d: Too less element for calculating the contrastive loss.",
+                   nmod);
+    BSCLIP_REQUIRE(log_scale_dev, "bsclip_infonce_fwd_bwd_ts: log_scale_dev is null");
+    BSCLIP_REQUIRE(scale_out, "bsclip_infonce_fwd_bwd_ts: scale_out is null");
+    BSCLIP_REQUIRE(aligned_to(4, log_scale_dev, scale_out), "bsclip_infonce_fwd_bwd_ts: log_scale_dev / scale_out must be 4-B aligned");
+    BSCLIP_REQUIRE(z, "bsclip_infonce_fwd_bwd_ts: null pointer");
+    for (int m = 0; m < nmod; ++m) {
+        BSCLIP_REQUIRE(z[m], "bsclip_infonce_fwd_bwd_ts: z[%d] is null", m);
+        BSCLIP_REQUIRE(!dz || n_local <= 0 || dz[m], "bsclip_infonce_fwd_bwd_ts: dz[%d] is null", m);
+    }
+    return infonce_run("bsclip_infonce_fwd_bwd_ts", z, nmod, labels, N, D, 0.f, log_scale_dev, scale_out, row0, n_local, loss_out, dz,
+                       workspace, stream);
 }
 
 extern "C" int bsclip_infonce_set_impl(int impl) {

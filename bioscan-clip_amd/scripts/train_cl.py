@@ -35,7 +35,7 @@ from bioscanclip.epoch.train_epoch import train_epoch  # noqa: E402
 from bioscanclip.hip import dist as hdist  # noqa: E402
 from bioscanclip.hip.optim import FusedAdamW  # noqa: E402
 from bioscanclip.model.loss_func import ContrastiveLoss, GlobalBatchContrastiveLoss  # noqa: E402
-from bioscanclip.model.simple_clip import load_clip_model  # noqa: E402
+from bioscanclip.model.simple_clip import load_clip_model, trainable_temperature  # noqa: E402
 from bioscanclip.util.config import load_config  # noqa: E402
 from bioscanclip.util.synthetic import SyntheticCLIPLoader, SyntheticEvalLoader, SyntheticRawLoader  # noqa: E402
 
@@ -224,10 +224,12 @@ def main_process(rank: int, world_size: int, args):
 
     if mc.for_open_clip:
         raise NotImplementedError("the open_clip branch is not part of the HIP-accelerated path")
+    # model_config.trainable_temperature: the criterion reads the model's learnable log scale on the device
+    logit_scale = model.logit_scale if trainable_temperature(args) else 1 / 0.07
     if world_size > 1:
-        criterion = GlobalBatchContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=1 / 0.07)
+        criterion = GlobalBatchContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale)
     else:
-        criterion = ContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=1 / 0.07)
+        criterion = ContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale)
 
     print_when_rank_zero("training...", rank)
     folder_path = None
@@ -294,6 +296,9 @@ def main(argv=None):
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     print_when_rank_zero(f'world_size: {world_size}', rank)
+    if trainable_temperature(args) and world_size > 1:   # GlobalBatchContrastiveLoss would refuse it after the model was built
+        raise ValueError(f"model_config.trainable_temperature: a trainable temperature is not built for more than one rank "
+                         f"(world_size={world_size})")
     return main_process(rank, world_size, args)
 
 

@@ -383,6 +383,21 @@ int bsclip_infonce_set_impl(int impl);
 int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, float scale,
                            int row0, int n_local, float* loss_out, float* const* dz, float* workspace,
                            void* stream);
+/* Trainable temperature: bsclip_infonce_fwd_bwd with the scale in device memory as its logarithm.
+ * log_scale_dev: one f32 t on the device, read when the kernels run and not at launch, so a replayed graph sees each step's value.
+ * The scale used is s = exp(min(max(t, 0), ln 100)) (open_clip's clamp range; exactly 1 and 100 at and beyond the ends).
+ * loss_out and dz are those of bsclip_infonce_fwd_bwd at that s, bit for bit: same layouts, same row0 / n_local meaning, the
+ * same three forms chosen by the same rules, bsclip_infonce_set_impl honoured, the same workspace size.
+ * scale_out f32 [2], required; it is also written early and read by the kernels of the call, so it must not alias anything else:
+ *   scale_out[1] = s;
+ *   scale_out[0] = the rank's share of dLoss/dt = s/(P N) * sum_{a != b} sum_{i in [row0, row0 + n_local)} sum_j
+ *                  (cnt_i p^{ab}_ij - T_ij) G^{ab}_ij   (P = nmod (nmod - 1), G the cosines, p = softmax_j(s G), T_ij = [label_i ==
+ *                  label_j], cnt_i = sum_j T_ij).  The shares of disjoint row slices add up to dLoss/dt, which is what a SUM
+ *                  all-reduce needs.  0 when dz is NULL or n_local == 0, and 0 when t lies outside [0, ln 100] (the clamp's derivative).
+ * No atomics: a repeated call returns the same bits.  All arguments are checked before the first launch; -1 names the bad one. */
+int bsclip_infonce_fwd_bwd_ts(const float* const* z, int nmod, const int64_t* labels, int N, int D, const float* log_scale_dev,
+                              int row0, int n_local, float* loss_out, float* const* dz, float* scale_out, float* workspace,
+                              void* stream);
 
 /* ---- retrieval --------------------------------------------------------------------------------
  * make_prediction (scripts/inference_and_eval.py:414-445): faiss IndexFlatIP over L2-normalised keys f32 [K, D], searched
