@@ -15,6 +15,10 @@ never waits for the step it has just enqueued: what ``bench.py`` measures is wha
 shape differs from the captured one (a last, smaller batch) is enqueued eagerly.  ``BSCLIP_GRAPH=0`` forces the eager loop.  With
 more than one rank the step is a set of per-tower captured graphs (forward_k | loss | backward_k | AdamW) with each tower's
 all-gather and all-reduce issued eagerly from that tower's stream between them (``GraphedDistStep``).
+
+Gradient clipping / skipping (``FusedAdamW.set_grad_clip``) lives inside ``optimizer.step()`` on the device: the loop
+never learns whether a step was skipped, so ``scheduler.step()`` advances on a skipped step too (as it does beside
+``torch.cuda.amp.GradScaler``), and the epoch line reports the norm statistics from one ``grad_stats(reset=True)`` read-back.
 """
 import os
 import time
@@ -141,8 +145,12 @@ def train_epoch(activate_wandb, total_epochs, epoch, dataloader, model, optimize
         report(pending[0], value, pending[1])
 
     mean_loss = running / max(n_steps, 1)
+    line = f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}"
     if torch.is_tensor(getattr(criterion, "logit_scale", None)):   # learnable temperature: one read-back per epoch
-        print(f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}, logit scale: {criterion.current_scale().item():.6f}")
-    else:
-        print(f"Epoch [{epoch}/{total_epochs}], Loss: {mean_loss}")
+        line += f", logit scale: {criterion.current_scale().item():.6f}"
+    if getattr(optimizer, "grad_clip_enabled", lambda: False)():    # FusedAdamW's norm record: one read-back per epoch, then reset
+        gs = optimizer.grad_stats(reset=True)
+        line += (f", grad norm: mean {gs['norm_mean']:.6g} max {gs['norm_max']:.6g}, clipped {gs['clipped']}/{gs['steps']}, "
+                 f"skipped {gs['skipped']}/{gs['steps']}")
+    print(line)
     return mean_loss

@@ -151,6 +151,11 @@ SIGNATURES = {
     "bsclip_gemm_splitk_f32": (I, [P, I, P, I, P, I, I, I, I, I, P, P]),
     "bsclip_adamw_step": (I, [P, P, P, P, L, F, F, F, F, F, I, F, P]),
     "bsclip_adamw_step_dev": (I, [P, P, P, P, L, P, F, F, F, F, F, P]),
+    "bsclip_grad_norm_partials": (L, [L]),
+    "bsclip_grad_sumsq_partial": (I, [P, L, P, P]),
+    "bsclip_grad_clip_finish": (I, [P, L, F, P, P]),
+    "bsclip_counter_add_if": (I, [P, U, P, P]),
+    "bsclip_adamw_step_clip": (I, [P, P, P, P, L, P, P, F, F, F, F, P]),
     "bsclip_set_dropout_step": (I, [P]),
     "bsclip_counter_add": (I, [P, U, P]),
     "bsclip_count_nonfinite": (I, [P, L, I, P, P]),

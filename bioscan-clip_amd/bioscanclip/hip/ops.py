@@ -1094,6 +1094,58 @@ def adamw_step_dev(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scal
                                           float(eps), float(weight_decay), float(grad_scale), _stream()))
 
 
+GRAD_CLIP_STATE_WORDS = 12   # the device record of grad_clip_finish (include/bsclip.h): int32 [12], 16-byte aligned
+
+
+def grad_norm_partials(n):
+    """How many f64 partial sums ``grad_sumsq_partial`` writes for a buffer of ``n`` floats (a pure function of ``n``)."""
+    count = int(_l.load().bsclip_grad_norm_partials(int(n)))
+    if count < 1:
+        raise ValueError(f"grad_norm_partials: n={n} must be positive")
+    return count
+
+
+def _grad_clip_state_ok(state, name):
+    _req(state.is_cuda and state.element_size() == 4 and state.is_contiguous() and state.numel() >= GRAD_CLIP_STATE_WORDS,
+         f"{name}: state must be a contiguous device record of {GRAD_CLIP_STATE_WORDS} 4-byte words")
+
+
+def grad_sumsq_partial(g, partial):
+    """partial[b] = sum of g[i]^2 over workgroup b's elements, in f64; ``partial`` is exactly ``grad_norm_partials(g.numel())`` long."""
+    _req(g.dtype == F32 and g.is_cuda and g.is_contiguous() and g.numel() > 0, "grad_sumsq_partial: contiguous f32 GPU buffer")
+    _req(partial.dtype == torch.float64 and partial.is_cuda and partial.is_contiguous() and partial.device == g.device
+         and partial.numel() == grad_norm_partials(g.numel()), "grad_sumsq_partial: partial must be f64 [grad_norm_partials(n)]")
+    check(_l.load().bsclip_grad_sumsq_partial(_p(g), g.numel(), _p(partial), _stream()))
+
+
+def grad_clip_finish(partial, max_norm, state):
+    """All partials summed in index order -> (apply, coef, norm, counters) in the device record ``state``; ``max_norm`` > 0, +inf for
+    monitoring and skipping without clipping."""
+    _req(partial.dtype == torch.float64 and partial.is_cuda and partial.is_contiguous() and partial.numel() > 0,
+         "grad_clip_finish: partial must be a contiguous f64 GPU buffer")
+    _grad_clip_state_ok(state, "grad_clip_finish")
+    _req(float(max_norm) > 0.0, f"grad_clip_finish: max_norm={max_norm} must be positive")
+    check(_l.load().bsclip_grad_clip_finish(_p(partial), partial.numel(), float(max_norm), _p(state), _stream()))
+
+
+def counter_add_if(counter, inc, cond):
+    """counter += inc when the device word ``cond`` is not zero."""
+    _req(counter.is_cuda and counter.numel() >= 1 and counter.element_size() == 4, "counter: 4-byte device word")
+    _req(cond.is_cuda and cond.numel() >= 1 and cond.element_size() == 4, "cond: 4-byte device word")
+    check(_l.load().bsclip_counter_add_if(_p(counter), int(inc) & 0xFFFFFFFF, _p(cond), _stream()))
+
+
+def adamw_step_clip(p, g, m, v, hyper, state, beta1, beta2, eps, weight_decay):
+    """``adamw_step_dev`` on ``g * coef`` with ``coef`` read from ``state`` (``grad_clip_finish``); nothing is written when the record
+    says skip."""
+    _req(all(t.dtype == F32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v)), "adamw: flat f32 buffers")
+    _req(hyper.element_size() == 4 and hyper.is_cuda and hyper.is_contiguous() and hyper.numel() >= 2,
+         "adamw: hyper must be a device pair of 4-byte words (lr f32, step uint32)")
+    _grad_clip_state_ok(state, "adamw_step_clip")
+    check(_l.load().bsclip_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), float(beta1), float(beta2),
+                                           float(eps), float(weight_decay), _stream()))
+
+
 def set_dropout_step(counter):
     """Every dropout-carrying launch this thread makes from now on mixes the device word ``counter`` (uint32/int32 [1]) into
     its seed at run time (None: seeds are used as passed)."""

@@ -9,15 +9,71 @@ from . import ops
 class FusedAdamW(torch.optim.Optimizer):
     """Drop-in for ``torch.optim.AdamW``: same constructor, ``param_groups[0]['lr']`` honoured every step (so
     torch LR schedulers work).  Parameters that live in an engine ``FlatParams`` buffer are updated with one
-    ``bsclip_adamw_step`` launch per buffer; any other trainable tensor gets its own launch of the same kernel."""
+    ``bsclip_adamw_step`` launch per buffer; any other trainable tensor gets its own launch of the same kernel.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    ``max_grad_norm`` / ``skip_nonfinite`` (``set_grad_clip``), both off by default: the global L2 norm of all flat
+    gradients is formed on the device, the update runs on ``g * min(1, max_grad_norm / (norm + 1e-6))``
+    (``torch.nn.utils.clip_grad_norm_``) and a step whose norm is not finite changes nothing -- parameters, moments and the step
+    count stay (``GradScaler.step``).  No host read-back: eager and captured steps issue the same launches."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._flat_state = {}
         self._flats = []
         self._dev_hyper = False
         self._shard = None        # (rank, world, group): optimizer-state sharding over the ranks (shard_state)
+        self._clip_on = False
+        self._max_norm = float("inf")
+        self._clip_state = None       # int32 [12]: the device record of bsclip_grad_clip_finish
+        self._clip_partials = None    # f64: every flat buffer's partial sums, one slice behind the other
+        self.set_grad_clip(max_grad_norm, skip_nonfinite)
+
+    def set_grad_clip(self, max_grad_norm, skip_nonfinite=True):
+        """``max_grad_norm``: clip the global gradient norm to it (None or +inf: no clipping).  ``skip_nonfinite``: leave parameters,
+        moments and the step count untouched when the norm is Inf / NaN, and keep the statistics of ``grad_stats()``.  Clipping needs
+        the skip: a non-finite norm cannot be clipped.  ``(None, False)`` is the plain optimizer.  The norm bound is a launch argument:
+        set it before the step is captured."""
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"FusedAdamW: max_grad_norm={max_grad_norm} must be positive (None: no clipping)")
+            if not skip_nonfinite:
+                raise ValueError("FusedAdamW: max_grad_norm needs skip_nonfinite=True (a non-finite gradient norm cannot be clipped)")
+        if self._clip_on and not skip_nonfinite:
+            self._refresh_steps_from_device()     # the host-side counts take over again
+        self._clip_on = bool(skip_nonfinite)
+        self._max_norm = float("inf") if max_grad_norm is None else max_grad_norm
+        return self
+
+    def grad_clip_enabled(self):
+        return self._clip_on
+
+    def _refresh_steps_from_device(self):
+        """With the feature on the device step word counts APPLIED steps and the host's ``st["step"]`` attempted ones: bring the host
+        count back to the device's (one read-back per flat buffer)."""
+        if not self._clip_on:
+            return
+        for st in self._flat_state.values():
+            if "hyper" in st:
+                st["step"] = int(st["hyper"][1].item())
+
+    def grad_stats(self, reset=False):
+        """The gradient-norm record since the last reset, read back with one synchronisation: steps seen / skipped (non-finite norm) /
+        clipped, mean and maximum of the finite norms, and the last step's norm and coefficient.  ``reset=True`` zeroes the counters
+        and the sums behind the read (a stream-ordered fill)."""
+        out = {"steps": 0, "skipped": 0, "clipped": 0, "norm_mean": 0.0, "norm_max": 0.0, "norm_last": 0.0, "coef_last": 1.0}
+        if self._clip_state is None:
+            return out
+        w = self._clip_state.cpu().numpy()
+        steps, skipped, clipped = (int(x) for x in w[4:7].view("uint32"))
+        total, largest = (float(x) for x in w[8:12].view("float64"))
+        applied = steps - skipped
+        out.update(steps=steps, skipped=skipped, clipped=clipped, norm_mean=total / applied if applied else 0.0, norm_max=largest,
+                   norm_last=float(w[2:3].view("float32")[0]), coef_last=float(w[1:2].view("float32")[0]))
+        if reset:
+            self._clip_state[4:].zero_()
+        return out
 
     def shard_state(self, group=None):
         """Multi-rank full fine-tuning (every rank would otherwise hold the full 2 x 4 B per parameter of AdamW
@@ -99,6 +155,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["step"] += 1
         self.stage_hyper()
 
+    def _true_step(self, st):
+        """The step count of one flat buffer's state: the host's, or with skipping on the device word (applied steps only)."""
+        if self._clip_on and "hyper" in st:
+            return int(st["hyper"][1].item())
+        return st["step"]
+
     def _state_for(self, f):
         """Adam moments of one flat buffer.  Keyed by the PARAMETERS it holds (they outlive an engine rebuild: a checkpoint
         loaded mid-run, a precision switch), not by the buffer object; every parameter's slice is also published in
@@ -115,7 +177,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if prev is not None:                  # engine rebuilt (checkpoint loaded mid-run): the optimisation continues
                     st["m"].copy_(prev["m"])
                     st["v"].copy_(prev["v"])
-                    st["step"] = prev["step"]
+                    st["step"] = self._true_step(prev)
                 self._flat_state = {k: v for k, v in self._flat_state.items() if v.get("key") != key}
                 self._flat_state[id(f)] = st
             return st
@@ -125,7 +187,7 @@ class FusedAdamW(torch.optim.Optimizer):
             if prev is not None:                      # engine rebuilt: the optimisation continues, it does not restart
                 st["m"].copy_(prev["m"])
                 st["v"].copy_(prev["v"])
-                st["step"] = prev["step"]
+                st["step"] = self._true_step(prev)
             else:                                     # moments restored by load_state_dict() before the buffer existed
                 for p, o in zip(f.params, f.offsets):
                     ps = self.state.get(p)
@@ -144,6 +206,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._shard is not None:
             raise NotImplementedError("FusedAdamW: the moments are sharded over the ranks (shard_state); the reference checkpoints "
                                       "the model only (train_cl.py:219-220)")
+        self._refresh_steps_from_device()             # skipped steps do not count (the device word is the true count)
         for f in self._flats:                         # the per-parameter step counts follow the flat buffer's
             st = self._flat_state.get(id(f))
             if st is not None:
@@ -181,9 +244,68 @@ class FusedAdamW(torch.optim.Optimizer):
                 else:
                     p.grad.zero_()
 
+    def _step_clipped(self):
+        """The step with the norm / clip / skip feature on.  Launches, eager and captured alike: one ``grad_sumsq_partial`` per flat
+        buffer (over the WHOLE gradient, also when the update is sharded), one ``grad_clip_finish``, then per buffer
+        ``counter_add_if`` on its step word and ``adamw_step_clip``.  The step word is filled once, when the ``hyper`` pair is
+        created, and from then on only advanced on the device: it counts applied steps, ``st["step"]`` attempted ones."""
+        in_opt = {id(p): g for g in self.param_groups for p in g["params"]}
+        flats = [f for f in self._flats if f.valid() and all(id(p) in in_opt for p in f.params)]
+        capturing = bool(flats) and flats[0].grad.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        handled = {id(p) for f in flats for p in f.params}
+        for group in self.param_groups:
+            for p in group["params"]:
+                if id(p) not in handled and p.grad is not None:
+                    raise RuntimeError("FusedAdamW: gradient clipping / skipping needs every trainable tensor in an engine's flat "
+                                       "buffer (the norm is formed over the flat gradient buffers)")
+        if not flats:
+            return
+        counts = [ops.grad_norm_partials(f.grad.numel()) for f in flats]
+        total = sum(counts)
+        dev = flats[0].grad.device
+        if self._clip_state is None or self._clip_state.device != dev or self._clip_partials.numel() < total:
+            if capturing:                             # a captured graph would hold a buffer of its private pool
+                raise RuntimeError("FusedAdamW: run one eager step with gradient clipping / skipping on before capturing (its "
+                                   "device buffers are allocated there)")
+            if self._clip_state is None or self._clip_state.device != dev:
+                self._clip_state = torch.zeros(ops.GRAD_CLIP_STATE_WORDS, dtype=torch.int32, device=dev)
+            self._clip_partials = torch.empty(total, dtype=torch.float64, device=dev)
+        state, off = self._clip_state, 0
+        for f, c in zip(flats, counts):
+            f.bind_grads()
+            ops.grad_sumsq_partial(f.grad, self._clip_partials[off:off + c])
+            off += c
+        ops.grad_clip_finish(self._clip_partials[:total], self._max_norm, state)
+        for f in flats:
+            g = in_opt[id(f.params[0])]
+            st = self._state_for(f)
+            if "hyper" not in st:
+                if capturing:
+                    raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing")
+                st["hyper"] = torch.zeros(2, dtype=torch.int32, device=f.data.device)   # [lr as f32 bits, step as uint32]
+                st["hyper"][1:2].fill_(st["step"])
+            st["step"] += 1
+            lo, hi = self._slice_of(f)
+            if hi <= lo:
+                continue
+            fdata, fgrad = (f.data, f.grad) if self._shard is None else (f.data[lo:hi], f.grad[lo:hi])
+            if not capturing:
+                lr = float(g["lr"])
+                if st.get("lr_staged") != lr:
+                    st["hyper"].view(torch.float32)[0:1].fill_(lr)
+                    st["lr_staged"] = lr
+            ops.counter_add_if(st["hyper"][1:2], 1, state[0:1])
+            ops.adamw_step_clip(fdata, fgrad, st["m"], st["v"], st["hyper"], state, g["betas"][0], g["betas"][1], g["eps"],
+                                g["weight_decay"])
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._clip_on:
+            self._step_clipped()
+            if self._shard is not None and not torch.cuda.is_current_stream_capturing():
+                self.sync_updated_slices()
+            return loss
         handled = set()
         in_opt = {id(p): g for g in self.param_groups for p in g["params"]}
         for f in self._flats:

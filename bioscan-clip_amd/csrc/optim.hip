@@ -763,3 +763,176 @@ extern "C" int bsclip_adamw_step_dev(float* p, const float* g, float* m, float* 
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }
+
+// ---- global gradient norm, clipping and overflow-safe steps ----------------------------------------------------------
+// grad_sumsq : per-workgroup f64 sums of g^2 over one flat gradient buffer (one HBM pass, fixed order, no atomics)
+// grad_clip_finish : one workgroup sums every buffer's partials in index order and leaves (apply, coef, norm, counters) in a device
+//               record -- torch.nn.utils.clip_grad_norm_'s coefficient, GradScaler's "skip the step when the gradient is not finite"
+// counter_add_if / adamw_clip : the step word and the update, both conditional on the record's `apply`
+namespace {
+
+constexpr int GN_BLOCK = 256;
+constexpr long GN_SPAN = 8192;        // elements a workgroup owns at least: two rounds of four 16-byte loads per thread
+constexpr long GN_MAX_PARTIALS = 1024;   // four workgroups per CU; beyond GN_SPAN * GN_MAX_PARTIALS elements the spans grow
+constexpr int GC_TILE = 1024;         // partials staged through LDS per round of grad_clip_finish_kernel
+
+__device__ __forceinline__ double sumsq4(f32x4 v) {   // the square of an f32 is exact in f64
+    const double a = (double)v[0], b = (double)v[1], c = (double)v[2], d = (double)v[3];
+    return (a * a + b * b) + (c * c + d * d);
+}
+
+// Workgroup b owns the 16-byte vectors [b * chunk, (b + 1) * chunk) of g (chunk = ceil((n / 4) / gridDim.x)); the last workgroup also
+// owns the n % 4 tail elements.  Thread t takes vectors t, t + 256, ... of the chunk, four loads in flight; the 256 sums are combined
+// in a fixed order: the lanes of a wave by xor-shuffles, the four waves in wave order through LDS.
+__global__ __launch_bounds__(GN_BLOCK) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ partial) {
+    __shared__ double red[GN_BLOCK / 64];
+    const long nvec = n >> 2;
+    const long chunk = (nvec + gridDim.x - 1) / gridDim.x;
+    const long lo = min((long)blockIdx.x * chunk, nvec), hi = min(lo + chunk, nvec);
+    const f32x4* src = reinterpret_cast<const f32x4*>(g);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    long i = lo + threadIdx.x;
+    for (; i + 3 * GN_BLOCK < hi; i += 4 * GN_BLOCK) {
+        const f32x4 v0 = src[i], v1 = src[i + GN_BLOCK], v2 = src[i + 2 * GN_BLOCK], v3 = src[i + 3 * GN_BLOCK];
+        s0 += sumsq4(v0);
+        s1 += sumsq4(v1);
+        s2 += sumsq4(v2);
+        s3 += sumsq4(v3);
+    }
+    for (; i < hi; i += GN_BLOCK) s0 += sumsq4(src[i]);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (n & 3)) {
+        const double t = (double)g[(nvec << 2) + threadIdx.x];
+        s1 += t * t;
+    }
+    double s = (s0 + s1) + (s2 + s3);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// state: twelve 4-byte words (include/bsclip.h).  The partials are staged through LDS a tile at a time and summed by ONE thread in
+// index order: a few thousand dependent f64 adds at the most (three buffers at the cap), microseconds beside the pass that made them.
+__global__ __launch_bounds__(GN_BLOCK) void grad_clip_finish_kernel(const double* __restrict__ partial, long n_partial, float max_norm,
+                                                                     unsigned* __restrict__ state) {
+    __shared__ double tile[GC_TILE];
+    double total = 0.0;
+    for (long base = 0; base < n_partial; base += GC_TILE) {
+        const int cnt = (int)min((long)GC_TILE, n_partial - base);
+        for (int k = threadIdx.x; k < cnt; k += GN_BLOCK) tile[k] = partial[base + k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < cnt; ++k) total += tile[k];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const bool finite = isfinite(total);
+    const double root = sqrt(total);
+    const float norm = (float)root;
+    const float coef = finite ? (float)fmin(1.0, (double)max_norm / (root + 1e-6)) : 0.f;
+    const unsigned clipped = finite && coef < 1.f ? 1u : 0u;
+    double* sums = reinterpret_cast<double*>(state + 8);   // state is 16-byte aligned
+    state[0] = finite ? 1u : 0u;
+    state[1] = __float_as_uint(coef);
+    state[2] = __float_as_uint(norm);
+    state[3] = clipped;
+    state[4] += 1u;
+    state[5] += finite ? 0u : 1u;
+    state[6] += clipped;
+    state[7] = 0u;
+    if (finite) {
+        sums[0] += (double)norm;
+        sums[1] = fmax(sums[1], (double)norm);
+    }
+}
+
+__global__ void counter_add_if_kernel(unsigned* p, unsigned inc, const unsigned* cond) {
+    if (*cond != 0u) *p += inc;
+}
+
+// adamw_dev_kernel, operation for operation, with the gradient multiplied by the record's coef and nothing stored when the record
+// says skip (state[0] == 0: the gradient was not finite)
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, long n,
+                                                          const float* __restrict__ hyper, const unsigned* __restrict__ state,
+                                                          float beta1, float beta2, float eps, float wd) {
+    if (state[0] == 0u) return;
+    const float grad_scale = __uint_as_float(state[1]);
+    const float lr = hyper[0];
+    const double step = (double)reinterpret_cast<const unsigned*>(hyper)[1];
+    const float inv_bc1 = (float)(1.0 / (1.0 - pow((double)beta1, step)));
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, step)));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float gi = g[i] * grad_scale;
+        float pi = p[i] * (1.0f - lr * wd);
+        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
+        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+        pi -= (lr * inv_bc1) * (mi / denom);
+        p[i] = pi;
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t bsclip_grad_norm_partials(int64_t n) {
+    if (n <= 0) {
+        bsclip_set_error("bsclip_grad_norm_partials: n=%ld must be positive", (long)n);
+        return -1;
+    }
+    const int64_t blocks = (n + GN_SPAN - 1) / GN_SPAN;
+    return blocks > GN_MAX_PARTIALS ? GN_MAX_PARTIALS : blocks;
+}
+
+extern "C" int bsclip_grad_sumsq_partial(const float* g, int64_t n, double* partial, void* stream) {
+    BSCLIP_REQUIRE(g, "bsclip_grad_sumsq_partial: g is null");
+    BSCLIP_REQUIRE(partial, "bsclip_grad_sumsq_partial: partial is null");
+    BSCLIP_REQUIRE(n > 0, "bsclip_grad_sumsq_partial: n=%ld must be positive", (long)n);
+    BSCLIP_REQUIRE(aligned_to(16, g), "bsclip_grad_sumsq_partial: g must be 16-byte aligned (vector loads)");
+    BSCLIP_REQUIRE(aligned_to(8, partial), "bsclip_grad_sumsq_partial: partial must be 8-byte aligned (f64)");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)bsclip_grad_norm_partials(n)), dim3(GN_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), g, (long)n, partial);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_grad_clip_finish(const double* partial, int64_t n_partial, float max_norm, void* state, void* stream) {
+    BSCLIP_REQUIRE(partial, "bsclip_grad_clip_finish: partial is null");
+    BSCLIP_REQUIRE(state, "bsclip_grad_clip_finish: state is null");
+    BSCLIP_REQUIRE(n_partial > 0, "bsclip_grad_clip_finish: n_partial=%ld must be positive", (long)n_partial);
+    BSCLIP_REQUIRE(max_norm > 0.f, "bsclip_grad_clip_finish: max_norm=%g must be positive (+inf: no clipping)", (double)max_norm);
+    BSCLIP_REQUIRE(aligned_to(8, partial), "bsclip_grad_clip_finish: partial must be 8-byte aligned (f64)");
+    BSCLIP_REQUIRE(aligned_to(16, state), "bsclip_grad_clip_finish: state must be 16-byte aligned");
+    hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(GN_BLOCK), 0, static_cast<hipStream_t>(stream), partial, (long)n_partial,
+                       max_norm, static_cast<unsigned*>(state));
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_counter_add_if(uint32_t* counter, uint32_t inc, const uint32_t* cond, void* stream) {
+    BSCLIP_REQUIRE(counter, "bsclip_counter_add_if: counter is null");
+    BSCLIP_REQUIRE(cond, "bsclip_counter_add_if: cond is null");
+    BSCLIP_REQUIRE(aligned_to(4, counter, cond), "bsclip_counter_add_if: counter and cond must be 4-byte aligned");
+    hipLaunchKernelGGL(counter_add_if_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), counter, inc, cond);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, const void* state,
+                                      float beta1, float beta2, float eps, float weight_decay, void* stream) {
+    BSCLIP_REQUIRE(p && g && m && v, "bsclip_adamw_step_clip: null pointer among p, g, m, v");
+    BSCLIP_REQUIRE(hyper_dev, "bsclip_adamw_step_clip: hyper_dev is null");
+    BSCLIP_REQUIRE(state, "bsclip_adamw_step_clip: state is null");
+    BSCLIP_REQUIRE(n > 0, "bsclip_adamw_step_clip: n=%ld must be positive", (long)n);
+    BSCLIP_REQUIRE(aligned_to(4, p, g, m, v, hyper_dev), "bsclip_adamw_step_clip: p, g, m, v and hyper_dev must be 4-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, state), "bsclip_adamw_step_clip: state must be 16-byte aligned");
+    long blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, (long)n,
+                       hyper_dev, static_cast<const unsigned*>(state), beta1, beta2, eps, weight_decay);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}

@@ -169,8 +169,29 @@ def jpeg_entropy_mode(args):
     return mode
 
 
+def grad_clip_options(args):
+    """``model_config.grad_clip_norm=<float>`` (open_clip's ``--grad-clip-norm``): clip the global gradient norm to it and skip a step
+    whose gradient is not finite.  ``model_config.skip_nonfinite_steps=true`` alone: skip such steps and report the norm, no clipping.
+    Returns ``(max_grad_norm or None, skip_nonfinite)``, ``(None, False)`` when neither key is there; a norm that is not a positive
+    number is refused here, before the model is built.  The LR scheduler advances on a skipped step too, as it does beside
+    ``torch.cuda.amp.GradScaler``."""
+    mc = getattr(args, "model_config", None)
+    raw = getattr(mc, "grad_clip_norm", None)
+    skip = bool(getattr(mc, "skip_nonfinite_steps", False))
+    if raw is None or raw == "":
+        return None, skip
+    try:
+        norm = float(raw)
+    except (TypeError, ValueError):
+        norm = float("nan")
+    if isinstance(raw, bool) or not norm > 0.0:
+        raise ValueError(f"model_config.grad_clip_norm must be a positive number, got {raw!r}")
+    return norm, True
+
+
 def main_process(rank: int, world_size: int, args):
     towers16 = fp16_towers(args)
+    max_grad_norm, skip_nonfinite = grad_clip_options(args)
     jpeg_entropy = jpeg_entropy_mode(args)
     if getattr(args, "debug_flag", False) or rank != 0:
         args.activate_wandb = False
@@ -215,7 +236,7 @@ def main_process(rank: int, world_size: int, args):
     lr = 0.001
     if hasattr(mc, 'lr_config') and hasattr(mc.lr_config, 'lr'):
         lr = mc.lr_config.lr
-    optimizer = FusedAdamW(model.parameters(), lr=lr)
+    optimizer = FusedAdamW(model.parameters(), lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     if world_size > 1 and getattr(mc, "disable_lora", False):
         # full fine-tuning on several ranks: each rank keeps the AdamW moments of one slice of every flat buffer (3.2 GB / W for
         # I+D+T instead of 3.2 GB per rank) and broadcasts its updated slice (hip/optim.py shard_state)
@@ -293,6 +314,7 @@ def main(argv=None):
     fp16_towers(args)   # refuse an unbuilt fp16 backward before any GPU work
     jpeg_entropy_mode(args)
     eval_source(args)
+    grad_clip_options(args)
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     print_when_rank_zero(f'world_size: {world_size}', rank)

@@ -740,6 +740,32 @@ int bsclip_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, f
 int bsclip_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, float beta1,
                           float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 
+/* ---- global gradient norm, clipping (torch.nn.utils.clip_grad_norm_) and overflow-safe steps (GradScaler.step), all on the device
+ * and capturable.  Per optimizer step: one bsclip_grad_sumsq_partial per flat gradient buffer into consecutive slices
+ * of one partials buffer, one bsclip_grad_clip_finish over all of them, then per buffer bsclip_counter_add_if on the step word and
+ * bsclip_adamw_step_clip.
+ * grad_norm_partials: how many partial sums grad_sumsq_partial writes for n floats: a pure function of n, >= 1, monotone, capped
+ *   (-1 for n <= 0).
+ * grad_sumsq_partial: partial[b] = sum of g[i]^2 over the elements workgroup b owns, squared and summed in f64 (the square of an f32
+ *   is exact there, and a large finite gradient stays finite), in a fixed order without atomics: a repeated call gives the same bits.
+ *   g 16-byte aligned, n arbitrary.
+ * grad_clip_finish (one workgroup): total = partial[0] + ... + partial[n_partial - 1] in index order (f64); finite = isfinite(total)
+ *   -- an Inf or NaN anywhere makes it false; norm = (float)sqrt(total); coef = finite ? (float)min(1, max_norm / (sqrt(total) + 1e-6))
+ *   : 0 (torch's clip_coef_clamped).  max_norm = +inf: coef is exactly 1 (monitoring and skipping only); max_norm <= 0 or NaN is
+ *   refused.  state: caller-owned, 16-byte aligned, twelve 4-byte words, zeroed once by the caller:
+ *     0 apply (uint32: 1 = finite, 0 = skip)   1 coef (f32)   2 norm (f32; the non-finite value itself when skipped)
+ *     3 clipped this step (uint32: finite and coef < 1)   4 steps seen   5 steps skipped   6 steps clipped (uint32, running)   7 zero
+ *     8-9 f64 running sum of the finite steps' norms   10-11 f64 largest finite norm
+ * counter_add_if: *counter += inc when *cond != 0 (bsclip_counter_add's conditional form: AdamW's step word counts applied steps).
+ * adamw_step_clip: bsclip_adamw_step_dev's arithmetic with the gradient multiplied by state's coef; returns without a store when
+ *   state's apply is 0.  With coef == 1 it leaves the bits bsclip_adamw_step_dev(..., grad_scale = 1) leaves. */
+int64_t bsclip_grad_norm_partials(int64_t n);
+int bsclip_grad_sumsq_partial(const float* g, int64_t n, double* partial, void* stream);
+int bsclip_grad_clip_finish(const double* partial, int64_t n_partial, float max_norm, void* state, void* stream);
+int bsclip_counter_add_if(uint32_t* counter, uint32_t inc, const uint32_t* cond, void* stream);
+int bsclip_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, const void* state,
+                           float beta1, float beta2, float eps, float weight_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
