@@ -1078,8 +1078,17 @@ def waug_set_lora_layers(table, layers, ld_w, H, dtype=BF16):
     check(_l.load().bsclip_waug_set_lora_layers(_p(table), int(layers) | fmt, int(ld_w), int(H), _stream()))
 
 
-def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+def _adamw_flat_ok(p, g, m, v):
     _req(all(t.dtype == F32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v)), "adamw: flat f32 buffers")
+
+
+def _adamw_hyper_ok(hyper):
+    _req(hyper.element_size() == 4 and hyper.is_cuda and hyper.is_contiguous() and hyper.numel() >= 2,
+         "adamw: hyper must be a device pair of 4-byte words (lr f32, step uint32)")
+
+
+def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    _adamw_flat_ok(p, g, m, v)
     check(_l.load().bsclip_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
                                       float(eps), float(weight_decay), int(step), float(grad_scale), _stream()))
 
@@ -1087,9 +1096,8 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
 def adamw_step_dev(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scale=1.0):
     """AdamW with (lr, step) read from the device pair ``hyper`` = [lr as f32, step as uint32] when the kernel runs:
     graph-capturable (advance the step word with ``counter_add(hyper[1:2])``)."""
-    _req(all(t.dtype == F32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v)), "adamw: flat f32 buffers")
-    _req(hyper.element_size() == 4 and hyper.is_cuda and hyper.is_contiguous() and hyper.numel() >= 2,
-         "adamw: hyper must be a device pair of 4-byte words (lr f32, step uint32)")
+    _adamw_flat_ok(p, g, m, v)
+    _adamw_hyper_ok(hyper)
     check(_l.load().bsclip_adamw_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), float(beta1), float(beta2),
                                           float(eps), float(weight_decay), float(grad_scale), _stream()))
 
@@ -1138,9 +1146,8 @@ def counter_add_if(counter, inc, cond):
 def adamw_step_clip(p, g, m, v, hyper, state, beta1, beta2, eps, weight_decay):
     """``adamw_step_dev`` on ``g * coef`` with ``coef`` read from ``state`` (``grad_clip_finish``); nothing is written when the record
     says skip."""
-    _req(all(t.dtype == F32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v)), "adamw: flat f32 buffers")
-    _req(hyper.element_size() == 4 and hyper.is_cuda and hyper.is_contiguous() and hyper.numel() >= 2,
-         "adamw: hyper must be a device pair of 4-byte words (lr f32, step uint32)")
+    _adamw_flat_ok(p, g, m, v)
+    _adamw_hyper_ok(hyper)
     _grad_clip_state_ok(state, "adamw_step_clip")
     check(_l.load().bsclip_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), float(beta1), float(beta2),
                                            float(eps), float(weight_decay), _stream()))

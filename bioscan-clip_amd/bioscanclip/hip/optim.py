@@ -134,25 +134,31 @@ class FusedAdamW(torch.optim.Optimizer):
                 return g
         return self.param_groups[0]
 
+    def _stage_lr(self, st, lr):
+        """Enqueue ``lr`` into the lr word of one state's ``hyper`` pair unless it is what was staged last: a fill kernel whose value is
+        a launch argument, stream-ordered behind the previous step, nothing for the host to overwrite while it is in flight.  Always
+        issued OUTSIDE a graph (a captured fill would freeze the value): by an eager step, or before the replay that consumes it."""
+        lr = float(lr)
+        if st.get("lr_staged") != lr:
+            st["hyper"].view(torch.float32)[0:1].fill_(lr)
+            st["lr_staged"] = lr
+
+    def _hyper_states(self):
+        """(flat buffer, state) of every flat buffer that owns a device ``hyper`` pair."""
+        states = ((f, self._flat_state.get(id(f))) for f in self._flats)
+        return [(f, st) for f, st in states if st is not None and "hyper" in st]
+
     def stage_hyper(self):
-        """Enqueue the current lr of every flat buffer's own param group into its device word (a fill kernel whose value is a
-        launch argument: stream-ordered behind the previous step, nothing for the host to overwrite while it is in flight).
-        Called by ``step()`` when it is not being captured and by ``GraphedStep`` before each replay."""
-        for f in self._flats:
-            st = self._flat_state.get(id(f))
-            if st is not None and "hyper" in st:
-                lr = float(self._group_of(f)["lr"])
-                if st.get("lr_staged") != lr:
-                    st["hyper"].view(torch.float32)[0:1].fill_(lr)
-                    st["lr_staged"] = lr
+        """Stage the current lr of every flat buffer's own param group into its device word (``_stage_lr``).  Called by ``GraphedStep``
+        before each replay."""
+        for f, st in self._hyper_states():
+            self._stage_lr(st, self._group_of(f)["lr"])
 
     def advance_host_state(self):
         """Host half of one optimizer step, for a graph replay: the host's step counts follow the device words (which the
         replayed graph advances itself) and the current lr is staged."""
-        for f in self._flats:
-            st = self._flat_state.get(id(f))
-            if st is not None and "hyper" in st:
-                st["step"] += 1
+        for _, st in self._hyper_states():
+            st["step"] += 1
         self.stage_hyper()
 
     def _true_step(self, st):
@@ -162,41 +168,32 @@ class FusedAdamW(torch.optim.Optimizer):
         return st["step"]
 
     def _state_for(self, f):
-        """Adam moments of one flat buffer.  Keyed by the PARAMETERS it holds (they outlive an engine rebuild: a checkpoint
-        loaded mid-run, a precision switch), not by the buffer object; every parameter's slice is also published in
-        ``self.state[p]`` as views (``exp_avg``, ``exp_avg_sq``, ``step``) so ``state_dict()`` / ``load_state_dict()`` carry
-        the moments like torch.optim.AdamW's do."""
+        """Adam moments of this rank's slice of one flat buffer (the whole buffer when unsharded).  Keyed by the PARAMETERS the buffer
+        holds (they outlive an engine rebuild: a checkpoint loaded mid-run, a precision switch), not by the buffer object.  Unsharded,
+        every parameter's part is also published in ``self.state[p]`` as views (``exp_avg``, ``exp_avg_sq``, ``step``) so
+        ``state_dict()`` / ``load_state_dict()`` carry the moments like torch.optim.AdamW's do."""
         key = tuple(id(p) for p in f.params)
+        lo, hi = self._slice_of(f)
         st = self._flat_state.get(id(f))
-        if self._shard is not None:
-            lo, hi = self._slice_of(f)
-            if st is None or st["m"].numel() != hi - lo or st.get("key") != key:
-                prev = next((v for v in self._flat_state.values() if v.get("key") == key and v.get("slice") == (lo, hi)), None)
-                st = {"m": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device),
-                      "v": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device), "step": 0, "key": key, "slice": (lo, hi)}
-                if prev is not None:                  # engine rebuilt (checkpoint loaded mid-run): the optimisation continues
-                    st["m"].copy_(prev["m"])
-                    st["v"].copy_(prev["v"])
-                    st["step"] = self._true_step(prev)
-                self._flat_state = {k: v for k, v in self._flat_state.items() if v.get("key") != key}
-                self._flat_state[id(f)] = st
+        if st is not None and st["m"].numel() == hi - lo and st.get("key") == key:
             return st
-        if st is None or st["m"].numel() != f.data.numel() or st.get("key") != key:
-            prev = next((v for v in self._flat_state.values() if v.get("key") == key and v["m"].numel() == f.data.numel()), None)
-            st = {"m": torch.zeros_like(f.data), "v": torch.zeros_like(f.data), "step": 0, "key": key}
-            if prev is not None:                      # engine rebuilt: the optimisation continues, it does not restart
-                st["m"].copy_(prev["m"])
-                st["v"].copy_(prev["v"])
-                st["step"] = self._true_step(prev)
-            else:                                     # moments restored by load_state_dict() before the buffer existed
-                for p, o in zip(f.params, f.offsets):
-                    ps = self.state.get(p)
-                    if ps and "exp_avg" in ps and ps["exp_avg"].numel() == p.numel():
-                        st["m"][o:o + p.numel()].copy_(ps["exp_avg"].reshape(-1).to(st["m"].device))
-                        st["v"][o:o + p.numel()].copy_(ps["exp_avg_sq"].reshape(-1).to(st["v"].device))
-                        st["step"] = max(st["step"], int(ps.get("step", 0)))
-            self._flat_state = {k: v for k, v in self._flat_state.items() if v.get("key") != key}
-            self._flat_state[id(f)] = st
+        prev = next((v for v in self._flat_state.values() if v.get("key") == key and v.get("slice") == (lo, hi)), None)
+        st = {"m": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device),
+              "v": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device), "step": 0, "key": key, "slice": (lo, hi)}
+        if prev is not None:                          # engine rebuilt (checkpoint loaded mid-run): the optimisation continues, it does not restart
+            st["m"].copy_(prev["m"])
+            st["v"].copy_(prev["v"])
+            st["step"] = self._true_step(prev)
+        elif self._shard is None:                     # moments restored by load_state_dict() before the buffer existed
+            for p, o in zip(f.params, f.offsets):
+                ps = self.state.get(p)
+                if ps and "exp_avg" in ps and ps["exp_avg"].numel() == p.numel():
+                    st["m"][o:o + p.numel()].copy_(ps["exp_avg"].reshape(-1).to(st["m"].device))
+                    st["v"][o:o + p.numel()].copy_(ps["exp_avg_sq"].reshape(-1).to(st["v"].device))
+                    st["step"] = max(st["step"], int(ps.get("step", 0)))
+        self._flat_state = {k: v for k, v in self._flat_state.items() if v.get("key") != key}
+        self._flat_state[id(f)] = st
+        if self._shard is None:
             for p, o in zip(f.params, f.offsets):
                 self.state[p] = {"step": st["step"], "exp_avg": st["m"][o:o + p.numel()].view(p.shape),
                                  "exp_avg_sq": st["v"][o:o + p.numel()].view(p.shape)}
@@ -244,22 +241,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 else:
                     p.grad.zero_()
 
-    def _step_clipped(self):
-        """The step with the norm / clip / skip feature on.  Launches, eager and captured alike: one ``grad_sumsq_partial`` per flat
-        buffer (over the WHOLE gradient, also when the update is sharded), one ``grad_clip_finish``, then per buffer
-        ``counter_add_if`` on its step word and ``adamw_step_clip``.  The step word is filled once, when the ``hyper`` pair is
-        created, and from then on only advanced on the device: it counts applied steps, ``st["step"]`` attempted ones."""
-        in_opt = {id(p): g for g in self.param_groups for p in g["params"]}
-        flats = [f for f in self._flats if f.valid() and all(id(p) in in_opt for p in f.params)]
-        capturing = bool(flats) and flats[0].grad.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        handled = {id(p) for f in flats for p in f.params}
-        for group in self.param_groups:
-            for p in group["params"]:
-                if id(p) not in handled and p.grad is not None:
-                    raise RuntimeError("FusedAdamW: gradient clipping / skipping needs every trainable tensor in an engine's flat "
-                                       "buffer (the norm is formed over the flat gradient buffers)")
-        if not flats:
-            return
+    def _norm_pass(self, flats, capturing):
+        """The global gradient norm, eager and captured alike: one ``grad_sumsq_partial`` per flat buffer (over the WHOLE gradient, also
+        when the update is sharded), then one ``grad_clip_finish``.  Returns the device record the updates are conditional on."""
         counts = [ops.grad_norm_partials(f.grad.numel()) for f in flats]
         total = sum(counts)
         dev = flats[0].grad.device
@@ -270,90 +254,79 @@ class FusedAdamW(torch.optim.Optimizer):
             if self._clip_state is None or self._clip_state.device != dev:
                 self._clip_state = torch.zeros(ops.GRAD_CLIP_STATE_WORDS, dtype=torch.int32, device=dev)
             self._clip_partials = torch.empty(total, dtype=torch.float64, device=dev)
-        state, off = self._clip_state, 0
+        off = 0
         for f, c in zip(flats, counts):
             f.bind_grads()
             ops.grad_sumsq_partial(f.grad, self._clip_partials[off:off + c])
             off += c
-        ops.grad_clip_finish(self._clip_partials[:total], self._max_norm, state)
-        for f in flats:
-            g = in_opt[id(f.params[0])]
-            st = self._state_for(f)
-            if "hyper" not in st:
-                if capturing:
-                    raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing")
-                st["hyper"] = torch.zeros(2, dtype=torch.int32, device=f.data.device)   # [lr as f32 bits, step as uint32]
+        ops.grad_clip_finish(self._clip_partials[:total], self._max_norm, self._clip_state)
+        return self._clip_state
+
+    def _step_flat(self, f, g, capturing, clip):
+        """The update of this rank's slice of flat buffer ``f`` with param group ``g``'s hyperparameters: exactly one of ``adamw_step``
+        (lr and step as launch arguments), ``adamw_step_dev`` (device hyper) and, with ``clip`` the norm pass's device record,
+        ``counter_add_if`` + ``adamw_step_clip``.  The step word of the ``hyper`` pair lives on the device so that no in-flight node
+        ever reads host memory.  Device hyper: it is the host's count, set by a fill that carries the value as a launch argument, or
+        under capture advanced by a ``counter_add`` node on every replay.  Clipping: it is filled once, when the pair is created, and
+        from then on only advanced on the device, by ``counter_add_if``: it counts APPLIED steps, ``st["step"]`` attempted ones."""
+        st = self._state_for(f)
+        lo, hi = self._slice_of(f)
+        # device hyper: an empty slice launches nothing and gets no pair; clipping: every buffer gets one (an empty slice's stays as filled)
+        if "hyper" not in st and (clip is not None or (self._dev_hyper and hi > lo)):
+            if capturing:
+                raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing")
+            st["hyper"] = torch.zeros(2, dtype=torch.int32, device=f.data.device)   # [lr as f32 bits, step as uint32]
+            if clip is not None:
                 st["hyper"][1:2].fill_(st["step"])
-            st["step"] += 1
-            lo, hi = self._slice_of(f)
-            if hi <= lo:
-                continue
-            fdata, fgrad = (f.data, f.grad) if self._shard is None else (f.data[lo:hi], f.grad[lo:hi])
-            if not capturing:
-                lr = float(g["lr"])
-                if st.get("lr_staged") != lr:
-                    st["hyper"].view(torch.float32)[0:1].fill_(lr)
-                    st["lr_staged"] = lr
-            ops.counter_add_if(st["hyper"][1:2], 1, state[0:1])
-            ops.adamw_step_clip(fdata, fgrad, st["m"], st["v"], st["hyper"], state, g["betas"][0], g["betas"][1], g["eps"],
-                                g["weight_decay"])
+        st["step"] += 1
+        if hi <= lo:
+            return
+        fdata, fgrad = (f.data, f.grad) if self._shard is None else (f.data[lo:hi], f.grad[lo:hi])
+        (beta1, beta2), eps, wd = g["betas"], g["eps"], g["weight_decay"]
+        if clip is None and not self._dev_hyper:
+            ops.adamw_step(fdata, fgrad, st["m"], st["v"], g["lr"], beta1, beta2, eps, wd, st["step"])
+            return
+        if clip is None:
+            if capturing:
+                ops.counter_add(st["hyper"][1:2], 1)              # a node of the graph: every replay advances the step word
+            else:
+                st["hyper"][1:2].fill_(st["step"])                 # value travels as a launch argument
+        if not capturing:
+            self._stage_lr(st, g["lr"])
+        if clip is None:
+            ops.adamw_step_dev(fdata, fgrad, st["m"], st["v"], st["hyper"], beta1, beta2, eps, wd)
+        else:
+            ops.counter_add_if(st["hyper"][1:2], 1, clip[0:1])
+            ops.adamw_step_clip(fdata, fgrad, st["m"], st["v"], st["hyper"], clip, beta1, beta2, eps, wd)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        if self._clip_on:
-            self._step_clipped()
-            if self._shard is not None and not torch.cuda.is_current_stream_capturing():
-                self.sync_updated_slices()
-            return loss
-        handled = set()
         in_opt = {id(p): g for g in self.param_groups for p in g["params"]}
-        for f in self._flats:
-            if not f.valid() or not all(id(p) in in_opt for p in f.params):
-                continue
-            g = in_opt[id(f.params[0])]
-            st = self._state_for(f)
-            f.bind_grads()
-            st["step"] += 1
-            lo, hi = self._slice_of(f)
-            if hi <= lo:
-                handled.update(id(p) for p in f.params)
-                continue
-            fdata, fgrad = (f.data, f.grad) if self._shard is None else (f.data[lo:hi], f.grad[lo:hi])
+        flats = [f for f in self._flats if f.valid() and all(id(p) in in_opt for p in f.params)]
+        # asked once per step; a step on CPU tensors (the launch traces of tests/) cannot be under capture
+        capturing = bool(flats) and flats[0].data.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        handled = {id(p) for f in flats for p in f.params}
+        loose = [(g, p) for g in self.param_groups for p in g["params"] if id(p) not in handled and p.grad is not None]
+        if self._clip_on and loose:
+            raise RuntimeError("FusedAdamW: gradient clipping / skipping needs every trainable tensor in an engine's flat "
+                               "buffer (the norm is formed over the flat gradient buffers)")
+        clip = self._norm_pass(flats, capturing) if self._clip_on and flats else None
+        for f in flats:
+            if clip is None:
+                f.bind_grads()
+            self._step_flat(f, in_opt[id(f.params[0])], capturing, clip)
+        for g, p in loose:                            # a trainable tensor in no flat buffer: its own launch of the host-argument step
             if self._dev_hyper:
-                capturing = torch.cuda.is_current_stream_capturing()
-                if "hyper" not in st:
-                    if capturing:
-                        raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing")
-                    st["hyper"] = torch.zeros(2, dtype=torch.int32, device=f.data.device)   # [lr as f32 bits, step as uint32]
-                if capturing:
-                    ops.counter_add(st["hyper"][1:2], 1)          # a node of the graph: every replay advances the step word
-                else:
-                    st["hyper"][1:2].fill_(st["step"])             # value travels as a launch argument
-                    lr = float(g["lr"])
-                    if st.get("lr_staged") != lr:
-                        st["hyper"].view(torch.float32)[0:1].fill_(lr)
-                        st["lr_staged"] = lr
-                ops.adamw_step_dev(fdata, fgrad, st["m"], st["v"], st["hyper"], g["betas"][0], g["betas"][1], g["eps"],
-                                   g["weight_decay"])
-            else:
-                ops.adamw_step(fdata, fgrad, st["m"], st["v"], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                               g["weight_decay"], st["step"])
-            handled.update(id(p) for p in f.params)
-        for group in self.param_groups:
-            for p in group["params"]:
-                if id(p) in handled or p.grad is None:
-                    continue
-                if self._dev_hyper:
-                    raise RuntimeError("FusedAdamW: device-side (lr, step) needs every trainable tensor in an engine's flat buffer")
-                if not (p.is_cuda and p.dtype == torch.float32 and p.data.is_contiguous() and p.grad.is_contiguous()):
-                    raise RuntimeError("FusedAdamW: parameters must be contiguous f32 GPU tensors (no CPU path)")
-                st = self.state[p]
-                if not st:
-                    st["m"], st["v"], st["step"] = torch.zeros_like(p.data), torch.zeros_like(p.data), 0
-                st["step"] += 1
-                ops.adamw_step(p.data.view(-1), p.grad.view(-1), st["m"].view(-1), st["v"].view(-1), group["lr"],
-                               group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], st["step"])
-        if self._shard is not None and not torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: device-side (lr, step) needs every trainable tensor in an engine's flat buffer")
+            if not (p.is_cuda and p.dtype == torch.float32 and p.data.is_contiguous() and p.grad.is_contiguous()):
+                raise RuntimeError("FusedAdamW: parameters must be contiguous f32 GPU tensors (no CPU path)")
+            st = self.state[p]
+            if not st:
+                st["m"], st["v"], st["step"] = torch.zeros_like(p.data), torch.zeros_like(p.data), 0
+            st["step"] += 1
+            ops.adamw_step(p.data.view(-1), p.grad.view(-1), st["m"].view(-1), st["v"].view(-1), g["lr"], g["betas"][0], g["betas"][1],
+                           g["eps"], g["weight_decay"], st["step"])
+        if self._shard is not None and not capturing:
             self.sync_updated_slices()
         return loss

@@ -498,10 +498,11 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ g,
     }
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                     float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                     float beta1, float beta2, float eps, float wd, float inv_bc1,
-                                                     float inv_sqrt_bc2, float grad_scale) {
+// The AdamW update of a workgroup's elements (grid-stride, 256 threads), the one body of the three kernels below: what they compute
+// stays equal bit for bit because it is the same code.
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, long n, float lr, float beta1, float beta2, float eps, float wd,
+                                             float inv_bc1, float inv_sqrt_bc2, float grad_scale) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float gi = g[i] * grad_scale;
         float pi = p[i] * (1.0f - lr * wd);
@@ -518,25 +519,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // lr and step come from device memory: hyper[0] = lr (f32), hyper[1] = step count (uint32 bits, advanced by a
 // bsclip_counter_add node of the captured step, so no in-flight node ever reads host memory); the bias corrections are
 // formed in f64 like the host form does
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, long n,
-                                                         const float* __restrict__ hyper, float beta1, float beta2, float eps,
-                                                         float wd, float grad_scale) {
+struct AdamwHyper {
+    float lr, inv_bc1, inv_sqrt_bc2;
+};
+__device__ __forceinline__ AdamwHyper adamw_hyper(const float* __restrict__ hyper, float beta1, float beta2) {
     const float lr = hyper[0];
     const double step = (double)reinterpret_cast<const unsigned*>(hyper)[1];
     const float inv_bc1 = (float)(1.0 / (1.0 - pow((double)beta1, step)));
     const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, step)));
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * grad_scale;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        pi -= (lr * inv_bc1) * (mi / denom);
-        p[i] = pi;
-        m[i] = mi;
-        v[i] = vi;
-    }
+    return {lr, inv_bc1, inv_sqrt_bc2};
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                     float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                     float beta1, float beta2, float eps, float wd, float inv_bc1,
+                                                     float inv_sqrt_bc2, float grad_scale) {
+    adamw_update(p, g, m, v, n, lr, beta1, beta2, eps, wd, inv_bc1, inv_sqrt_bc2, grad_scale);
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, long n,
+                                                         const float* __restrict__ hyper, float beta1, float beta2, float eps,
+                                                         float wd, float grad_scale) {
+    const AdamwHyper h = adamw_hyper(hyper, beta1, beta2);
+    adamw_update(p, g, m, v, n, h.lr, beta1, beta2, eps, wd, h.inv_bc1, h.inv_sqrt_bc2, grad_scale);
 }
 
 }  // namespace
@@ -738,15 +744,18 @@ extern "C" int bsclip_colsum(const void* g, int ld_g, int g_is_bf16, int M, int 
     return BSCLIP_OK;
 }
 
+static unsigned adamw_grid(int64_t n) {   // the three AdamW kernels: 256 elements per workgroup, grid-stride beyond 2048 workgroups
+    const int64_t blocks = (n + 255) / 256;
+    return (unsigned)(blocks > 2048 ? 2048 : blocks);
+}
+
 extern "C" int bsclip_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                                  float beta2, float eps, float weight_decay, int step, float grad_scale,
                                  void* stream) {
     BSCLIP_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bsclip_adamw_step: bad args (n=%ld step=%d)", (long)n, step);
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v,
+    hipLaunchKernelGGL(adamw_kernel, dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v,
                        (long)n, lr, beta1, beta2, eps, weight_decay, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)),
                        grad_scale);
     BSCLIP_LAUNCH_CHECK();
@@ -756,9 +765,7 @@ extern "C" int bsclip_adamw_step(float* p, const float* g, float* m, float* v, i
 extern "C" int bsclip_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev,
                                      float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
     BSCLIP_REQUIRE(p && g && m && v && hyper_dev && n > 0, "bsclip_adamw_step_dev: null/empty input");
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v,
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v,
                        (long)n, hyper_dev, beta1, beta2, eps, weight_decay, grad_scale);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
@@ -851,29 +858,16 @@ __global__ void counter_add_if_kernel(unsigned* p, unsigned inc, const unsigned*
     if (*cond != 0u) *p += inc;
 }
 
-// adamw_dev_kernel, operation for operation, with the gradient multiplied by the record's coef and nothing stored when the record
-// says skip (state[0] == 0: the gradient was not finite)
+// adamw_dev_kernel (the same adamw_hyper and adamw_update) with the gradient multiplied by the record's coef and nothing stored when
+// the record says skip (state[0] == 0: the gradient was not finite)
 __global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, long n,
                                                           const float* __restrict__ hyper, const unsigned* __restrict__ state,
                                                           float beta1, float beta2, float eps, float wd) {
     if (state[0] == 0u) return;
     const float grad_scale = __uint_as_float(state[1]);
-    const float lr = hyper[0];
-    const double step = (double)reinterpret_cast<const unsigned*>(hyper)[1];
-    const float inv_bc1 = (float)(1.0 / (1.0 - pow((double)beta1, step)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, step)));
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * grad_scale;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        pi -= (lr * inv_bc1) * (mi / denom);
-        p[i] = pi;
-        m[i] = mi;
-        v[i] = vi;
-    }
+    const AdamwHyper h = adamw_hyper(hyper, beta1, beta2);
+    adamw_update(p, g, m, v, n, h.lr, beta1, beta2, eps, wd, h.inv_bc1, h.inv_sqrt_bc2, grad_scale);
 }
 
 }  // namespace
@@ -929,9 +923,7 @@ extern "C" int bsclip_adamw_step_clip(float* p, const float* g, float* m, float*
     BSCLIP_REQUIRE(n > 0, "bsclip_adamw_step_clip: n=%ld must be positive", (long)n);
     BSCLIP_REQUIRE(aligned_to(4, p, g, m, v, hyper_dev), "bsclip_adamw_step_clip: p, g, m, v and hyper_dev must be 4-byte aligned");
     BSCLIP_REQUIRE(aligned_to(16, state), "bsclip_adamw_step_clip: state must be 16-byte aligned");
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, (long)n,
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, (long)n,
                        hyper_dev, static_cast<const unsigned*>(state), beta1, beta2, eps, weight_decay);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
