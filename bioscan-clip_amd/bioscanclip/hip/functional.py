@@ -125,6 +125,59 @@ def infonce(zs, labels, scale, row0=0, n_local=None):
     return _InfoNCE.apply(labels.to(torch.int64).contiguous(), float(scale), row0, n_local, ws, *[z.to(F32) for z in zs])
 
 
+class _SigmoidLoss(torch.autograd.Function):
+    """The sigmoid (SigLIP) loss with a learnable scale and bias (``bsclip_sigmoid_loss_fwd_bwd``): ``log_scale`` (t) and ``bias``
+    (b) are one f32 each on the GPU, read by the kernels when they run.  One call leaves the loss, dLoss/dz and, in ``aux_out``,
+    (dLoss/dt of the own rows, the scale used, dLoss/db of the own rows, b); the backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, labels, log_scale, bias, row0, n_local, workspace, aux_out, *zs):
+        zs = [z.contiguous() for z in zs]
+        N = zs[0].shape[0]
+        n_local = N if n_local is None else n_local
+        loss = torch.zeros(1, dtype=F32, device=zs[0].device)
+        need_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or any(ctx.needs_input_grad[7:])
+        dzs = [torch.empty(n_local, z.shape[1], dtype=F32, device=z.device) for z in zs] if need_grad else None
+        ops.sigmoid_loss_fwd_bwd(zs, labels, log_scale, bias, loss, dzs, aux_out, row0=row0, n_local=n_local, workspace=workspace)
+        ctx.dzs, ctx.row0, ctx.N, ctx.aux_out, ctx.t_shape, ctx.b_shape = dzs, row0, N, aux_out, log_scale.shape, bias.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        outs = []
+        for i, d in enumerate(ctx.dzs):
+            if not ctx.needs_input_grad[7 + i]:
+                outs.append(None)
+            elif d.shape[0] == ctx.N:
+                outs.append(d * g)
+            else:  # gathered batch: only the local rows carry gradient (SURVEY 8e)
+                full = torch.zeros(ctx.N, d.shape[1], dtype=F32, device=d.device)
+                full[ctx.row0:ctx.row0 + d.shape[0]] = d * g
+                outs.append(full)
+        dt = (ctx.aux_out[0] * g).reshape(ctx.t_shape) if ctx.needs_input_grad[1] else None
+        db = (ctx.aux_out[2] * g).reshape(ctx.b_shape) if ctx.needs_input_grad[2] else None
+        return (None, dt, db, None, None, None, None) + tuple(outs)
+
+
+def sigmoid_loss(zs, labels, log_scale, bias, row0=0, n_local=None):
+    """loss = 1/(P N) sum over the directed modality pairs and the cells (i, j) of softplus(-y_ij (s zn^a_i . zn^b_j + b)), with
+    s = exp(clamp(log_scale, 0, ln 100)) and y = +1 where the labels agree, -1 elsewhere.  The returned loss carries ``aux_out`` =
+    (dLoss/dt of the own rows, s, dLoss/db of the own rows, b)."""
+    if len(zs) < 2:
+        raise ValueError("Too less element for calculating the contrastive loss.")
+    if not zs[0].is_cuda:
+        raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
+    for name, v in (("log_scale", log_scale), ("bias", bias)):
+        if not (torch.is_tensor(v) and v.is_cuda and v.dtype == F32 and v.numel() == 1):
+            raise ValueError(f"sigmoid_loss: {name} must be a 1-element f32 CUDA tensor")
+    ws = _workspace(zs[0].shape[0], len(zs), zs[0].device)
+    aux_out = torch.empty(4, dtype=F32, device=zs[0].device)
+    loss = _SigmoidLoss.apply(labels.to(torch.int64).contiguous(), log_scale, bias, row0, n_local, ws, aux_out,
+                              *[z.to(F32) for z in zs])
+    loss.aux_out = aux_out
+    return loss
+
+
 # ---- supervised fine-tuning head: Linear(768, C) + CrossEntropyLoss (reference util.py:13-25, fine_tuning_epoch.py:27) ----------
 HEAD_D = 768
 

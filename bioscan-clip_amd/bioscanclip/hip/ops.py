@@ -665,6 +665,19 @@ def infonce_fwd_bwd_ts(zs, labels, log_scale, loss_out, dzs, scale_out, row0=0, 
                                               _p(scale_out), _p(workspace), _stream()))
 
 
+def sigmoid_loss_fwd_bwd(zs, labels, log_scale, bias, loss_out, dzs, aux_out, row0=0, n_local=None, workspace=None):
+    """The sigmoid (SigLIP) loss over every modality pair: x = s G + b with s = exp(clamp(t, 0, ln 100)), t = ``log_scale`` and
+    b = ``bias`` (one f32 each on the GPU), read by the kernels when they run.  zs / dzs / row0 / n_local / workspace as for
+    ``infonce_fwd_bwd``.  ``aux_out`` f32 [4] receives (the own rows' share of dLoss/dt, s, the own rows' share of dLoss/db, b)."""
+    for name, v in (("log_scale", log_scale), ("bias", bias)):
+        _req(torch.is_tensor(v) and v.is_cuda and v.dtype == F32 and v.numel() == 1, f"{name} must be a 1-element f32 CUDA tensor")
+    _req(torch.is_tensor(aux_out) and aux_out.is_cuda and aux_out.dtype == F32 and aux_out.is_contiguous()
+         and aux_out.numel() >= 4, "aux_out must be a contiguous f32 CUDA tensor with >= 4 elements")
+    nmod, N, D, n_local, zp, dzp = _infonce_args(zs, labels, loss_out, dzs, row0, n_local, workspace)
+    check(_l.load().bsclip_sigmoid_loss_fwd_bwd(zp, nmod, _p(labels), N, D, _p(log_scale), _p(bias), row0, n_local, _p(loss_out), dzp,
+                                                _p(aux_out), _p(workspace), _stream()))
+
+
 def _topk_outputs(queries, K, k, msg_q, msg_k):
     """What ``topk_ip`` and ``topk_ip_indexed`` share: the query check and the outputs.  Returns (Q, D, scores, idx)."""
     _req(queries.dim() == 2 and queries.dtype == F32 and queries.is_contiguous() and queries.is_cuda, msg_q)

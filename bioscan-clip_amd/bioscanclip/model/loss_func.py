@@ -5,11 +5,14 @@
 The arithmetic is the fused HIP InfoNCE (``bsclip_infonce_fwd_bwd``): soft-target CE over every ordered modality
 pair, second ``F.normalize`` applied inside (loss_func.py:43-44).  The temperature is fixed at construction (a float) or
 learnable: an ``nn.Parameter`` holding t = log(scale), which the kernels read on the device (``bsclip_infonce_fwd_bwd_ts``).
+
+``SigmoidContrastiveLoss`` is a second criterion with the same call signature: the pairwise sigmoid loss of SigLIP on a learnable
+scale and bias (``bsclip_sigmoid_loss_fwd_bwd``, ``model_config.contrastive_loss: sigmoid``).
 """
 import torch
 import torch.nn as nn
 
-from bioscanclip.hip.functional import infonce
+from bioscanclip.hip.functional import infonce, sigmoid_loss
 
 
 def construct_label_metrix(labels):
@@ -55,6 +58,49 @@ class ContrastiveLoss(nn.Module):
         if len(feature_list) < 2:
             raise ValueError("Too less element for calculating the contrastive loss.")
         return self._infonce(feature_list, label)
+
+
+class SigmoidContrastiveLoss(nn.Module):
+    """The pairwise sigmoid loss of SigLIP (Zhai et al., ICCV 2023) over every modality pair, with ``ContrastiveLoss``'s call
+    signature: every cell (i, j) is a binary decision "same label or not" on x = s cos(i, j) + b, so several positives per row
+    need no soft targets and nothing is normalised over the batch.  ``logit_scale`` (t = log s, clamped to [0, ln 100]) and
+    ``logit_bias`` (b) are the model's ``nn.Parameter``s (``model_config.contrastive_loss: sigmoid``); the kernels read them on the
+    device (``bsclip_sigmoid_loss_fwd_bwd``).  One rank only: ``world_size`` is the process group's size when not given."""
+
+    def __init__(self, logit_scale, logit_bias, world_size=None):
+        super().__init__()
+        if world_size is None:
+            import torch.distributed as dist
+            world_size = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if world_size > 1:
+            raise ValueError(f"SigmoidContrastiveLoss: the sigmoid loss is not built for more than one rank (world_size={world_size})")
+        for name, v in (("logit_scale", logit_scale), ("logit_bias", logit_bias)):
+            if not (torch.is_tensor(v) and v.numel() == 1):
+                raise TypeError(f"SigmoidContrastiveLoss: {name} is a 1-element tensor (the model's parameter)")
+        # the model owns both: kept out of this module's own parameters, as ContrastiveLoss keeps its learnable temperature
+        object.__setattr__(self, "logit_scale", logit_scale)
+        object.__setattr__(self, "logit_bias", logit_bias)
+        self._aux_out = None
+
+    def current_scale(self):
+        """The scale the last forward used, as a device scalar (before any forward, exp(clamp(t, 0, ln 100)) of the parameter)."""
+        if self._aux_out is not None:
+            return self._aux_out[1]
+        return self.logit_scale.detach().float().clamp(0.0, 4.605170185988092).exp().reshape(())
+
+    def current_bias(self):
+        """The bias the last forward used, as a device scalar (before any forward, the parameter's present value)."""
+        if self._aux_out is not None:
+            return self._aux_out[3]
+        return self.logit_bias.detach().float().reshape(())
+
+    def forward(self, image_features, dna_features, text_features, label):
+        feature_list = [item for item in (image_features, dna_features, text_features) if item is not None]
+        if len(feature_list) < 2:
+            raise ValueError("Too less element for calculating the contrastive loss.")
+        loss = sigmoid_loss(feature_list, label, self.logit_scale, self.logit_bias)
+        self._aux_out = loss.aux_out
+        return loss
 
 
 class GlobalBatchContrastiveLoss(ContrastiveLoss):

@@ -47,16 +47,17 @@ class SimpleCLIP(nn.Module):
         self._temperature_flat = None
 
     def bind_temperature(self):
-        """The learnable temperature's flat buffer (``model.logit_scale``, when the model has one): one parameter padded to four
-        floats, the home FusedAdamW updates like an engine's.  Built with the first training forward, and again when the parameter
-        was moved (``model.to``) -- ``hip.dist.flat_buffers`` finds it here."""
-        t = self._parameters.get("logit_scale")
-        if t is None or not (t.requires_grad and t.is_cuda and torch.is_grad_enabled()):
+        """The flat buffer of the loss's learnable scalars (``model.logit_scale``, and ``model.logit_bias`` of the sigmoid loss, when
+        the model has them): each parameter padded to four floats -- four floats for the temperature alone, eight with the bias at
+        offset 4 -- the home FusedAdamW updates like an engine's.  Built with the first training forward, and again when a
+        parameter was moved (``model.to``) -- ``hip.dist.flat_buffers`` finds it here."""
+        ps = [p for p in (self._parameters.get("logit_scale"), self._parameters.get("logit_bias")) if p is not None]
+        if not ps or not all(p.requires_grad and p.is_cuda for p in ps) or not torch.is_grad_enabled():
             return
         flat = self._temperature_flat
-        if flat is None or flat.params[0] is not t or not flat.valid():
+        if flat is None or len(flat.params) != len(ps) or any(a is not b for a, b in zip(flat.params, ps)) or not flat.valid():
             from bioscanclip.hip.engine import FlatParams
-            self._temperature_flat = FlatParams([t], t.device)
+            self._temperature_flat = FlatParams(ps, ps[0].device)
 
     def forward(self, image_input, dna_input, language_input):
         image_output = None
@@ -127,6 +128,26 @@ def trainable_temperature(args):
     return bool(getattr(getattr(args, "model_config", None), "trainable_temperature", False))
 
 
+SIGMOID_LOG_SCALE, SIGMOID_BIAS = math.log(10.0), -10.0   # SigLIP's initial values (Zhai et al. 2023, section 3.2)
+
+
+def contrastive_loss_kind(args):
+    """``model_config.contrastive_loss``: ``infonce`` (also when the key is absent) or ``sigmoid``; anything else is refused, and so is
+    ``sigmoid`` next to ``trainable_temperature`` (the sigmoid loss brings its own learnable scale)."""
+    kind = str(getattr(getattr(args, "model_config", None), "contrastive_loss", "infonce")).lower()
+    if kind not in ("infonce", "sigmoid"):
+        raise ValueError(f"model_config.contrastive_loss={kind!r}: expected 'infonce' or 'sigmoid'")
+    if kind == "sigmoid" and trainable_temperature(args):
+        raise ValueError("model_config.contrastive_loss=sigmoid has its own learnable scale: leave trainable_temperature off")
+    return kind
+
+
+def sigmoid_init(args):
+    """(t, b) the sigmoid loss starts from: ``model_config.sigmoid_log_scale`` / ``model_config.sigmoid_bias``, ln 10 and -10 by default."""
+    mc = getattr(args, "model_config", None)
+    return float(getattr(mc, "sigmoid_log_scale", SIGMOID_LOG_SCALE)), float(getattr(mc, "sigmoid_bias", SIGMOID_BIAS))
+
+
 def load_clip_model(args, device=None):
     """Reference simple_clip.py:125-203, same config keys (``args.model_config.{image,dna,language,output_dim,
     disable_lora}``, ``args.bioscan_bert_checkpoint``).  ``disable_lora: true`` selects full fine-tuning (hip/engine_ft.py).
@@ -180,6 +201,13 @@ def load_clip_model(args, device=None):
         # t = log(logit scale), the initial value of the reference's SimpleCLIP_With_Trainable_Temp sketch; the contrastive loss
         # reads it on the device (ContrastiveLoss(logit_scale=model.logit_scale)).  Only training uses it: no forward reads it.
         model.logit_scale = nn.Parameter(torch.tensor(math.log(1 / 0.07)))
+
+    if contrastive_loss_kind(args) == "sigmoid":
+        # the sigmoid loss's learnable scalars, t = log(scale) and the bias; SigmoidContrastiveLoss(model.logit_scale, model.logit_bias)
+        # reads them on the device.  Only training uses them: no forward reads them.
+        t0, b0 = sigmoid_init(args)
+        model.logit_scale = nn.Parameter(torch.tensor(t0))
+        model.logit_bias = nn.Parameter(torch.tensor(b0))
 
     if device is not None:
         model.to(device)

@@ -78,12 +78,17 @@ def load_model_and_checkpoint(args, device, ckpt_optional=False):
     if hasattr(mc, "load_ckpt") and mc.load_ckpt is False or ckpt_optional and not hasattr(mc, "ckpt_path"):
         return model, False
     state_dict = remove_extra_pre_fix(torch.load(str(mc.ckpt_path), map_location="cpu"))
-    # the learnable temperature (model_config.trainable_temperature) is the one key a checkpoint and a model may disagree on: a
-    # checkpoint trained without it starts the temperature at its initial value, a model built without it ignores the checkpoint's
-    wants = "logit_scale" in model._parameters
-    if wants and "logit_scale" not in state_dict:
-        print(f"checkpoint {mc.ckpt_path} has no logit_scale: the temperature keeps its initial value "
-              f"(logit_scale = {float(model.logit_scale.detach()):.6f})")
-    load_checked(model, state_dict, f"checkpoint {mc.ckpt_path}", allow_missing=("logit_scale",) if wants else (),
-                 allow_unexpected=() if wants else ("logit_scale",))
+    # the loss's learnable scalars (model_config.trainable_temperature: logit_scale; model_config.contrastive_loss=sigmoid: logit_scale
+    # and logit_bias) are the keys a checkpoint and a model may disagree on: a checkpoint trained without one starts it at its
+    # initial value, a model built without one ignores the checkpoint's
+    missing, unexpected = [], []
+    for key, what in (("logit_scale", "temperature"), ("logit_bias", "bias")):
+        if key in model._parameters:
+            missing.append(key)
+            if key not in state_dict:
+                print(f"checkpoint {mc.ckpt_path} has no {key}: the {what} keeps its initial value "
+                      f"({key} = {float(model._parameters[key].detach()):.6f})")
+        else:
+            unexpected.append(key)
+    load_checked(model, state_dict, f"checkpoint {mc.ckpt_path}", allow_missing=tuple(missing), allow_unexpected=tuple(unexpected))
     return model, True

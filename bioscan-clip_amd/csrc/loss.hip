@@ -22,6 +22,9 @@
 // slabs of <= 1024 rows as f32 in the workspace, a separate row-reduce / dL/dG kernel reads them back.
 // Batched slab form (the default up to 1024 padded rows, i.e. one slab): the slab form's arithmetic with the logits of all directed
 // pairs kept side by side and one launch per stage over all modalities / pairs (see g_infonce_impl below).
+//
+// Sigmoid (SigLIP) loss with a learnable scale and bias (bsclip_sigmoid_loss_fwd_bwd, further down): the same prep kernels, split
+// products and l2norm backward with elementwise kernels of its own (sig_*), in the batched and the slab form; no fused form.
 #include <math.h>
 #include <stdlib.h>
 
@@ -375,6 +378,153 @@ __global__ __launch_bounds__(256) void infonce_combine_ts_kernel(const float* __
     infonce_combine_rows<true>(part, N, tiles, cnt, lse, contrib, sc[1], tcontrib);
 }
 
+// ---- sigmoid (SigLIP) loss: every cell (i, j) of a logits matrix is its own binary decision ----
+// x = s G + b with s = exp(clamp(t, 0, ln 100)) as above, y = +1 where the labels agree and -1 elsewhere, term softplus(-y x),
+// w = d term / dx = -y sigmoid(-y x).  t and b are read from device memory by every kernel that needs them (each forms the same s
+// from the same t, so no kernel runs ahead of the others to leave it somewhere).  With u = -y x the one exponential taken is
+// exp(-|u|) in (0, 1]: x reaches +-130 at s = 100 with a large |b|, where log(1 + exp(u)) and 1 / (1 + exp(-u)) overflow.
+// The term is elementwise and G^{ba} = (G^{ab})^T, so the directed pairs (a, b) and (b, a) hold the same terms: the loss and the
+// two scalar gradients are summed over the unordered pairs a < b and doubled.  The sums are carried in f64 (three adds per cell, a
+// fixed order): the loss, dLoss/dt and dLoss/db then carry the rounding of their f32 terms and nothing from the order of summation.
+__device__ __forceinline__ float sig_scale(const float* __restrict__ log_scale) {
+    const float t = log_scale[0];
+    return t <= 0.f ? 1.0f : t >= LN_100 ? 100.0f : expf(t);
+}
+__device__ __forceinline__ void sig_cell(float g, bool same, float s, float b, float& sp, float& w) {
+    const float x = fmaf(s, g, b);
+    const float u = same ? -x : x;
+    const float e = expf(-fabsf(u));
+    sp = fmaxf(u, 0.f) + log1pf(e);
+    const float sg = (u >= 0.f ? 1.0f : e) / (1.0f + e);   // sigmoid(u)
+    w = same ? -sg : sg;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One wave per row i of a slab of G (cosines, ld = Np): part[3 i .. 3 i + 2] = sum_j over j < N of (softplus term, w, w G)
+__device__ __forceinline__ void sig_row_reduce_rows(const float* __restrict__ G, int row0, int nrows, int N, int Np,
+                                                    const float* __restrict__ log_scale, const float* __restrict__ bias,
+                                                    const int64_t* __restrict__ labels, double* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int r = (blockIdx.x * 256 + threadIdx.x) >> 6;  // row inside the slab
+    if (r >= nrows) return;
+    const int row = row0 + r;
+    const float* g = G + (size_t)r * Np;
+    const int64_t li = labels[row];
+    const float s = sig_scale(log_scale), b = bias[0];
+    double asp = 0.0, aw = 0.0, awg = 0.0;
+    for (int j = lane; j < N; j += 64) {
+        float sp, w;
+        sig_cell(g[j], labels[j] == li, s, b, sp, w);
+        asp += (double)sp;
+        aw += (double)w;
+        awg += (double)w * (double)g[j];
+    }
+    asp = wave_sum_f64(asp);
+    aw = wave_sum_f64(aw);
+    awg = wave_sum_f64(awg);
+    if (lane == 0) {
+        double* p = part + (size_t)row * 3;
+        p[0] = asp;
+        p[1] = aw;
+        p[2] = awg;
+    }
+}
+__global__ __launch_bounds__(256) void sig_row_reduce_kernel(const float* __restrict__ G, int row0, int nrows, int N, int Np,
+                                                              const float* __restrict__ log_scale, const float* __restrict__ bias,
+                                                              const int64_t* __restrict__ labels, double* __restrict__ part) {
+    sig_row_reduce_rows(G, row0, nrows, N, Np, log_scale, bias, labels, part);
+}
+// unordered pair blockIdx.y (a < b in the order (0,1), (0,2), (1,2)): all N rows of the kept logits matrix of the directed pair
+// (a, b), G[a (nmod - 1) + b - 1]; part is [nu, Np, 3]
+__global__ __launch_bounds__(256) void sig_row_reduce_batched_kernel(const float* __restrict__ G, int nmod, int N, int Np,
+                                                                      const float* __restrict__ log_scale,
+                                                                      const float* __restrict__ bias,
+                                                                      const int64_t* __restrict__ labels, double* __restrict__ part) {
+    const int u = blockIdx.y;
+    const int a = u == 2 ? 1 : 0, b = u == 0 ? 1 : 2;
+    const size_t p = a * (nmod - 1) + b - 1;
+    sig_row_reduce_rows(G + p * Np * Np, 0, N, N, Np, log_scale, bias, labels, part + (size_t)u * Np * 3);
+}
+
+// W[i_local, j] = 2 s w_ij / den, j < N, else 0: dLoss/dG^{ab} + (dLoss/dG^{ba})^T with den = P N, as the split GEMM operand
+// [hi | hi | lo] (bf16 [n_local, 3*Np]) of dzn^a = sum_b W^{ab} zn^b
+__device__ __forceinline__ void sig_w_elems(const float* __restrict__ G, int N, int Np, int row0, int n_local,
+                                            const float* __restrict__ log_scale, const float* __restrict__ bias, float den,
+                                            const int64_t* __restrict__ labels, bf16_t* __restrict__ W) {
+    const float s = sig_scale(log_scale), b = bias[0];
+    const float coef = 2.0f * s / den;
+    const long total = (long)n_local * Np;
+    for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
+        const int il = (int)(it / Np), j = (int)(it % Np);
+        float w = 0.f;
+        if (j < N) {
+            float sp;
+            sig_cell(G[(size_t)il * Np + j], labels[row0 + il] == labels[j], s, b, sp, w);
+            w *= coef;
+        }
+        bf16_t h, l;
+        split_bf(w, h, l);
+        bf16_t* dst = W + (size_t)il * 3 * Np + j;
+        dst[0] = h;
+        dst[Np] = h;
+        dst[2 * Np] = l;
+    }
+}
+__global__ __launch_bounds__(256) void sig_w_kernel(const float* __restrict__ G, int N, int Np, int row0, int n_local,
+                                                     const float* __restrict__ log_scale, const float* __restrict__ bias, float den,
+                                                     const int64_t* __restrict__ labels, bf16_t* __restrict__ W) {
+    sig_w_elems(G, N, Np, row0, n_local, log_scale, bias, den, labels, W);
+}
+// directed pair blockIdx.y: rows [row0, row0 + n_local) of its kept logits matrix G[p] -> W[p] ([n_local, 3 Np], w_stride apart)
+__global__ __launch_bounds__(256) void sig_w_batched_kernel(const float* __restrict__ G, int N, int Np, int row0, int n_local,
+                                                             const float* __restrict__ log_scale, const float* __restrict__ bias,
+                                                             float den, const int64_t* __restrict__ labels, bf16_t* __restrict__ W,
+                                                             size_t w_stride) {
+    const size_t p = blockIdx.y;
+    sig_w_elems(G + (p * Np + row0) * Np, N, Np, row0, n_local, log_scale, bias, den, labels, W + p * w_stride);
+}
+
+// loss = two_over_den * sum over the nu unordered pairs and the rows i < N of part[.][i][0]; aux = (the own rows' share of dLoss/dt,
+// s, the own rows' share of dLoss/db, b) with the shares summed over the rows [row0, row0 + n_own) -- single workgroup, fixed
+// order, f64 (bitwise reproducible).  Only entries the row reductions wrote are read.
+__global__ __launch_bounds__(256) void sig_final_kernel(const double* __restrict__ part, int nu, int Np, int N, int row0, int n_own,
+                                                         double two_over_den, const float* __restrict__ log_scale,
+                                                         const float* __restrict__ bias, float* __restrict__ loss_out,
+                                                         float* __restrict__ aux) {
+    __shared__ double red[3][256];
+    double sp = 0.0, w = 0.0, wg = 0.0;
+    for (int u = 0; u < nu; ++u) {
+        const double* p = part + (size_t)u * Np * 3;
+        for (int i = threadIdx.x; i < N; i += 256) sp += p[(size_t)i * 3];
+        for (int i = row0 + threadIdx.x; i < row0 + n_own; i += 256) {
+            w += p[(size_t)i * 3 + 1];
+            wg += p[(size_t)i * 3 + 2];
+        }
+    }
+    red[0][threadIdx.x] = sp;
+    red[1][threadIdx.x] = w;
+    red[2][threadIdx.x] = wg;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float t = log_scale[0];
+        const float s = sig_scale(log_scale);
+        loss_out[0] = (float)(red[0][0] * two_over_den);
+        aux[0] = (n_own > 0 && t >= 0.f && t <= LN_100) ? (float)((double)s * red[2][0] * two_over_den) : 0.f;
+        aux[1] = s;
+        aux[2] = n_own > 0 ? (float)(red[1][0] * two_over_den) : 0.f;
+        aux[3] = bias[0];
+    }
+}
+
 // 0 = by size (default): below 2 048 padded rows a product is <= 8 x 8 tiles of the 256 x 256 GEMM -- at the bench's N = 256 ONE
 // tile per directed pair, 255 CUs idle -- and the slab form on 128 x 128 tiles is faster (0.18 vs 0.28 ms at N = 256, 1.35 vs
 // 1.27 at N = 2 048, 8.3 vs 4.5 at N = 8 192: profiles/r02_e_infonce_fused_vs_slab.log).  Up to SLAB_ROWS padded rows (one slab)
@@ -679,6 +829,187 @@ extern "C" int bsclip_infonce_fwd_bwd_ts(const float* const* z, int nmod, const 
     }
     return infonce_run("bsclip_infonce_fwd_bwd_ts", z, nmod, labels, N, D, 0.f, log_scale_dev, scale_out, row0, n_local, loss_out, dz,
                        workspace, stream);
+}
+
+// Sigmoid (SigLIP) loss with a learnable scale and bias (bsclip.h).  The InfoNCE workspace and its prep kernels, products and l2norm
+// backward; of the layout it uses zn / inv / PA / PB / PBt / G / W / dacc, and the row sums ([nu, Np, 3] f64, nu = nmod (nmod - 1) / 2)
+// lie at the head of the dacc region, which pass 2 only writes after the final kernel has read them (as tcontrib above).  Two forms,
+// the same device code per cell: batched (Np <= SLAB_ROWS: every stage one launch over all modalities / pairs, the logits of all
+// directed pairs kept) and slab by slab.  bsclip_infonce_set_impl does not reach here: there is no fused-epilogue form.
+// Pass 1 forms the logits of each unordered pair a < b once for the loss and the scalar gradients.  Pass 2 needs the own rows of
+// every directed pair: dzn^a = sum_b (W^{ab} + (W^{ba})^T) zn^b = 2 sum_b W^{ab} zn^b over the own rows of W^{ab}, and the own
+// rows of W^{ba} are columns of W^{ab} only when the own rows are all rows -- the reverse products are formed, not transposed.
+extern "C" int bsclip_sigmoid_loss_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D,
+                                           const float* log_scale_dev, const float* bias_dev, int row0, int n_local, float* loss_out,
+                                           float* const* dz, float* aux_out, float* workspace, void* stream) {
+    const char* fn = "bsclip_sigmoid_loss_fwd_bwd";
+    // everything is checked before the first launch
+    BSCLIP_REQUIRE(nmod >= 2 && nmod <= 3, "%s: nmod=%d: Too less element for calculating the contrastive loss.", fn, nmod);
+    BSCLIP_REQUIRE(log_scale_dev, "%s: log_scale_dev is null", fn);
+    BSCLIP_REQUIRE(bias_dev, "%s: bias_dev is null", fn);
+    BSCLIP_REQUIRE(aux_out, "%s: aux_out is null", fn);
+    BSCLIP_REQUIRE(aligned_to(4, log_scale_dev, bias_dev, aux_out), "%s: log_scale_dev / bias_dev / aux_out must be 4-B aligned", fn);
+    BSCLIP_REQUIRE(z, "%s: z is null", fn);
+    BSCLIP_REQUIRE(labels, "%s: labels is null", fn);
+    BSCLIP_REQUIRE(loss_out, "%s: loss_out is null", fn);
+    BSCLIP_REQUIRE(workspace, "%s: workspace is null", fn);
+    BSCLIP_REQUIRE(D == 768, "%s: D=%d (supported: 768)", fn, D);
+    BSCLIP_REQUIRE(N > 0 && N <= 16384 && row0 >= 0 && n_local >= 0 && row0 + n_local <= N, "%s: N=%d row0=%d n_local=%d", fn, N,
+                   row0, n_local);
+    BSCLIP_REQUIRE(aligned_to(16, workspace), "%s: workspace must be 16-B aligned", fn);
+    const bool want_dz = dz && n_local > 0;
+    for (int m = 0; m < nmod; ++m) {
+        BSCLIP_REQUIRE(z[m], "%s: z[%d] is null", fn, m);
+        BSCLIP_REQUIRE(aligned_to(16, z[m]), "%s: z[%d] must be 16-B aligned", fn, m);
+        BSCLIP_REQUIRE(!want_dz || dz[m], "%s: dz[%d] is null", fn, m);
+        BSCLIP_REQUIRE(!want_dz || aligned_to(16, dz[m]), "%s: dz[%d] must be 16-B aligned", fn, m);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Layout L = make_layout(N, nmod, D);
+    const int Np = L.Np;
+    float* ws = workspace;
+    float* zn = ws + L.zn;
+    float* inv = ws + L.inv;
+    bf16_t* PA = reinterpret_cast<bf16_t*>(ws + L.PA);
+    bf16_t* PB = reinterpret_cast<bf16_t*>(ws + L.PB);
+    bf16_t* PBt = reinterpret_cast<bf16_t*>(ws + L.PBt);
+    float* G = ws + L.G;
+    bf16_t* W = reinterpret_cast<bf16_t*>(ws + L.W);
+    float* dacc = ws + L.dacc;
+    double* part = reinterpret_cast<double*>(dacc);   // [nu, Np, 3] f64 = 6 nu Np floats of the region's nmod Np D; 16-B aligned
+    const int ndir = nmod * (nmod - 1), nu = ndir / 2;
+    const float den = (float)ndir * (float)N;
+    const double two_over_den = 2.0 / ((double)ndir * (double)N);
+    const size_t opA = (size_t)Np * 3 * D;  // elements per modality in PA / PB
+    const size_t opT = (size_t)D * 3 * Np;  // elements per modality in PBt
+    const int n_own = want_dz ? n_local : 0;   // rows whose shares of dLoss/dt and dLoss/db are reported
+    const bool batched = Np <= SLAB_ROWS && bsclip_gemm_batched_ok(N, Np, 3 * D, BSCLIP_EPI_F32) &&
+                         (!want_dz || (bsclip_gemm_batched_ok(n_local, D, 3 * Np, BSCLIP_EPI_F32) &&
+                                       bsclip_gemm_batched_ok(n_local, D, 3 * Np, BSCLIP_EPI_RESID_F32)));
+    if (batched) {
+        ModPtrs src{};
+        for (int m = 0; m < nmod; ++m) src.z[m] = z[m];
+        hipLaunchKernelGGL(loss_prep_batched_kernel, dim3(ceil_div(Np, 4), nmod), dim3(256), 0, s, src, N, Np, D, zn, inv, PA, PB);
+        if (want_dz)
+            hipLaunchKernelGGL(loss_transpose_split_batched_kernel, dim3(D / 64, Np / 64, nmod), dim3(256), 0, s, zn, Np, D, PBt);
+        BSCLIP_LAUNCH_CHECK();
+
+        // ---- pass 1: one launch forms the logits the call needs -- the unordered pairs for the loss, and with them the reverse
+        // pairs when there is a backward (all N rows: one launch has one M) -- each at its directed-pair slot of G ----
+        const size_t g_stride = (size_t)Np * Np;                 // floats per pair in G
+        const size_t w_stride = (size_t)L.slab * 3 * Np;         // bf16 elements per pair in W
+        bsclip_gemm_batch gl{};
+        int nb = 0;
+        for (int p = 0; p < ndir; ++p) {
+            int a, b;
+            pair_ab(p, nmod, a, b);
+            if (!want_dz && a > b) continue;
+            gl.A[nb] = PA + a * opA;
+            gl.B[nb] = PB + b * opA;
+            gl.C[nb] = G + p * g_stride;
+            ++nb;
+        }
+        int rc = bsclip_gemm_bf16_batched(gl, nb, 3 * D, 3 * D, Np, N, Np, 3 * D, BSCLIP_EPI_F32, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(sig_row_reduce_batched_kernel, dim3(ceil_div(N, 4), nu), dim3(256), 0, s, G, nmod, N, Np, log_scale_dev,
+                           bias_dev, labels, part);
+        hipLaunchKernelGGL(sig_final_kernel, dim3(1), dim3(256), 0, s, part, nu, Np, N, row0, n_own, two_over_den, log_scale_dev,
+                           bias_dev, loss_out, aux_out);
+        BSCLIP_LAUNCH_CHECK();
+        if (!want_dz) return BSCLIP_OK;
+
+        // ---- pass 2: dL/dG of every directed pair from the kept logits, then dzn_a = sum_b W_ab zn_b: the first partner written,
+        // the second added (the association of the slab form) ----
+        long blocks = ((long)n_local * Np + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(sig_w_batched_kernel, dim3((unsigned)blocks, ndir), dim3(256), 0, s, G, N, Np, row0, n_local, log_scale_dev,
+                           bias_dev, den, labels, W, w_stride);
+        for (int k = 0; k < nmod - 1; ++k) {   // k-th partner of every a: pair a * (nmod - 1) + k
+            bsclip_gemm_batch gd{};
+            for (int a = 0; a < nmod; ++a) {
+                const int p = a * (nmod - 1) + k;
+                int pa, b;
+                pair_ab(p, nmod, pa, b);
+                gd.A[a] = W + p * w_stride;
+                gd.B[a] = PBt + b * opT;
+                gd.C[a] = dacc + (size_t)a * Np * D;
+            }
+            rc = bsclip_gemm_bf16_batched(gd, nmod, 3 * Np, 3 * Np, D, n_local, D, 3 * Np,
+                                          k == 0 ? BSCLIP_EPI_F32 : BSCLIP_EPI_RESID_F32, stream);
+            if (rc) return rc;
+        }
+        // Jacobian of the in-loss F.normalize: dz = (g - zn (zn . g)) / ||z||
+        bsclip_l2norm_bwd_batch nbk{};
+        for (int a = 0; a < nmod; ++a) {
+            nbk.y[a] = zn + ((size_t)a * Np + row0) * D;
+            nbk.inv_norm[a] = inv + (size_t)a * Np + row0;
+            nbk.dy[a] = dacc + (size_t)a * Np * D;
+            nbk.dx[a] = dz[a];
+        }
+        rc = bsclip_l2norm_bwd_batched(nbk, nmod, n_local, D, stream);
+        if (rc) return rc;
+        BSCLIP_LAUNCH_CHECK();
+        return BSCLIP_OK;
+    }
+
+    for (int m = 0; m < nmod; ++m) {
+        hipLaunchKernelGGL(loss_prep_kernel, dim3(ceil_div(Np, 4)), dim3(256), 0, s, z[m], N, Np, D, zn + (size_t)m * Np * D,
+                           inv + (size_t)m * Np, PA + m * opA, PB + m * opA);
+        if (want_dz)
+            hipLaunchKernelGGL(loss_transpose_split_kernel, dim3(D / 64, Np / 64), dim3(256), 0, s, zn + (size_t)m * Np * D, Np, D,
+                               PBt + m * opT);
+    }
+    BSCLIP_LAUNCH_CHECK();
+
+    // ---- pass 1: the row sums of every unordered pair, slab by slab ----
+    int u = 0;
+    for (int a = 0; a < nmod; ++a)
+        for (int b = a + 1; b < nmod; ++b, ++u)
+            for (int r0 = 0; r0 < N; r0 += L.slab) {
+                const int nr = N - r0 < L.slab ? N - r0 : L.slab;
+                int rc = bsclip_gemm_bf16(PA + a * opA + (size_t)r0 * 3 * D, 3 * D, PB + b * opA, 3 * D, G, Np, nr, Np, 3 * D,
+                                          BSCLIP_EPI_F32, nullptr, stream);
+                if (rc) return rc;
+                hipLaunchKernelGGL(sig_row_reduce_kernel, dim3(ceil_div(nr, 4)), dim3(256), 0, s, G, r0, nr, N, Np, log_scale_dev,
+                                   bias_dev, labels, part + (size_t)u * Np * 3);
+            }
+    hipLaunchKernelGGL(sig_final_kernel, dim3(1), dim3(256), 0, s, part, nu, Np, N, row0, n_own, two_over_den, log_scale_dev, bias_dev,
+                       loss_out, aux_out);
+    BSCLIP_LAUNCH_CHECK();
+    if (!want_dz) return BSCLIP_OK;
+
+    // ---- pass 2: d loss / d zn_a[rows row0 .. row0+n_local) = sum_b W_ab zn_b ----
+    for (int a = 0; a < nmod; ++a) {
+        float* da = dacc + (size_t)a * Np * D;
+        bool first = true;
+        for (int b = 0; b < nmod; ++b) {
+            if (a == b) continue;
+            for (int l0 = 0; l0 < n_local; l0 += L.slab) {  // row slabs of the rank's own rows
+                const int nr = n_local - l0 < L.slab ? n_local - l0 : L.slab;
+                int rc = bsclip_gemm_bf16(PA + a * opA + (size_t)(row0 + l0) * 3 * D, 3 * D, PB + b * opA, 3 * D, G, Np, nr, Np, 3 * D,
+                                          BSCLIP_EPI_F32, nullptr, stream);
+                if (rc) return rc;
+                long blocks = ((long)nr * Np + 255) / 256;
+                if (blocks > 4096) blocks = 4096;
+                hipLaunchKernelGGL(sig_w_kernel, dim3((unsigned)blocks), dim3(256), 0, s, G, N, Np, row0 + l0, nr, log_scale_dev,
+                                   bias_dev, den, labels, W);
+                float* dar = da + (size_t)l0 * D;
+                bsclip_epi_args ea{};
+                ea.struct_size = sizeof(ea);
+                ea.resid = dar;
+                ea.ld_resid = D;
+                rc = bsclip_gemm_bf16(W, 3 * Np, PBt + b * opT, 3 * Np, dar, D, nr, D, 3 * Np,
+                                      first ? BSCLIP_EPI_F32 : BSCLIP_EPI_RESID_F32, first ? nullptr : &ea, stream);
+                if (rc) return rc;
+            }
+            first = false;
+        }
+        // Jacobian of the in-loss F.normalize: dz = (g - zn (zn . g)) / ||z||
+        int rc = bsclip_l2norm_bwd(zn + ((size_t)a * Np + row0) * D, inv + (size_t)a * Np + row0, da, n_local, D, dz[a], stream);
+        if (rc) return rc;
+    }
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
 }
 
 extern "C" int bsclip_infonce_set_impl(int impl) {

@@ -34,8 +34,8 @@ import torch.optim.lr_scheduler as lr_scheduler  # noqa: E402
 from bioscanclip.epoch.train_epoch import train_epoch  # noqa: E402
 from bioscanclip.hip import dist as hdist  # noqa: E402
 from bioscanclip.hip.optim import FusedAdamW  # noqa: E402
-from bioscanclip.model.loss_func import ContrastiveLoss, GlobalBatchContrastiveLoss  # noqa: E402
-from bioscanclip.model.simple_clip import load_clip_model, trainable_temperature  # noqa: E402
+from bioscanclip.model.loss_func import ContrastiveLoss, GlobalBatchContrastiveLoss, SigmoidContrastiveLoss  # noqa: E402
+from bioscanclip.model.simple_clip import contrastive_loss_kind, load_clip_model, trainable_temperature  # noqa: E402
 from bioscanclip.util.config import load_config  # noqa: E402
 from bioscanclip.util.synthetic import SyntheticCLIPLoader, SyntheticEvalLoader, SyntheticRawLoader  # noqa: E402
 
@@ -247,7 +247,10 @@ def main_process(rank: int, world_size: int, args):
         raise NotImplementedError("the open_clip branch is not part of the HIP-accelerated path")
     # model_config.trainable_temperature: the criterion reads the model's learnable log scale on the device
     logit_scale = model.logit_scale if trainable_temperature(args) else 1 / 0.07
-    if world_size > 1:
+    if contrastive_loss_kind(args) == "sigmoid":
+        # model_config.contrastive_loss=sigmoid: the pairwise sigmoid loss on the model's learnable log scale and bias (one rank)
+        criterion = SigmoidContrastiveLoss(model.logit_scale, model.logit_bias, world_size=world_size)
+    elif world_size > 1:
         criterion = GlobalBatchContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale)
     else:
         criterion = ContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale)
@@ -320,6 +323,9 @@ def main(argv=None):
     print_when_rank_zero(f'world_size: {world_size}', rank)
     if trainable_temperature(args) and world_size > 1:   # GlobalBatchContrastiveLoss would refuse it after the model was built
         raise ValueError(f"model_config.trainable_temperature: a trainable temperature is not built for more than one rank "
+                         f"(world_size={world_size})")
+    if contrastive_loss_kind(args) == "sigmoid" and world_size > 1:   # refused before the model is built
+        raise ValueError(f"model_config.contrastive_loss=sigmoid: the sigmoid loss is not built for more than one rank "
                          f"(world_size={world_size})")
     return main_process(rank, world_size, args)
 

@@ -398,6 +398,34 @@ int bsclip_infonce_fwd_bwd(const float* const* z, int nmod, const int64_t* label
 int bsclip_infonce_fwd_bwd_ts(const float* const* z, int nmod, const int64_t* labels, int N, int D, const float* log_scale_dev,
                               int row0, int n_local, float* loss_out, float* const* dz, float* scale_out, float* workspace,
                               void* stream);
+/* Sigmoid (SigLIP, Zhai et al. ICCV 2023) contrastive loss with a learnable scale and bias, forward + backward in one call.
+ * z: nmod (2 or 3) f32 [N, 768]; zn = F.normalize(z) is applied inside, with its Jacobian in the backward; G^{ab} = zn^a (zn^b)^T.
+ * log_scale_dev, bias_dev: one f32 each on the device (t and b), read when the kernels run and not at launch, so a replayed graph
+ * sees each step's values.  s = exp(min(max(t, 0), ln 100)) as in bsclip_infonce_fwd_bwd_ts (exactly 1 and 100 at and beyond the ends).
+ *   x_ij = s G_ij + b,  y_ij = +1 if label_i == label_j else -1,
+ *   loss = 1/(P N) * sum_{a != b} sum_i sum_j softplus(-y_ij x^{ab}_ij),  P = nmod (nmod - 1)
+ * (directed pairs, so the value compares with the InfoNCE mean; (a,b) and (b,a) hold the same terms, each unordered pair's logits
+ * are formed once for the loss).  softplus and the sigmoid are the stable forms: exp is only taken of -|x|.
+ * row0 / n_local as for bsclip_infonce_fwd_bwd: dz[m] f32 [n_local, 768] holds dLoss/dz^m of the rows [row0, row0 + n_local);
+ * dz NULL or n_local == 0: loss only.  loss_out is the loss over all rows in either case.
+ * aux_out f32 [4], required, written last (it must not alias log_scale_dev or bias_dev), with w_ij = -y_ij sigmoid(-y_ij x_ij):
+ *   aux_out[0] = the own rows' share of dLoss/dt = 2 s/(P N) * sum_{a < b} sum_{i in [row0, row0 + n_local)} sum_j w^{ab}_ij G^{ab}_ij;
+ *                0 when dz is NULL or n_local == 0, and 0 when t lies outside [0, ln 100] (the clamp's derivative)
+ *   aux_out[1] = s
+ *   aux_out[2] = the own rows' share of dLoss/db = 2/(P N) * sum_{a < b} sum_{i in own rows} sum_j w^{ab}_ij; 0 when dz is NULL or n_local == 0
+ *   aux_out[3] = b
+ * A row's share holds the cells (i, j) of G^{ab}, a < b, and their mirror cells (j, i) of G^{ba}; the shares of disjoint row slices
+ * add up to the whole gradient, which is what a SUM all-reduce needs.
+ * workspace: bsclip_infonce_workspace_floats(N, nmod) floats, 16-B aligned.  Of the InfoNCE layout the call uses the normalised
+ * rows, the split operands, the logits (G) and dL/dG (W) regions and the gradient accumulator; the per-row sums of pass 1
+ * (f64 [nmod (nmod - 1) / 2, Np, 3]) lie at the head of the gradient accumulator, which pass 2 writes after they were read.
+ * Two forms by size, as for InfoNCE: up to 1024 padded rows one launch per stage over all pairs, above that 1024-row slabs launch
+ * by launch.  There is no fused-epilogue form: bsclip_infonce_set_impl has no effect here.
+ * No atomics, sums in f64 in a fixed order: a repeated call returns the same bits.  D = 768, N <= 16384; every argument is
+ * checked before the first launch; -1 names the bad one. */
+int bsclip_sigmoid_loss_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, const float* log_scale_dev,
+                                const float* bias_dev, int row0, int n_local, float* loss_out, float* const* dz, float* aux_out,
+                                float* workspace, void* stream);
 
 /* ---- retrieval --------------------------------------------------------------------------------
  * make_prediction (scripts/inference_and_eval.py:414-445): faiss IndexFlatIP over L2-normalised keys f32 [K, D], searched
