@@ -150,6 +150,8 @@ def train_epoch(activate_wandb, total_epochs, epoch, dataloader, model, optimize
         line += f", logit scale: {criterion.current_scale().item():.6f}"
     if torch.is_tensor(getattr(criterion, "logit_bias", None)):    # the sigmoid loss's learnable bias, read back with the scale
         line += f", logit bias: {criterion.current_bias().item():.6f}"
+    if hasattr(criterion, "memory_bank_size"):                     # cross-batch memory: the valid slots, one read-back per epoch
+        line += f", memory bank: {int(criterion.filled().item())}/{criterion.memory_bank_size}"
     if getattr(optimizer, "grad_clip_enabled", lambda: False)():    # FusedAdamW's norm record: one read-back per epoch, then reset
         gs = optimizer.grad_stats(reset=True)
         line += (f", grad norm: mean {gs['norm_mean']:.6g} max {gs['norm_max']:.6g}, clipped {gs['clipped']}/{gs['steps']}, "

@@ -125,6 +125,75 @@ def infonce(zs, labels, scale, row0=0, n_local=None):
     return _InfoNCE.apply(labels.to(torch.int64).contiguous(), float(scale), row0, n_local, ws, *[z.to(F32) for z in zs])
 
 
+class MemoryBank:
+    """The device state of a cross-batch memory: one f32 bank per modality (``ops.xbm_bank_floats(Q)`` elements; the first
+    Q * 768 are the normalised rows by slot), the slots' labels (int64 [Q]) and ``state`` = (head, filled) as int32 [2].  Plain
+    references: the owner (``MemoryBankContrastiveLoss``) allocates them and keeps them alive."""
+
+    def __init__(self, banks, labels, state):
+        self.banks, self.labels, self.state = list(banks), labels, state
+        self.Q = labels.numel()
+        self._ws = {}
+
+    def workspace(self, N, nmod):
+        """The workspace of the loss and enqueue calls at batch size N, kept per shape for the bank's lifetime: a captured step holds
+        a pointer into it."""
+        ws = self._ws.get((N, nmod))
+        if ws is None:
+            ws = self._ws[(N, nmod)] = torch.empty(ops.xbm_workspace_floats(N, self.Q, nmod), dtype=F32, device=self.labels.device)
+        return ws
+
+    def rows(self, m):
+        """The documented f32 rows of modality ``m`` as a [Q, 768] view."""
+        return self.banks[m][:self.Q * 768].view(self.Q, 768)
+
+
+class _InfoNCEXbm(torch.autograd.Function):
+    """InfoNCE with the valid slots of a cross-batch memory as extra key columns (``bsclip_infonce_xbm_fwd_bwd``).  ``log_scale``
+    is t = log(scale), one f32 on the GPU; the bank takes no gradient; dLoss/dt comes out of the same call in ``scale_out``."""
+
+    @staticmethod
+    def forward(ctx, labels, log_scale, bank, workspace, scale_out, *zs):
+        zs = [z.contiguous() for z in zs]
+        loss = torch.zeros(1, dtype=F32, device=zs[0].device)
+        need_grad = ctx.needs_input_grad[1] or any(ctx.needs_input_grad[5:])
+        dzs = [torch.empty_like(z) for z in zs] if need_grad else None
+        ops.infonce_xbm(zs, labels, log_scale, bank.banks, bank.labels, bank.state, loss, dzs, scale_out, workspace)
+        ctx.dzs, ctx.scale_out, ctx.t_shape = dzs, scale_out, log_scale.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        outs = [d * g if ctx.needs_input_grad[5 + i] else None for i, d in enumerate(ctx.dzs)]
+        dt = (ctx.scale_out[0] * g).reshape(ctx.t_shape) if ctx.needs_input_grad[1] else None
+        return (None, dt, None, None, None) + tuple(outs)
+
+
+def infonce_xbm(zs, labels, log_scale, bank):
+    """The InfoNCE of ``infonce`` over the current batch AND the valid slots of ``bank`` (a ``MemoryBank``), read as it stands:
+    nothing is enqueued here.  ``log_scale`` is a 1-element f32 CUDA tensor holding t = log(scale) -- the model's parameter when the
+    temperature is learnable (it then receives dLoss/dt), a plain device word otherwise.  The returned loss carries ``scale_out`` =
+    (dLoss/dt, the scale used)."""
+    if len(zs) < 2:
+        raise ValueError("Too less element for calculating the contrastive loss.")
+    if not zs[0].is_cuda:
+        raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
+    if not (torch.is_tensor(log_scale) and log_scale.is_cuda and log_scale.dtype == F32 and log_scale.numel() == 1):
+        raise ValueError("infonce_xbm: log_scale is the log scale, a 1-element f32 CUDA tensor")
+    ws = bank.workspace(zs[0].shape[0], len(zs))
+    scale_out = torch.empty(2, dtype=F32, device=zs[0].device)
+    loss = _InfoNCEXbm.apply(labels.to(torch.int64).contiguous(), log_scale, bank, ws, scale_out, *[z.to(F32) for z in zs])
+    loss.scale_out = scale_out
+    return loss
+
+
+def xbm_enqueue(zs, labels, bank):
+    """Write the (detached) rows of ``zs`` and their labels into ``bank`` and advance its ring, all on the device."""
+    zs = [z.detach().to(F32).contiguous() for z in zs]
+    ws = bank.workspace(zs[0].shape[0], len(zs))
+    ops.xbm_enqueue(zs, labels.to(torch.int64).contiguous(), bank.banks, bank.labels, bank.state, ws)
+
+
 class _SigmoidLoss(torch.autograd.Function):
     """The sigmoid (SigLIP) loss with a learnable scale and bias (``bsclip_sigmoid_loss_fwd_bwd``): ``log_scale`` (t) and ``bias``
     (b) are one f32 each on the GPU, read by the kernels when they run.  One call leaves the loss, dLoss/dz and, in ``aux_out``,

@@ -97,6 +97,10 @@ SIGNATURES = {
     "bsclip_infonce_fwd_bwd": (I, [POINTER(c_void_p), I, P, I, I, F, I, I, P, POINTER(c_void_p), P, P]),
     "bsclip_infonce_fwd_bwd_ts": (I, [POINTER(c_void_p), I, P, I, I, P, I, I, P, POINTER(c_void_p), P, P, P]),
     "bsclip_sigmoid_loss_fwd_bwd": (I, [POINTER(c_void_p), I, P, I, I, P, P, I, I, P, POINTER(c_void_p), P, P, P]),
+    "bsclip_xbm_bank_floats": (L, [I]),
+    "bsclip_xbm_workspace_floats": (L, [I, I, I]),
+    "bsclip_xbm_enqueue": (I, [POINTER(c_void_p), I, P, I, I, POINTER(c_void_p), P, I, P, P, P]),
+    "bsclip_infonce_xbm_fwd_bwd": (I, [POINTER(c_void_p), I, P, I, I, P, POINTER(c_void_p), P, I, P, P, POINTER(c_void_p), P, P, P]),
     "bsclip_topk_ip_workspace_floats": (L, [I, I, I]),
     "bsclip_topk_ip": (I, [P, I, P, I, I, I, P, P, P, P]),
     "bsclip_retrieval_index_floats": (L, [I, I]),

@@ -678,6 +678,70 @@ def sigmoid_loss_fwd_bwd(zs, labels, log_scale, bias, loss_out, dzs, aux_out, ro
                                                 _p(aux_out), _p(workspace), _stream()))
 
 
+
+def xbm_bank_floats(Q):
+    n = _l.load().bsclip_xbm_bank_floats(int(Q))
+    if n < 0:
+        raise ValueError(f"xbm: Q={Q} must be a multiple of 256 in 256 .. 16384")
+    return n
+
+
+def xbm_workspace_floats(N, Q, nmod):
+    n = _l.load().bsclip_xbm_workspace_floats(int(N), int(Q), int(nmod))
+    if n < 0:
+        raise ValueError(f"xbm: bad N={N} (1 .. 1024, <= Q) / Q={Q} (a multiple of 256 in 256 .. 16384) / nmod={nmod} (2 or 3)")
+    return n
+
+
+def _xbm_args(zs, labels, banks, bank_labels, state, workspace, name):
+    """The checks ``xbm_enqueue`` and ``infonce_xbm`` share; returns (nmod, N, D, Q, zp, bp)."""
+    nmod = len(zs)
+    if nmod < 2:
+        raise ValueError("Too less element for calculating the contrastive loss.")
+    N, D = zs[0].shape
+    dev = zs[0].device
+    _req(all(z.is_cuda and z.dtype == F32 and z.is_contiguous() and tuple(z.shape) == (N, D) for z in zs), f"{name}: zs f32 [N,D] on the GPU")
+    _req(labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == N and labels.device == dev, f"{name}: labels int64 [N]")
+    _req(bank_labels.dtype == torch.int64 and bank_labels.is_contiguous() and bank_labels.dim() == 1 and bank_labels.device == dev,
+         f"{name}: bank_labels int64 [Q]")
+    Q = bank_labels.numel()
+    need = xbm_bank_floats(Q)
+    _req(len(banks) == nmod and all(b.dtype == F32 and b.is_contiguous() and b.numel() >= need and b.device == dev for b in banks),
+         f"{name}: one contiguous f32 bank of >= {need} elements per modality")
+    _i32(state, dev, f"{name}: state must be a contiguous int32 [2] tensor on the inputs' GPU", shape=(2,))
+    need = xbm_workspace_floats(N, Q, nmod)
+    _req(workspace is not None and workspace.dtype == F32 and workspace.numel() >= need and workspace.is_contiguous()
+         and workspace.device == dev, f"{name}: workspace must be f32 with >= {need} elements")
+    zp = (ctypes.c_void_p * nmod)(*[z.data_ptr() for z in zs])
+    bp = (ctypes.c_void_p * nmod)(*[b.data_ptr() for b in banks])
+    return nmod, N, D, Q, zp, bp
+
+
+def xbm_enqueue(zs, labels, banks, bank_labels, state, workspace):
+    """Write the normalised rows of ``zs`` (2-3 f32 [N, 768]) and ``labels`` into the ring at ``state`` = (head, filled), int32 [2] on
+    the GPU, and advance it there; nothing is written when a row holds a non-finite value (``bsclip_xbm_enqueue``)."""
+    nmod, N, D, Q, zp, bp = _xbm_args(zs, labels, banks, bank_labels, state, workspace, "xbm_enqueue")
+    check(_l.load().bsclip_xbm_enqueue(zp, nmod, _p(labels), N, D, bp, _p(bank_labels), Q, _p(state), _p(workspace), _stream()))
+
+
+def infonce_xbm(zs, labels, log_scale, banks, bank_labels, state, loss_out, dzs, scale_out, workspace):
+    """InfoNCE with the valid bank slots as extra keys (``bsclip_infonce_xbm_fwd_bwd``): ``log_scale`` is t = log(scale), one f32 on
+    the GPU; ``scale_out`` f32 [2] receives (dLoss/dt, the scale used); ``dzs`` f32 [N, 768] per modality, or None for the loss only."""
+    _req(torch.is_tensor(log_scale) and log_scale.is_cuda and log_scale.dtype == F32 and log_scale.numel() == 1,
+         "log_scale must be a 1-element f32 CUDA tensor")
+    _req(torch.is_tensor(scale_out) and scale_out.is_cuda and scale_out.dtype == F32 and scale_out.is_contiguous()
+         and scale_out.numel() >= 2, "scale_out must be a contiguous f32 CUDA tensor with >= 2 elements")
+    nmod, N, D, Q, zp, bp = _xbm_args(zs, labels, banks, bank_labels, state, workspace, "infonce_xbm")
+    _req(loss_out.dtype == F32 and loss_out.is_cuda and loss_out.numel() >= 1, "loss_out f32 [1]")
+    dzp = None
+    if dzs is not None:
+        _req(len(dzs) == nmod and all(d.dtype == F32 and d.is_contiguous() and d.is_cuda and tuple(d.shape) == (N, D) for d in dzs),
+             "dzs f32 [N, D]")
+        dzp = (ctypes.c_void_p * nmod)(*[d.data_ptr() for d in dzs])
+    check(_l.load().bsclip_infonce_xbm_fwd_bwd(zp, nmod, _p(labels), N, D, _p(log_scale), bp, _p(bank_labels), Q, _p(state),
+                                               _p(loss_out), dzp, _p(scale_out), _p(workspace), _stream()))
+
+
 def _topk_outputs(queries, K, k, msg_q, msg_k):
     """What ``topk_ip`` and ``topk_ip_indexed`` share: the query check and the outputs.  Returns (Q, D, scores, idx)."""
     _req(queries.dim() == 2 and queries.dtype == F32 and queries.is_contiguous() and queries.is_cuda, msg_q)

@@ -8,11 +8,16 @@ learnable: an ``nn.Parameter`` holding t = log(scale), which the kernels read on
 
 ``SigmoidContrastiveLoss`` is a second criterion with the same call signature: the pairwise sigmoid loss of SigLIP on a learnable
 scale and bias (``bsclip_sigmoid_loss_fwd_bwd``, ``model_config.contrastive_loss: sigmoid``).
+
+``MemoryBankContrastiveLoss`` is ``ContrastiveLoss`` with a cross-batch memory (``model_config.memory_bank_size``): the embeddings of
+the last steps stay on the GPU and enter the InfoNCE as extra key columns without gradient (``bsclip_infonce_xbm_fwd_bwd``).
 """
+import math
+
 import torch
 import torch.nn as nn
 
-from bioscanclip.hip.functional import infonce, sigmoid_loss
+from bioscanclip.hip.functional import MemoryBank, infonce, infonce_xbm, sigmoid_loss, xbm_enqueue
 
 
 def construct_label_metrix(labels):
@@ -100,6 +105,88 @@ class SigmoidContrastiveLoss(nn.Module):
             raise ValueError("Too less element for calculating the contrastive loss.")
         loss = sigmoid_loss(feature_list, label, self.logit_scale, self.logit_bias)
         self._aux_out = loss.aux_out
+        return loss
+
+
+def check_memory_bank_size(Q, batch_size=None):
+    """``model_config.memory_bank_size`` as an int, or ValueError: a multiple of 256 in [256, 16384], at least the batch size."""
+    if isinstance(Q, bool) or not isinstance(Q, int):
+        raise ValueError(f"memory_bank_size={Q!r}: an integer number of slots")
+    if Q % 256 != 0 or not 256 <= Q <= 16384:
+        raise ValueError(f"memory_bank_size={Q}: a multiple of 256 in 256 .. 16384")
+    if batch_size is not None and Q < batch_size:
+        raise ValueError(f"memory_bank_size={Q} is smaller than the batch size {batch_size}: a step's rows must fit the ring")
+    return Q
+
+
+class MemoryBankContrastiveLoss(ContrastiveLoss):
+    """``ContrastiveLoss`` over the current batch and a cross-batch memory (XBM, Wang et al., CVPR 2020): the normalised embeddings
+    of the last steps, ``memory_bank_size`` slots per modality in a ring on the GPU, are extra key columns of every ordered pair's
+    logits and take no gradient.  In train mode a forward computes the loss on the bank as it stands and THEN enqueues the detached
+    current embeddings, so a sample never meets its own copy in the step that wrote it; in eval mode it reads the bank and enqueues
+    nothing.  Ring position and fill count live on the device and every launch reads them there, so the step can be captured.
+
+    The banks, their labels and the state are non-persistent buffers, allocated on first use for the modalities present: they are
+    in no state dict and no checkpoint, and a restarted run refills the bank in memory_bank_size / batch steps.  ``logit_scale``
+    is a float or the model's learnable ``nn.Parameter`` (t = log scale).  One rank only: ``world_size`` is the process group's
+    size when not given."""
+
+    def __init__(self, criterion=None, logit_scale=1 / 0.07, memory_bank_size=4096, world_size=None):
+        if world_size is None:
+            import torch.distributed as dist
+            world_size = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if world_size > 1:
+            raise ValueError(f"MemoryBankContrastiveLoss: the cross-batch memory is not built for more than one rank (world_size={world_size})")
+        super().__init__(criterion, logit_scale)
+        self.memory_bank_size = check_memory_bank_size(memory_bank_size)
+        self._bank = None
+        self._present = None
+
+    def _allocate(self, present, device):
+        from bioscanclip.hip import ops
+        Q = self.memory_bank_size
+        n = ops.xbm_bank_floats(Q)
+        for name in present:
+            self.register_buffer(f"bank_{name}", torch.zeros(n, dtype=torch.float32, device=device), persistent=False)
+        self.register_buffer("bank_labels", torch.zeros(Q, dtype=torch.int64, device=device), persistent=False)
+        self.register_buffer("bank_state", torch.zeros(2, dtype=torch.int32, device=device), persistent=False)   # (head, filled)
+        if not torch.is_tensor(self.logit_scale):   # the fixed temperature as the device word the kernels read
+            self.register_buffer("log_scale_word", torch.tensor([math.log(float(self.logit_scale))], dtype=torch.float32, device=device),
+                                 persistent=False)
+        self._bank = MemoryBank([getattr(self, f"bank_{name}") for name in present], self.bank_labels, self.bank_state)
+        self._present = present
+
+    def bank(self):
+        """The ``MemoryBank`` (None before the first forward)."""
+        return self._bank
+
+    def reset(self):
+        """Empty the bank: head = filled = 0 (the slots' contents stop mattering)."""
+        if self._bank is not None:
+            self.bank_state.zero_()
+
+    def filled(self):
+        """The number of valid slots as a device scalar (no host synchronisation)."""
+        if self._bank is None:
+            return torch.zeros((), dtype=torch.int32)
+        return self.bank_state[1]
+
+    def forward(self, image_features, dna_features, text_features, label, logit_scale=1 / 0.07):
+        named = [(n, f) for n, f in (("image", image_features), ("dna", dna_features), ("text", text_features)) if f is not None]
+        if len(named) < 2:
+            raise ValueError("Too less element for calculating the contrastive loss.")
+        present, feats = tuple(n for n, _ in named), [f for _, f in named]
+        if not feats[0].is_cuda:
+            raise RuntimeError("bioscanclip: tensors must live on the GPU (no CPU compute path)")
+        if self._bank is None:
+            self._allocate(present, feats[0].device)
+        elif present != self._present:
+            raise ValueError(f"MemoryBankContrastiveLoss: the bank holds {self._present}, this batch has {present}")
+        t = self.logit_scale if torch.is_tensor(self.logit_scale) else self.log_scale_word
+        loss = infonce_xbm(feats, label, t, self._bank)
+        self._scale_out = loss.scale_out
+        if self.training:
+            xbm_enqueue(feats, label, self._bank)
         return loss
 
 

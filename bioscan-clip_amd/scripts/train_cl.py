@@ -34,7 +34,8 @@ import torch.optim.lr_scheduler as lr_scheduler  # noqa: E402
 from bioscanclip.epoch.train_epoch import train_epoch  # noqa: E402
 from bioscanclip.hip import dist as hdist  # noqa: E402
 from bioscanclip.hip.optim import FusedAdamW  # noqa: E402
-from bioscanclip.model.loss_func import ContrastiveLoss, GlobalBatchContrastiveLoss, SigmoidContrastiveLoss  # noqa: E402
+from bioscanclip.model.loss_func import (ContrastiveLoss, GlobalBatchContrastiveLoss, MemoryBankContrastiveLoss,  # noqa: E402
+                                          SigmoidContrastiveLoss)
 from bioscanclip.model.simple_clip import contrastive_loss_kind, load_clip_model, trainable_temperature  # noqa: E402
 from bioscanclip.util.config import load_config  # noqa: E402
 from bioscanclip.util.synthetic import SyntheticCLIPLoader, SyntheticEvalLoader, SyntheticRawLoader  # noqa: E402
@@ -189,6 +190,23 @@ def grad_clip_options(args):
     return norm, True
 
 
+def memory_bank_size(args, world_size=1):
+    """``model_config.memory_bank_size``: the slots per modality of the cross-batch memory (``MemoryBankContrastiveLoss``), or None
+    when the key is absent (off).  A multiple of 256 in 256 .. 16384 and at least the batch size; refused together with
+    ``contrastive_loss=sigmoid`` and with more than one rank."""
+    mc = args.model_config
+    if not hasattr(mc, "memory_bank_size") or mc.memory_bank_size is None:
+        return None
+    from bioscanclip.model.loss_func import check_memory_bank_size
+    Q = check_memory_bank_size(mc.memory_bank_size, int(mc.batch_size))
+    if contrastive_loss_kind(args) == "sigmoid":
+        raise ValueError("model_config.memory_bank_size: the cross-batch memory is built for the InfoNCE, not for contrastive_loss=sigmoid")
+    if world_size > 1:
+        raise ValueError(f"model_config.memory_bank_size: the cross-batch memory is not built for more than one rank "
+                         f"(world_size={world_size})")
+    return Q
+
+
 def main_process(rank: int, world_size: int, args):
     towers16 = fp16_towers(args)
     max_grad_norm, skip_nonfinite = grad_clip_options(args)
@@ -250,6 +268,10 @@ def main_process(rank: int, world_size: int, args):
     if contrastive_loss_kind(args) == "sigmoid":
         # model_config.contrastive_loss=sigmoid: the pairwise sigmoid loss on the model's learnable log scale and bias (one rank)
         criterion = SigmoidContrastiveLoss(model.logit_scale, model.logit_bias, world_size=world_size)
+    elif memory_bank_size(args, world_size) is not None:
+        # model_config.memory_bank_size: the last steps' embeddings as extra keys without gradient (one rank; not checkpointed)
+        criterion = MemoryBankContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale,
+                                              memory_bank_size=memory_bank_size(args, world_size), world_size=world_size)
     elif world_size > 1:
         criterion = GlobalBatchContrastiveLoss(criterion=nn.CrossEntropyLoss(), logit_scale=logit_scale)
     else:
@@ -327,6 +349,7 @@ def main(argv=None):
     if contrastive_loss_kind(args) == "sigmoid" and world_size > 1:   # refused before the model is built
         raise ValueError(f"model_config.contrastive_loss=sigmoid: the sigmoid loss is not built for more than one rank "
                          f"(world_size={world_size})")
+    memory_bank_size(args, world_size)   # refused before the model is built
     return main_process(rank, world_size, args)
 
 

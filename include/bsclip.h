@@ -426,6 +426,47 @@ int bsclip_infonce_fwd_bwd_ts(const float* const* z, int nmod, const int64_t* la
 int bsclip_sigmoid_loss_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, const float* log_scale_dev,
                                 const float* bias_dev, int row0, int n_local, float* loss_out, float* const* dz, float* aux_out,
                                 float* workspace, void* stream);
+/* Cross-batch memory (XBM, Wang et al. CVPR 2020) for the InfoNCE: the normalised embeddings of the last steps stay on the GPU in
+ * one ring buffer per modality and enter the loss as extra key columns that take no gradient.  One rank only.
+ * bank[m]: f32, bsclip_xbm_bank_floats(Q) elements, 16-B aligned, one per modality.  Its first Q * 768 floats are the normalised
+ * f32 rows by slot (row j at [768 j, 768 j + 768)); what follows belongs to the implementation (each row's split-bf16 operands,
+ * row-major and transposed, written once at enqueue so that a step never re-splits the bank) and only these calls touch it.
+ * bank_labels: int64 [Q], the label of each slot, shared by the modalities.
+ * state_dev: int32 [2] on the device = (head, filled): head is the slot the next enqueue writes first, slot j is valid iff
+ * j < filled.  Both words are read, and by bsclip_xbm_enqueue written, when the kernels run and not at launch, so a replayed graph
+ * advances the ring.  An empty bank is state_dev = (0, 0); the contents of slots that are not valid never matter.
+ * Limits of both calls: D = 768, nmod 2 or 3, 1 <= N <= 1024, Q a multiple of 256 in [256, 16384], N <= Q, 16-byte aligned z[m],
+ * bank[m], dz[m] and workspace.  Every argument is checked before the first launch; -1 names the bad one.
+ * workspace: f32, bsclip_xbm_workspace_floats(N, Q, nmod) elements; the two calls may share it. */
+int64_t bsclip_xbm_bank_floats(int Q);
+int64_t bsclip_xbm_workspace_floats(int N, int Q, int nmod);
+/* Row i of every z[m] (f32 [N, 768]) is normalised (z / max(||z||, 1e-12)) and written to slot (head + i) % Q of bank[m], with
+ * labels[i] to bank_labels; then head = (head + N) % Q and filled = min(filled + N, Q), from a launch of its own that is
+ * stream-ordered after the row writes.  If any of the nmod * N input rows holds a non-finite value the whole call leaves the
+ * banks, the labels and the state untouched: per-row flags, reduced by one workgroup in a fixed order, predicate the writers
+ * (one overflowed step would otherwise poison the next Q / N steps).  5 launches. */
+int bsclip_xbm_enqueue(const float* const* z, int nmod, const int64_t* labels, int N, int D, float* const* bank, int64_t* bank_labels,
+                       int Q, int32_t* state_dev, float* workspace, void* stream);
+/* InfoNCE with the valid bank slots as extra keys, forward + backward in one call.  For every ordered pair (a, b), a != b, the key
+ * set C of b is its N own rows followed by the valid slots of bank[b]:
+ *   x_ij = s <zn^a_i, k^b_j>,  T_ij = [labels_i == label of key j],  cnt_i = sum_{j in C} T_ij
+ *   loss = 1/(P N) sum_{a != b} sum_i ( cnt_i logsumexp_{j in C} x_ij - sum_{j in C} T_ij x_ij ),  P = nmod (nmod - 1)
+ * s = exp(min(max(t, 0), ln 100)) with t = *log_scale_dev read on the device, as in bsclip_infonce_fwd_bwd_ts (a fixed temperature
+ * passes ln(scale) in a device word).  With filled = 0 this is bsclip_infonce_fwd_bwd_ts's loss.  Slots >= filled are selected out
+ * of the log-sum-exp, of T and of cnt (their contents may be anything, NaN included); the call zeroes the implementation's
+ * transposed operand of those slots in bank[m], the documented rows and bank_labels are only read.
+ * dz[m] f32 [N, 768] (dz NULL: loss only): dLoss/dz^m -- the row role of m in every (m, b) through own and bank columns, the column
+ * role in every (b, m) through its own N columns; bank rows take no gradient.
+ * scale_out f32 [2]: scale_out[1] = s; scale_out[0] = dLoss/dt = s/(P N) sum_{a != b} sum_i sum_{j in C} (cnt_i p_ij - T_ij) G_ij
+ * (G the cosines, p the softmax over C), 0 when dz is NULL or t lies outside [0, ln 100].
+ * No atomics: row statistics in f64 partials per row, one workgroup sums them, the long key reduction of dz runs as a split over
+ * the keys whose partial tiles are added in a fixed order; a repeated call returns the same bits.
+ * Launches with gradients: 8 + nmod + 2 R with R runs of stacked queries in the split over the keys (R = 2 at nmod = 2, 4 at
+ * nmod = 3): 14 and 19 wherever the products of one stage go as one batched launch over the pairs (every N <= 1024 except bank
+ * logits of ceil(N / 256) * Q / 256 >= 192 tiles, which go pair by pair). */
+int bsclip_infonce_xbm_fwd_bwd(const float* const* z, int nmod, const int64_t* labels, int N, int D, const float* log_scale_dev,
+                               float* const* bank, const int64_t* bank_labels, int Q, const int32_t* state_dev, float* loss_out,
+                               float* const* dz, float* scale_out, float* workspace, void* stream);
 
 /* ---- retrieval --------------------------------------------------------------------------------
  * make_prediction (scripts/inference_and_eval.py:414-445): faiss IndexFlatIP over L2-normalised keys f32 [K, D], searched
