@@ -190,7 +190,9 @@ __global__ __launch_bounds__(256) void cast_f32_f16_scaled_kernel(const float* _
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = (n4 << 2) + threadIdx.x;
-        out[i] = f2h<true>(in[i] * scale);
+        float v = in[i] * scale;
+        asm volatile("" : "+v"(v));   // keep product and conversion apart: fused into v_fma_mixlo_f16 (x, scale, +0) they turn -0 into +0
+        out[i] = f2h<true>(v);
     }
 }
 
