@@ -19,6 +19,9 @@ all-gather and all-reduce issued eagerly from that tower's stream between them (
 Gradient clipping / skipping (``FusedAdamW.set_grad_clip``) lives inside ``optimizer.step()`` on the device: the loop
 never learns whether a step was skipped, so ``scheduler.step()`` advances on a skipped step too (as it does beside
 ``torch.cuda.amp.GradScaler``), and the epoch line reports the norm statistics from one ``grad_stats(reset=True)`` read-back.
+
+The weight average (``FusedAdamW.set_ema``) lives inside the same update launch; the epoch line reports the decay it
+has reached (``ema_effective_decay()``: with skipping on, one read-back of the device's applied-step count).
 """
 import os
 import time
@@ -156,5 +159,7 @@ def train_epoch(activate_wandb, total_epochs, epoch, dataloader, model, optimize
         gs = optimizer.grad_stats(reset=True)
         line += (f", grad norm: mean {gs['norm_mean']:.6g} max {gs['norm_max']:.6g}, clipped {gs['clipped']}/{gs['steps']}, "
                  f"skipped {gs['skipped']}/{gs['steps']}")
+    if getattr(optimizer, "ema_enabled", lambda: False)():          # the weight average's decay at the applied-step count reached
+        line += f", ema decay: {optimizer.ema_effective_decay():.6f}"
     print(line)
     return mean_loss

@@ -161,6 +161,8 @@ SIGNATURES = {
     "bsclip_grad_clip_finish": (I, [P, L, F, P, P]),
     "bsclip_counter_add_if": (I, [P, U, P, P]),
     "bsclip_adamw_step_clip": (I, [P, P, P, P, L, P, P, F, F, F, F, P]),
+    "bsclip_adamw_step_ema": (I, [P, P, P, P, P, L, P, P, F, F, F, F, F, I, P]),
+    "bsclip_swap_f32": (I, [P, P, L, P]),
     "bsclip_set_dropout_step": (I, [P]),
     "bsclip_counter_add": (I, [P, U, P]),
     "bsclip_count_nonfinite": (I, [P, L, I, P, P]),

@@ -1230,6 +1230,37 @@ def adamw_step_clip(p, g, m, v, hyper, state, beta1, beta2, eps, weight_decay):
                                            float(eps), float(weight_decay), _stream()))
 
 
+def _overlap(a, b):
+    """True when the two contiguous tensors share a byte."""
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def adamw_step_ema(p, g, m, v, ema, hyper, state, beta1, beta2, eps, weight_decay, ema_decay, ema_warmup):
+    """``adamw_step_dev`` (``state`` None) or ``adamw_step_clip`` (``state`` the record of ``grad_clip_finish``) that also moves the
+    weight average: ``ema += w * (p_new - ema)`` with ``w = 1 - d_t`` formed on the device from the step word of ``hyper`` (DESIGN.md
+    4h).  Nothing is written, ``ema`` included, when the record says skip."""
+    _adamw_flat_ok(p, g, m, v)
+    _req(ema.dtype == F32 and ema.is_contiguous() and ema.numel() == p.numel(), "adamw_step_ema: ema must be a flat f32 buffer of p's size")
+    _req(not any(_overlap(ema, t) for t in (p, g, m, v)), "adamw_step_ema: ema must not alias p, g, m or v")
+    _adamw_hyper_ok(hyper)
+    if state is not None:
+        _grad_clip_state_ok(state, "adamw_step_ema")
+    _req(0.0 < float(ema_decay) < 1.0, f"adamw_step_ema: ema_decay={ema_decay} must lie strictly inside (0, 1)")
+    check(_l.load().bsclip_adamw_step_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(state), float(beta1),
+                                          float(beta2), float(eps), float(weight_decay), float(ema_decay), int(bool(ema_warmup)),
+                                          _stream()))
+
+
+def swap_f32(a, b):
+    """a[i] <-> b[i]: two contiguous f32 buffers of one size that share no byte."""
+    _req(a.dtype == F32 and b.dtype == F32, "swap_f32: f32 buffers")
+    _req(a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() and a.numel() > 0,
+         "swap_f32: contiguous buffers of the same non-zero size")
+    _req(not _overlap(a, b), "swap_f32: a and b must not be the same or overlapping buffers")
+    check(_l.load().bsclip_swap_f32(_p(a), _p(b), a.numel(), _stream()))
+
+
 def set_dropout_step(counter):
     """Every dropout-carrying launch this thread makes from now on mixes the device word ``counter`` (uint32/int32 [1]) into
     its seed at run time (None: seeds are used as passed)."""

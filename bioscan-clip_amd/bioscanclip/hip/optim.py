@@ -1,6 +1,8 @@
 """Fused AdamW over the engines' flat trainable buffers (reference: ``optim.AdamW(model.parameters(), lr)`` at
 scripts/train_cl.py:158 -- torch defaults betas (0.9, 0.999), eps 1e-8, weight_decay 0.01, applied to LoRA and head
 weights *and biases*; frozen parameters have no gradient and are skipped)."""
+import contextlib
+
 import torch
 
 from . import ops
@@ -14,9 +16,15 @@ class FusedAdamW(torch.optim.Optimizer):
     ``max_grad_norm`` / ``skip_nonfinite`` (``set_grad_clip``), both off by default: the global L2 norm of all flat
     gradients is formed on the device, the update runs on ``g * min(1, max_grad_norm / (norm + 1e-6))``
     (``torch.nn.utils.clip_grad_norm_``) and a step whose norm is not finite changes nothing -- parameters, moments and the step
-    count stay (``GradScaler.step``).  No host read-back: eager and captured steps issue the same launches."""
+    count stay (``GradScaler.step``).  No host read-back: eager and captured steps issue the same launches.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=False):
+    ``ema_decay`` / ``ema_warmup`` (``set_ema``), off by default: an exponential moving average of the weights (timm's
+    ``ModelEmaV2`` / ``V3``), one f32 buffer per flat buffer, moved inside the update launch (``bsclip_adamw_step_ema``) by the thread
+    that stored the new weight; it follows the applied-step count, so a skipped step leaves it alone.  ``ema_weights()`` swaps it with
+    the parameters in place for an evaluation or a checkpoint."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=True):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._flat_state = {}
@@ -27,7 +35,80 @@ class FusedAdamW(torch.optim.Optimizer):
         self._max_norm = float("inf")
         self._clip_state = None       # int32 [12]: the device record of bsclip_grad_clip_finish
         self._clip_partials = None    # f64: every flat buffer's partial sums, one slice behind the other
+        self._ema_decay = None        # None: no weight average
+        self._ema_warmup = True
+        self._ema_swapped = False     # inside ema_weights(): the flat buffers hold the average, st["ema"] the raw weights
         self.set_grad_clip(max_grad_norm, skip_nonfinite)
+        self.set_ema(ema_decay, ema_warmup)
+
+    _EMA_SHARDED = ("FusedAdamW: the weight average (EMA) cannot be kept with sharded optimizer state (shard_state): a slice owner "
+                    "would average only its slice of every flat buffer")
+
+    def set_ema(self, decay, warmup=True):
+        """``decay``: keep ``ema = decay_t * ema + (1 - decay_t) * p`` after every applied step, a float strictly inside (0, 1) (None:
+        off).  ``warmup``: ``decay_t = min(decay, (1 + t) / (10 + t))`` at applied step ``t`` (timm), else ``decay_t = decay``.  Call
+        before the first step: the average starts as a copy of the weights that step finds."""
+        if self._flat_state:
+            raise RuntimeError("FusedAdamW.set_ema: call before the first step (the average starts from the initial weights and is "
+                               "allocated with the moments)")
+        if decay is not None:
+            if isinstance(decay, bool) or not isinstance(decay, (int, float)):
+                raise ValueError(f"FusedAdamW: ema_decay={decay!r} must be a float strictly inside (0, 1) (None: no average)")
+            decay = float(decay)
+            if not 0.0 < decay < 1.0:
+                raise ValueError(f"FusedAdamW: ema_decay={decay!r} must be a float strictly inside (0, 1) (None: no average)")
+            if self._shard is not None:
+                raise RuntimeError(self._EMA_SHARDED)
+        self._ema_decay = decay
+        self._ema_warmup = bool(warmup)
+        return self
+
+    def ema_enabled(self):
+        return self._ema_decay is not None
+
+    def _ema_pairs(self):
+        """(flat buffer, its average) of every valid flat buffer whose average exists (none before the first step)."""
+        out = []
+        for f in self._flats:
+            if not f.valid():
+                continue
+            key = tuple(id(p) for p in f.params)
+            st = self._flat_state.get(id(f)) or next((v for v in self._flat_state.values() if v.get("key") == key), None)
+            if st is not None and "ema" in st and st["ema"].numel() == f.data.numel():
+                out.append((f, st["ema"]))
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the parameters ARE the averaged weights: every flat buffer is swapped with its average in place
+        (``bsclip_swap_f32``, one launch per buffer, no third buffer) and swapped back on exit, also when the block raises.  The
+        engines read the flat buffers on every forward and a captured graph holds their addresses, which stay: nothing is rebuilt.
+        Before the first step the average equals the weights and nothing is launched.  No step may run inside the block."""
+        if self._ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_weights: the weight average is off (ema_decay / set_ema)")
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.ema_weights: already inside an ema_weights() block")
+        pairs = self._ema_pairs()
+        if pairs and pairs[0][0].data.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.ema_weights: a stream is capturing (the swap belongs between replays, not into a graph)")
+        for f, ema in pairs:
+            ops.swap_f32(f.data, ema)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            for f, ema in pairs:
+                ops.swap_f32(f.data, ema)
+
+    def ema_effective_decay(self):
+        """``decay_t`` of the applied-step count reached so far, the decay the last applied step used (with skipping on: one
+        read-back of the device's step word).  None when the average is off."""
+        if self._ema_decay is None:
+            return None
+        st = next((s for s in self._flat_state.values() if "ema" in s), None)
+        t = self._true_step(st) if st is not None else 0
+        return min(self._ema_decay, (1.0 + t) / (10.0 + t)) if self._ema_warmup else self._ema_decay
 
     def set_grad_clip(self, max_grad_norm, skip_nonfinite=True):
         """``max_grad_norm``: clip the global gradient norm to it (None or +inf: no clipping).  ``skip_nonfinite``: leave parameters,
@@ -85,6 +166,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
             self._shard = None
             return self
+        if self._ema_decay is not None:
+            raise RuntimeError(self._EMA_SHARDED)
         if self._flat_state:
             raise RuntimeError("FusedAdamW.shard_state: call before the first step (moments are already allocated unsharded)")
         self._shard = (dist.get_rank(group), dist.get_world_size(group), group)
@@ -171,7 +254,9 @@ class FusedAdamW(torch.optim.Optimizer):
         """Adam moments of this rank's slice of one flat buffer (the whole buffer when unsharded).  Keyed by the PARAMETERS the buffer
         holds (they outlive an engine rebuild: a checkpoint loaded mid-run, a precision switch), not by the buffer object.  Unsharded,
         every parameter's part is also published in ``self.state[p]`` as views (``exp_avg``, ``exp_avg_sq``, ``step``) so
-        ``state_dict()`` / ``load_state_dict()`` carry the moments like torch.optim.AdamW's do."""
+        ``state_dict()`` / ``load_state_dict()`` carry the moments like torch.optim.AdamW's do.  With the weight average on, ``ema``
+        lives and travels with them: a copy of the parameters as the first step finds them, carried over a rebuild, restored from a
+        loaded state."""
         key = tuple(id(p) for p in f.params)
         lo, hi = self._slice_of(f)
         st = self._flat_state.get(id(f))
@@ -180,9 +265,15 @@ class FusedAdamW(torch.optim.Optimizer):
         prev = next((v for v in self._flat_state.values() if v.get("key") == key and v.get("slice") == (lo, hi)), None)
         st = {"m": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device),
               "v": torch.zeros(hi - lo, dtype=f.data.dtype, device=f.data.device), "step": 0, "key": key, "slice": (lo, hi)}
+        ema = self._ema_decay is not None
+        if ema:
+            st["ema"] = torch.empty(hi - lo, dtype=torch.float32, device=f.data.device)
+            st["ema"].copy_(f.data[lo:hi])            # timm's deep copy at construction: the weights before the first update
         if prev is not None:                          # engine rebuilt (checkpoint loaded mid-run): the optimisation continues, it does not restart
             st["m"].copy_(prev["m"])
             st["v"].copy_(prev["v"])
+            if ema and "ema" in prev:
+                st["ema"].copy_(prev["ema"])
             st["step"] = self._true_step(prev)
         elif self._shard is None:                     # moments restored by load_state_dict() before the buffer existed
             for p, o in zip(f.params, f.offsets):
@@ -191,12 +282,16 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["m"][o:o + p.numel()].copy_(ps["exp_avg"].reshape(-1).to(st["m"].device))
                     st["v"][o:o + p.numel()].copy_(ps["exp_avg_sq"].reshape(-1).to(st["v"].device))
                     st["step"] = max(st["step"], int(ps.get("step", 0)))
+                    if ema and "ema" in ps and ps["ema"].numel() == p.numel():
+                        st["ema"][o:o + p.numel()].copy_(ps["ema"].reshape(-1).to(st["ema"].device))
         self._flat_state = {k: v for k, v in self._flat_state.items() if v.get("key") != key}
         self._flat_state[id(f)] = st
         if self._shard is None:
             for p, o in zip(f.params, f.offsets):
                 self.state[p] = {"step": st["step"], "exp_avg": st["m"][o:o + p.numel()].view(p.shape),
                                  "exp_avg_sq": st["v"][o:o + p.numel()].view(p.shape)}
+                if ema:
+                    self.state[p]["ema"] = st["ema"][o:o + p.numel()].view(p.shape)
         return st
 
     def state_dict(self):
@@ -265,16 +360,21 @@ class FusedAdamW(torch.optim.Optimizer):
     def _step_flat(self, f, g, capturing, clip):
         """The update of this rank's slice of flat buffer ``f`` with param group ``g``'s hyperparameters: exactly one of ``adamw_step``
         (lr and step as launch arguments), ``adamw_step_dev`` (device hyper) and, with ``clip`` the norm pass's device record,
-        ``counter_add_if`` + ``adamw_step_clip``.  The step word of the ``hyper`` pair lives on the device so that no in-flight node
-        ever reads host memory.  Device hyper: it is the host's count, set by a fill that carries the value as a launch argument, or
+        ``counter_add_if`` + ``adamw_step_clip``; with the weight average on ``adamw_step_ema`` takes the place of all three (it reads
+        lr and step from the device pair in every mode, and the record when there is one).  The step word of the ``hyper`` pair lives
+        on the device so that no in-flight node ever reads host memory.  Device hyper: it is the host's count, set by a fill that carries the value as a launch argument, or
         under capture advanced by a ``counter_add`` node on every replay.  Clipping: it is filled once, when the pair is created, and
         from then on only advanced on the device, by ``counter_add_if``: it counts APPLIED steps, ``st["step"]`` attempted ones."""
         st = self._state_for(f)
         lo, hi = self._slice_of(f)
-        # device hyper: an empty slice launches nothing and gets no pair; clipping: every buffer gets one (an empty slice's stays as filled)
-        if "hyper" not in st and (clip is not None or (self._dev_hyper and hi > lo)):
+        ema = self._ema_decay is not None
+        # device hyper: an empty slice launches nothing and gets no pair; clipping and the weight average: every buffer gets one (an
+        # empty slice's stays as filled)
+        if "hyper" not in st and (clip is not None or ema or (self._dev_hyper and hi > lo)):
             if capturing:
-                raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing")
+                raise RuntimeError("FusedAdamW: run one eager step with device-side (lr, step) before capturing (with the weight "
+                                   "average on, its buffer is allocated there too)" if ema else
+                                   "FusedAdamW: run one eager step with device-side (lr, step) before capturing")
             st["hyper"] = torch.zeros(2, dtype=torch.int32, device=f.data.device)   # [lr as f32 bits, step as uint32]
             if clip is not None:
                 st["hyper"][1:2].fill_(st["step"])
@@ -283,7 +383,7 @@ class FusedAdamW(torch.optim.Optimizer):
             return
         fdata, fgrad = (f.data, f.grad) if self._shard is None else (f.data[lo:hi], f.grad[lo:hi])
         (beta1, beta2), eps, wd = g["betas"], g["eps"], g["weight_decay"]
-        if clip is None and not self._dev_hyper:
+        if clip is None and not self._dev_hyper and not ema:
             ops.adamw_step(fdata, fgrad, st["m"], st["v"], g["lr"], beta1, beta2, eps, wd, st["step"])
             return
         if clip is None:
@@ -293,10 +393,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["hyper"][1:2].fill_(st["step"])                 # value travels as a launch argument
         if not capturing:
             self._stage_lr(st, g["lr"])
-        if clip is None:
+        if clip is not None:
+            ops.counter_add_if(st["hyper"][1:2], 1, clip[0:1])
+        if ema:
+            ops.adamw_step_ema(fdata, fgrad, st["m"], st["v"], st["ema"], st["hyper"], clip, beta1, beta2, eps, wd, self._ema_decay,
+                               self._ema_warmup)
+        elif clip is None:
             ops.adamw_step_dev(fdata, fgrad, st["m"], st["v"], st["hyper"], beta1, beta2, eps, wd)
         else:
-            ops.counter_add_if(st["hyper"][1:2], 1, clip[0:1])
             ops.adamw_step_clip(fdata, fgrad, st["m"], st["v"], st["hyper"], clip, beta1, beta2, eps, wd)
 
     @torch.no_grad()
@@ -311,6 +415,14 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._clip_on and loose:
             raise RuntimeError("FusedAdamW: gradient clipping / skipping needs every trainable tensor in an engine's flat "
                                "buffer (the norm is formed over the flat gradient buffers)")
+        if self._ema_decay is not None:
+            if self._shard is not None:
+                raise RuntimeError(self._EMA_SHARDED)
+            if loose:
+                raise RuntimeError("FusedAdamW: the weight average (EMA) needs every trainable tensor in an engine's flat buffer (it "
+                                   "is kept per flat buffer, inside the fused update)")
+            if self._ema_swapped:
+                raise RuntimeError("FusedAdamW: no step inside an ema_weights() block (the flat buffers hold the average there)")
         clip = self._norm_pass(flats, capturing) if self._clip_on and flats else None
         for f in flats:
             if clip is None:

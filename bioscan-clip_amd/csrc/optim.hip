@@ -498,11 +498,15 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ g,
     }
 }
 
-// The AdamW update of a workgroup's elements (grid-stride, 256 threads), the one body of the three kernels below: what they compute
+// The AdamW update of a workgroup's elements (grid-stride, 256 threads), the one body of the AdamW kernels below: what they compute
 // stays equal bit for bit because it is the same code.
+// EMA: the thread that stored p[i] also moves the weight average towards it, ema[i] += ema_w * (p[i] - ema[i]) --
+// torch's lerp_(p, w) on the value still in its register; ema overlaps none of p, g, m, v.
+template <bool EMA = false>
 __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                              float* __restrict__ v, long n, float lr, float beta1, float beta2, float eps, float wd,
-                                             float inv_bc1, float inv_sqrt_bc2, float grad_scale) {
+                                             float inv_bc1, float inv_sqrt_bc2, float grad_scale, float* __restrict__ ema = nullptr,
+                                             float ema_w = 0.f) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float gi = g[i] * grad_scale;
         float pi = p[i] * (1.0f - lr * wd);
@@ -511,6 +515,10 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float*
         const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
         pi -= (lr * inv_bc1) * (mi / denom);
         p[i] = pi;
+        if constexpr (EMA) {
+            const float e = ema[i];
+            ema[i] = e + ema_w * (pi - e);
+        }
         m[i] = mi;
         v[i] = vi;
     }
@@ -744,7 +752,7 @@ extern "C" int bsclip_colsum(const void* g, int ld_g, int g_is_bf16, int M, int 
     return BSCLIP_OK;
 }
 
-static unsigned adamw_grid(int64_t n) {   // the three AdamW kernels: 256 elements per workgroup, grid-stride beyond 2048 workgroups
+static unsigned adamw_grid(int64_t n) {   // AdamW kernels, swap_f32: 256 elements per workgroup, grid-stride beyond 2048 workgroups
     const int64_t blocks = (n + 255) / 256;
     return (unsigned)(blocks > 2048 ? 2048 : blocks);
 }
@@ -870,6 +878,41 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, 
     adamw_update(p, g, m, v, n, h.lr, beta1, beta2, eps, wd, h.inv_bc1, h.inv_sqrt_bc2, grad_scale);
 }
 
+// adamw_dev_kernel (CLIP = false, state unused) or adamw_clip_kernel (CLIP = true) with the weight average updated by the same thread
+// (adamw_update<true>).  The average's weight w = 1 - d_t is one value per launch, formed in f64 from the step word like the bias
+// corrections: t counts applied steps, this one included; warm-up caps the decay at (1 + t) / (10 + t).
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, float* __restrict__ ema, long n,
+                                                         const float* __restrict__ hyper, const unsigned* __restrict__ state,
+                                                         float beta1, float beta2, float eps, float wd, float ema_decay,
+                                                         int ema_warmup) {
+    float grad_scale = 1.0f;
+    if constexpr (CLIP) {
+        if (state[0] == 0u) return;
+        grad_scale = __uint_as_float(state[1]);
+    }
+    const AdamwHyper h = adamw_hyper(hyper, beta1, beta2);
+    const double t = (double)reinterpret_cast<const unsigned*>(hyper)[1];
+    const double d_t = ema_warmup ? fmin((double)ema_decay, (1.0 + t) / (10.0 + t)) : (double)ema_decay;
+    const float w = (float)(1.0 - d_t);
+    adamw_update<true>(p, g, m, v, n, h.lr, beta1, beta2, eps, wd, h.inv_bc1, h.inv_sqrt_bc2, grad_scale, ema, w);
+}
+
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
+// true when the n-float ranges at a and b share no byte
+inline bool disjoint_f32(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * sizeof(float);
+    return x + bytes <= y || y + bytes <= x;
+}
+
 }  // namespace
 
 extern "C" int64_t bsclip_grad_norm_partials(int64_t n) {
@@ -925,6 +968,38 @@ extern "C" int bsclip_adamw_step_clip(float* p, const float* g, float* m, float*
     BSCLIP_REQUIRE(aligned_to(16, state), "bsclip_adamw_step_clip: state must be 16-byte aligned");
     hipLaunchKernelGGL(adamw_clip_kernel, dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, (long)n,
                        hyper_dev, static_cast<const unsigned*>(state), beta1, beta2, eps, weight_decay);
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_adamw_step_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* hyper_dev,
+                                     const void* clip_state, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                                     int ema_warmup, void* stream) {
+    BSCLIP_REQUIRE(p && g && m && v, "bsclip_adamw_step_ema: null pointer among p, g, m, v");
+    BSCLIP_REQUIRE(ema, "bsclip_adamw_step_ema: ema is null");
+    BSCLIP_REQUIRE(hyper_dev, "bsclip_adamw_step_ema: hyper_dev is null");
+    BSCLIP_REQUIRE(n > 0, "bsclip_adamw_step_ema: n=%ld must be positive", (long)n);
+    BSCLIP_REQUIRE(aligned_to(4, p, g, m, v, ema, hyper_dev), "bsclip_adamw_step_ema: p, g, m, v, ema and hyper_dev must be 4-byte aligned");
+    BSCLIP_REQUIRE(aligned_to(16, clip_state), "bsclip_adamw_step_ema: clip_state must be 16-byte aligned (or NULL)");
+    BSCLIP_REQUIRE(ema_decay > 0.f && ema_decay < 1.f, "bsclip_adamw_step_ema: ema_decay=%g must lie strictly inside (0, 1)",
+                   (double)ema_decay);
+    BSCLIP_REQUIRE(disjoint_f32(ema, p, n) && disjoint_f32(ema, g, n) && disjoint_f32(ema, m, n) && disjoint_f32(ema, v, n),
+                   "bsclip_adamw_step_ema: ema must not alias p, g, m or v");
+    pick_bool(clip_state != nullptr, [&](auto clip) {
+        hipLaunchKernelGGL((adamw_ema_kernel<decltype(clip)::value>), dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           p, g, m, v, ema, (long)n, hyper_dev, static_cast<const unsigned*>(clip_state), beta1, beta2, eps, weight_decay,
+                           ema_decay, ema_warmup);
+    });
+    BSCLIP_LAUNCH_CHECK();
+    return BSCLIP_OK;
+}
+
+extern "C" int bsclip_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    BSCLIP_REQUIRE(a && b, "bsclip_swap_f32: null pointer");
+    BSCLIP_REQUIRE(n > 0, "bsclip_swap_f32: n=%ld must be positive", (long)n);
+    BSCLIP_REQUIRE(aligned_to(4, a, b), "bsclip_swap_f32: a and b must be 4-byte aligned");
+    BSCLIP_REQUIRE(disjoint_f32(a, b, n), "bsclip_swap_f32: a and b must not be the same or overlapping ranges");
+    hipLaunchKernelGGL(swap_f32_kernel, dim3(adamw_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, (long)n);
     BSCLIP_LAUNCH_CHECK();
     return BSCLIP_OK;
 }

@@ -15,8 +15,12 @@ AdamW (+ optional one_cycle / exponential / step / cosine scheduler, stepped per
     augmentation chain and 5-mer tokeniser as HIP kernels, bioscanclip/util/gpu_pipeline.py);
   * the per-epoch evaluation (``eval_phase``, reference train_cl.py:217-243) runs natively: feature extraction with the HIP
     encoders and top-k retrieval with ``bsclip_topk_ip`` in place of faiss, on the synthetic evaluation loaders
-    (``synthetic_eval=true``) or on the val splits of a directory of shard splits (``eval_shards=<root>``, ``eval_phase_shards``).
+    (``synthetic_eval=true``) or on the val splits of a directory of shard splits (``eval_shards=<root>``, ``eval_phase_shards``);
+  * ``model_config.ema_decay=<float>`` (no reference counterpart): an exponential moving average of the trainable
+    weights kept inside the fused AdamW step; the per-epoch evaluation and ``best.pth`` use the averaged weights, ``last_ema.pth``
+    holds them beside ``last.pth`` (the raw weights, the state training continues from).
 """
+import contextlib
 import datetime
 import os
 import sys
@@ -190,6 +194,36 @@ def grad_clip_options(args):
     return norm, True
 
 
+def ema_options(args, world_size=1):
+    """``model_config.ema_decay=<float>`` (timm's ``--model-ema-decay``): keep an exponential moving average of the trainable weights
+    inside the fused AdamW step, evaluate it every epoch and save it as ``last_ema.pth`` / ``best.pth``.
+    ``model_config.ema_warmup=true|false`` (default true): ``decay_t = min(decay, (1 + t) / (10 + t))`` at applied step ``t``.  Returns
+    ``(decay or None, warmup)``, ``(None, True)`` when the key is absent; a decay that is not a number strictly inside (0, 1) is refused
+    here, before the model is built, and so is the average together with sharded optimizer state (more than one rank and
+    ``disable_lora``: a slice owner would average only its slice)."""
+    mc = getattr(args, "model_config", None)
+    raw = getattr(mc, "ema_decay", None)
+    warm = getattr(mc, "ema_warmup", True)
+    if isinstance(warm, str):
+        if warm.strip().lower() not in ("true", "false"):
+            raise ValueError(f"model_config.ema_warmup must be true or false, got {warm!r}")
+        warm = warm.strip().lower() == "true"
+    elif not isinstance(warm, bool):
+        raise ValueError(f"model_config.ema_warmup must be true or false, got {warm!r}")
+    if raw is None or raw == "":
+        return None, warm
+    try:
+        decay = float(raw)
+    except (TypeError, ValueError):
+        decay = float("nan")
+    if isinstance(raw, bool) or not 0.0 < decay < 1.0:
+        raise ValueError(f"model_config.ema_decay must be a number strictly inside (0, 1), got {raw!r}")
+    if world_size > 1 and getattr(mc, "disable_lora", False):
+        raise ValueError(f"model_config.ema_decay: the weight average is not kept with sharded optimizer state (full fine-tuning on "
+                         f"world_size={world_size} ranks shards the AdamW moments; a slice owner would average only its slice)")
+    return decay, warm
+
+
 def memory_bank_size(args, world_size=1):
     """``model_config.memory_bank_size``: the slots per modality of the cross-batch memory (``MemoryBankContrastiveLoss``), or None
     when the key is absent (off).  A multiple of 256 in 256 .. 16384 and at least the batch size; refused together with
@@ -210,6 +244,7 @@ def memory_bank_size(args, world_size=1):
 def main_process(rank: int, world_size: int, args):
     towers16 = fp16_towers(args)
     max_grad_norm, skip_nonfinite = grad_clip_options(args)
+    ema_decay, ema_warmup = ema_options(args, world_size)
     jpeg_entropy = jpeg_entropy_mode(args)
     if getattr(args, "debug_flag", False) or rank != 0:
         args.activate_wandb = False
@@ -255,6 +290,7 @@ def main_process(rank: int, world_size: int, args):
     if hasattr(mc, 'lr_config') and hasattr(mc.lr_config, 'lr'):
         lr = mc.lr_config.lr
     optimizer = FusedAdamW(model.parameters(), lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    optimizer.set_ema(ema_decay, ema_warmup)
     if world_size > 1 and getattr(mc, "disable_lora", False):
         # full fine-tuning on several ranks: each rank keeps the AdamW moments of one slice of every flat buffer (3.2 GB / W for
         # I+D+T instead of 3.2 GB per rank) and broadcasts its updated slice (hip/optim.py shard_state)
@@ -312,18 +348,23 @@ def main_process(rank: int, world_size: int, args):
                 last_ckpt_path = os.path.join(folder_path, 'last.pth')
                 torch.save(model.state_dict(), last_ckpt_path)  # reference key names: loadable by the reference
                 print(f'Last ckpt: {last_ckpt_path}')
-            if eval_loaders is not None:
-                if eval_source(args) == "shards":
-                    acc_dict, _ = eval_phase_shards(model, device, eval_loaders, k_list, args)
-                else:
-                    acc_dict, _ = eval_phase(model, device, *eval_loaders, k_list, args=args, rank=rank)
-                cell = acc_dict['encoded_image_feature']['encoded_image_feature']
-                overall_acc = (cell['seen']['micro_acc'][1]['species'] + cell['unseen']['micro_acc'][1]['species']) / 2
-                if best_overall_acc is None or best_overall_acc < overall_acc:
-                    best_epoch, best_overall_acc = epoch, overall_acc
-                    if folder_path is not None:
-                        torch.save(model.state_dict(), os.path.join(folder_path, 'best.pth'))
-                print(f'epoch {epoch}: overall_acc {overall_acc:.4f} (best {best_overall_acc:.4f} @ {best_epoch})')
+            # model_config.ema_decay: the averaged weights are the ones evaluated and shipped -- swapped into the flat buffers in place
+            # for the evaluation and the two checkpoints made from it, swapped back before the next epoch trains on the raw ones
+            with optimizer.ema_weights() if ema_decay is not None else contextlib.nullcontext():
+                if ema_decay is not None and folder_path is not None:
+                    torch.save(model.state_dict(), os.path.join(folder_path, 'last_ema.pth'))  # reference key names, as last.pth
+                if eval_loaders is not None:
+                    if eval_source(args) == "shards":
+                        acc_dict, _ = eval_phase_shards(model, device, eval_loaders, k_list, args)
+                    else:
+                        acc_dict, _ = eval_phase(model, device, *eval_loaders, k_list, args=args, rank=rank)
+                    cell = acc_dict['encoded_image_feature']['encoded_image_feature']
+                    overall_acc = (cell['seen']['micro_acc'][1]['species'] + cell['unseen']['micro_acc'][1]['species']) / 2
+                    if best_overall_acc is None or best_overall_acc < overall_acc:
+                        best_epoch, best_overall_acc = epoch, overall_acc
+                        if folder_path is not None:
+                            torch.save(model.state_dict(), os.path.join(folder_path, 'best.pth'))
+                    print(f'epoch {epoch}: overall_acc {overall_acc:.4f} (best {best_overall_acc:.4f} @ {best_epoch})')
     if world_size > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -350,6 +391,7 @@ def main(argv=None):
         raise ValueError(f"model_config.contrastive_loss=sigmoid: the sigmoid loss is not built for more than one rank "
                          f"(world_size={world_size})")
     memory_bank_size(args, world_size)   # refused before the model is built
+    ema_options(args, world_size)        # likewise: a bad decay, or the average together with sharded optimizer state
     return main_process(rank, world_size, args)
 
 

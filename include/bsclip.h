@@ -835,6 +835,20 @@ int bsclip_counter_add_if(uint32_t* counter, uint32_t inc, const uint32_t* cond,
 int bsclip_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, const void* state,
                            float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- exponential moving average of the weights inside the AdamW update (timm ModelEmaV2 / V3), capturable.
+ * adamw_step_ema: with clip_state == NULL bsclip_adamw_step_dev's arithmetic with grad_scale = 1, otherwise bsclip_adamw_step_clip's on
+ *   that record (gradient times coef; no store at all, ema included, when the record's apply is 0); p, m, v receive the bits those
+ *   entry points leave.  The thread that stored the new p[i] then does ema[i] += w * (p[i] - ema[i]) (torch's lerp_(p, w)), one f32 w
+ *   per launch formed in f64 on the device: t = hyper_dev[1] (the uint32 step word: applied steps, this one included),
+ *   d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay, w = (float)(1 - d_t).  0 < ema_decay < 1; ema [n] f32 shares
+ *   no byte with p, g, m, v; clip_state 16-byte aligned.  Same grid as the other AdamW entry points.
+ * swap_f32: a[i] <-> b[i] for i < n (evaluating the averaged weights in place, then putting the raw ones back); a and b must not be
+ *   the same or overlapping ranges. */
+int bsclip_adamw_step_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* hyper_dev,
+                          const void* clip_state, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                          int ema_warmup, void* stream);
+int bsclip_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
